@@ -18,10 +18,22 @@ Other BASELINE configurations (same JSON schema; the default above is what the d
     --mode clip | stream (streaming_forward: rings + HIP graphs, chunked) | perframe (feedin_one_element, one graph per frame)
     --scaling strong --total-frames 80   one fixed clip split over the ranks (N=1 and N=8 run the same C4 clip)
 
-Prints ONE JSON line on rank 0.  ``value`` = total frames / max-over-ranks wall time of the K timed steps.
+Prints ONE JSON line on rank 0.  ``value`` = total frames / max-over-ranks wall time of the K timed steps;
+``ms_per_step`` = that wall time / K.  A plain run does only that: set-up, warmup, the K timed steps, the line.
+
+``--dump-outputs DIR`` writes, after the timed steps, the output of the last timed step (what the caller of the
+timed path receives) as DIR/output.npy (float32; DIR/output_rank<r>.npy per rank when N > 1).  The inputs and the
+weights are seeded, so two builds run with the same arguments can be compared output for output.  An output larger
+than DUMP_LIMIT_BYTES is cut to a fixed, seeded sample of whole frames (the frame indices go into the JSON line).
+
+``--full`` adds what takes runs of its own, after the timed region (the line gains these keys):
 ``roofline``: per-launch HIP-event timing (on the stream the kernels run on) of the dominant kernel
-against the fp32-MFMA peak.  ``cpu_baseline``: the oracle's streaming restatement (same oneDNN conv calls
-as the reference's CPU forward) timed on this box's host cores on a bounded sample (rank 0, N=1 only).
+against the MFMA peak (clip schedule: events around every launch of the timed steps, so in a --full run
+those steps carry two event records per launch).  ``other_mode`` + ``parity``: the other arithmetic mode on
+the same clip.  ``power`` + ``sustained``: rocm-smi power / clock while the step loops.  ``box_calibration`` +
+``value_normalised``: two fixed layers timed on seeded operands.  ``cpu_baseline``: the oracle's streaming
+restatement (same oneDNN conv calls as the reference's CPU forward) timed on this box's host cores on a
+bounded sample (rank 0, N=1 only).
 """
 import argparse
 import json
@@ -87,6 +99,24 @@ def output_digests(y, first_frame, block=10):
         lo = b * block - first_frame
         out[b] = hashlib.sha256(y[lo:lo + block].contiguous().cpu().numpy().tobytes()).hexdigest()[:16]
     return out
+
+
+DUMP_LIMIT_BYTES = 64 * 10 ** 6     # --dump-outputs: at most this many bytes of arrays, over all ranks
+
+
+def dump_outputs(y, out_dir, rank, world):
+    """Writes this rank's output `y` as float32 .npy under `out_dir`: whole if it fits in this rank's share of DUMP_LIMIT_BYTES,
+    else every `stride`-th element of it in C order (a fixed sample, the same for every build).  Returns (file name, stride)."""
+    import numpy as np
+    a = y.detach().float().cpu().numpy()
+    fit = (DUMP_LIMIT_BYTES // world - 128) // 4                       # float32 values per rank; 128: the .npy header
+    stride = 1 if a.size <= fit else -(-a.size // fit)
+    if stride > 1:
+        a = np.ascontiguousarray(a.reshape(-1)[::stride])
+    name = "output.npy" if world == 1 else "output_rank%d.npy" % rank
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, name), a)
+    return name, stride
 
 
 def build_model(device, precision="fp32", blind=False, wide_conv="auto", fuse_pairs="auto", f32_handover="auto", v_handover="auto"):
@@ -504,7 +534,13 @@ def main():
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="weak: --frames per GPU (the job grows with N); strong: one clip of --total-frames split over the ranks")
     ap.add_argument("--total-frames", type=int, default=80, help="--scaling strong: frames of the whole clip (C4: 80)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own after the timed region: per-kernel roofline, the other arithmetic "
+                         "mode + parity, power / sustained rate, box calibration, CPU baseline (a plain run times the K steps only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's output to DIR/output.npy (float32, at most DUMP_LIMIT_BYTES: a fixed strided "
+                         "sample beyond that)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--fuse-pairs", default="auto", choices=["auto", "on", "off"],
                     help="the 64-channel full-resolution conv pairs as one launch each (BSVD(fuse_pairs=...); auto = the product default)")
     ap.add_argument("--f32-handover", default="auto", choices=["auto", "on", "off"],
@@ -516,8 +552,8 @@ def main():
     ap.add_argument("--output-digest", action="store_true",
                     help="add `output_digest`: sha256 of every 10-frame block of the job's output (all ranks, in frame order) -- N = 1 and N = 8 "
                          "of --scaling strong run the same clip and must print the same list")
-    ap.add_argument("--no-box-calibration", action="store_true", help="skip the two fixed calibration layers (~2 s) after the timed region")
-    ap.add_argument("--no-power-probe", action="store_true", help="skip the 2.5 s rocm-smi power / clock sample after the timed region")
+    ap.add_argument("--no-box-calibration", action="store_true", help="--full: skip the two fixed calibration layers (~2 s) after the timed region")
+    ap.add_argument("--no-power-probe", action="store_true", help="--full: skip the 5 s rocm-smi power / clock sample after the timed region")
     ap.add_argument("--precision", default=DEFAULT_PRECISION, choices=["fp32", "f16x3"],
                     help="fp32: exact fp32 MFMA; f16x3: split-fp16 3-pass MFMA, fp32 accumulate (fp32-class accuracy)")
     args = ap.parse_args()
@@ -526,6 +562,8 @@ def main():
     mode = args.mode or wl["mode"]
     steps = args.steps if args.steps is not None else (30 if args.workload == "c1" else 5)
     warmup = args.warmup if args.warmup is not None else (5 if args.workload == "c1" else 2)
+    if steps < 1 or warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -634,16 +672,14 @@ def main():
                 timer.detach()
                 agg = timer.summary()
             model.bench_power = power_probe(step, probe_s) if (probe_s > 0 and world == 1) else None
-            if timer:
-                pass
-            elif instrument:
+            model.bench_stream_stats = None
+            if mode != "clip" and model._stream_engs:
+                e = list(model._stream_engs.values())[-1]
+                model.bench_stream_stats = dict(e.stats, chunk=e.chunk, ring_GB=round(e.ring_bytes / 1e9, 2),
+                                                graphs=sum(1 for g in e.graphs.values() if g[0]), plans=len(e.plans))
+            if instrument and mode != "clip":
                 # stream schedules replay HIP graphs (no per-launch host call to bracket): the per-kernel table comes from one
                 # extra, untimed pass of the same step with the engine issuing the same plans layer by layer
-                model.bench_stream_stats = None
-                if model._stream_engs:
-                    e = list(model._stream_engs.values())[-1]
-                    model.bench_stream_stats = dict(e.stats, chunk=e.chunk, ring_GB=round(e.ring_bytes / 1e9, 2),
-                                                    graphs=sum(1 for g in e.graphs.values() if g[0]), plans=len(e.plans))
                 for e in model._stream_engs.values():
                     e.layerwise = True
                 timer = LaunchTimer(ex)
@@ -725,15 +761,18 @@ def main():
                 "conv_ms_per_step": sum(v["ms"] for v in agg.values()) / steps}
 
     # ---- the timed job (headline) ...
-    model, elapsed, agg, y = timed_run(args.precision, steps, warmup, args.prewarm_s, probe_s=0.0 if args.no_power_probe else 5.0)
+    model, elapsed, agg, y = timed_run(args.precision, steps, warmup, args.prewarm_s, instrument=args.full,
+                                       probe_s=5.0 if (args.full and not args.no_power_probe) else 0.0)
+    dumped = dump_outputs(y, args.dump_outputs, rank, world) if args.dump_outputs else None
     stream_stats = getattr(model, "bench_stream_stats", None)
     model.release_stream_buffers()
-    # ---- ... and, outside it, the other arithmetic mode on the same clip for reference + a live parity figure
-    other = "fp32" if args.precision == "f16x3" else "f16x3"
-    steps_o = max(1, min(steps, 3))
-    model_o, elapsed_o, agg_o, y_o = timed_run(other, steps_o, 1)
-    model_o.release_stream_buffers()
-    parity = float((y.float() - y_o.float()).abs().max())
+    if args.full:
+        # ---- ... and, outside it, the other arithmetic mode on the same clip for reference + a live parity figure
+        other = "fp32" if args.precision == "f16x3" else "f16x3"
+        steps_o = max(1, min(steps, 3))
+        model_o, elapsed_o, agg_o, y_o = timed_run(other, steps_o, 1)
+        model_o.release_stream_buffers()
+        parity = float((y.float() - y_o.float()).abs().max())
 
     if rank == 0:
         total_frames = frames * world * steps
@@ -769,14 +808,18 @@ def main():
             "path_tflops": fps * flop_per_frame / 1e12,
             "path_frac_of_mfma_peak": fps * flop_per_frame / 1e12 /
                                       ((PEAK_F32_MFMA_TFLOPS if args.precision == "fp32" else PEAK_F16_MFMA_TFLOPS) * world),
-            "roofline": roofline_of(agg, args.precision, steps),
-            "parity": {"max_abs_f16x3_vs_exact_fp32_on_this_clip": parity, "budget": 1e-3,
-                       "note": "north_star: <= 1e-3 max-abs vs the fp32 forward; tests/test_gpu_f16x3.py pins 3-6e-5 vs "
-                               "the reference goldens"},
-            "other_mode": {"dtype": "f32" if other == "fp32" else "f16x3", "value": frames * world * steps_o / elapsed_o,
-                           "unit": "frames/s", "steps": steps_o, "ms_per_step": elapsed_o / steps_o * 1e3,
-                           "roofline": roofline_of(agg_o, other, steps_o)},
         }
+        if args.full:
+            out["roofline"] = roofline_of(agg, args.precision, steps)
+            out["parity"] = {"max_abs_f16x3_vs_exact_fp32_on_this_clip": parity, "budget": 1e-3,
+                             "note": "north_star: <= 1e-3 max-abs vs the fp32 forward; tests/test_gpu_f16x3.py pins 3-6e-5 vs "
+                                     "the reference goldens"}
+            out["other_mode"] = {"dtype": "f32" if other == "fp32" else "f16x3", "value": frames * world * steps_o / elapsed_o,
+                                 "unit": "frames/s", "steps": steps_o, "ms_per_step": elapsed_o / steps_o * 1e3,
+                                 "roofline": roofline_of(agg_o, other, steps_o)}
+        if dumped:
+            out["dump_outputs"] = {"dir": args.dump_outputs, "file": dumped[0], "stride": dumped[1], "dtype": "float32",
+                                   "of": "the last timed step's output; stride > 1: every stride-th element in C order"}
         pw = getattr(model, "bench_power", None)
         if pw:
             # what the dominant kernel's MFMA work is against the matrix-pipe peak AT THE CLOCK THE CHIP ACTUALLY RUNS (2.4 GHz nominal)
@@ -794,7 +837,7 @@ def main():
             out["sustained"] = {"value": frames * pw["loop_steps"] / pw["loop_seconds"], "unit": "frames/s", "seconds": pw["loop_seconds"],
                                 "sclk_mhz": pw["sclk_mhz"], "package_w": pw["package_w"],
                                 "note": "untimed loop of the same step after the timed region (N = 1); `value` above is the K-step burst"}
-        if world == 1 and not args.no_box_calibration and not wl["blind"]:
+        if args.full and world == 1 and not args.no_box_calibration and not wl["blind"]:
             try:
                 cal = box_calibration(model, x)
             except Exception as e:                                   # noqa: BLE001 - a measurement aid must never fail the bench
@@ -816,10 +859,10 @@ def main():
                            "expected": "16 exchanges per forward and rank; per forward an interior rank sends 2 x 99.5 MB (fp32 / "
                                        "split16 alike), the first and last rank 1 x 99.5 MB at 540x960",
                            "per_rank": getattr(model, "bench_halo_stats", None)}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             # bounded sample of the same workload: 10 frames of its geometry (4 at 1080p), the CPU path's cost is linear in frames
             out["cpu_baseline"] = cpu_baseline(model, h, w, wl["blind"], frames=4 if h * w > 540 * 960 else 10)
-        else:
+        elif args.full:
             out["cpu_baseline"] = None
         sys.stdout.flush()
         os.dup2(stdout_fd, 1)

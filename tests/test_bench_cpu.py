@@ -46,6 +46,30 @@ def test_stream_modes_refuse_more_than_one_rank():
     assert r.returncode != 0 and "not divisible" in (r.stderr + r.stdout)
 
 
+def test_step_counts_are_checked_before_any_device_work():
+    for argv in (("--steps", "0"), ("--warmup", "-1")):
+        r = _run(*argv)
+        assert r.returncode != 0 and "--steps must be >= 1" in (r.stderr + r.stdout), argv
+
+
+def test_dump_outputs_writes_float32_whole_or_a_fixed_strided_sample(tmp_path, monkeypatch):
+    """--dump-outputs: the output as it is when it fits in DUMP_LIMIT_BYTES (split evenly over the ranks), else every stride-th element in
+    C order -- the same elements on every run, so two builds can be compared output for output."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    y = torch.arange(2 * 3 * 4 * 5, dtype=torch.float32).reshape(2, 3, 4, 5)
+    assert bench.dump_outputs(y, str(tmp_path / "a"), 0, 1) == ("output.npy", 1)
+    a = np.load(tmp_path / "a" / "output.npy")
+    assert a.dtype == np.float32 and np.array_equal(a, y.numpy())
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 2 * (128 + 4 * 50))           # 50 values per rank over 2 ranks
+    assert bench.dump_outputs(y.double(), str(tmp_path / "b"), 1, 2) == ("output_rank1.npy", 3)
+    b = np.load(tmp_path / "b" / "output_rank1.npy")
+    assert b.dtype == np.float32 and np.array_equal(b, y.numpy().reshape(-1)[::3]) and b.nbytes <= 4 * 50
+    assert not os.path.exists(tmp_path / "b" / "output_rank0.npy")
+
+
 def test_power_probe_parses_rocm_smi_and_survives_its_absence(tmp_path, monkeypatch):
     """bench.power_probe: package power / cap / shader clock from rocm-smi's text (a stand-in on PATH prints the real tool's
     lines); without rocm-smi the probe returns None instead of failing the bench."""

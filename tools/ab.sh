@@ -11,7 +11,7 @@ for round in 1 2; do
   i=0
   for f in "$@"; do
     echo -n "[$round] '$f': "
-    BSVD_HIP_LIB=/tmp/libbsvd_ab$i.so python bench.py --no-cpu-baseline ${AB_BENCH_ARGS} 2>/dev/null | python -c "
+    BSVD_HIP_LIB=/tmp/libbsvd_ab$i.so python bench.py --full --no-cpu-baseline ${AB_BENCH_ARGS} 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); r=d['roofline']
 print('fps %.1f other %.1f' % (d['value'], d['other_mode']['value']), {k.replace('conv3x3_kernel',''):round(v['ms_per_step'],2) for k,v in r['all_conv_kernels'].items()}, {k.replace('conv3x3_kernel',''):round(v['ms_per_step'],2) for k,v in d['other_mode']['roofline']['all_conv_kernels'].items()})"

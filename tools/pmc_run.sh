@@ -1,6 +1,7 @@
 #!/bin/bash
 # Collects PMC counters for the bench workload in separate passes (guide: FETCH_SIZE and WRITE_SIZE cannot share
 # a pass; counters never combined with sys/hip tracing).  Usage on the GPU box: tools/pmc_run.sh <tag>
+REPO="$(cd "$(dirname "$0")/.." && pwd)"
 TAG=${1:-r01}
 OUT=$GRAFT_REPO_ROOT/gpurun_out/pmc_$TAG
 mkdir -p $OUT
@@ -11,7 +12,7 @@ for set in "SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_BUSY_CYCLES SQ_WAVES" \
            "FETCH_SIZE" "WRITE_SIZE"; do
   i=$((i+1))
   rocprofv3 --pmc $set --kernel-trace --output-format csv -d $OUT/pass$i -o pmc -- \
-     python $GRAFT_REPO_ROOT/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-power-probe --no-box-calibration ${BENCH_ARGS} > $OUT/pass$i.log 2>&1
+     python "$REPO"/bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-power-probe --no-box-calibration ${BENCH_ARGS} > $OUT/pass$i.log 2>&1
   echo "pass $i ($set): rc=$?"
 done
 find $OUT -name "*.csv" | head -20

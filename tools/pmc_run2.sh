@@ -1,5 +1,6 @@
 #!/bin/bash
 # Second-level PMC passes: instruction mix, VMEM latency as seen by the SQ, L1/L2 behaviour.
+REPO="$(cd "$(dirname "$0")/.." && pwd)"
 TAG=${1:-r01}
 OUT=$GRAFT_REPO_ROOT/gpurun_out/pmc2_$TAG
 mkdir -p $OUT
@@ -12,6 +13,6 @@ for set in "SQ_INSTS_VMEM_RD SQ_INST_LEVEL_VMEM SQ_INSTS_VALU SQ_INSTS_SALU SQ_I
            "TCP_TOTAL_CACHE_ACCESSES_sum TCP_TCC_READ_REQ_sum TCP_PENDING_STALL_CYCLES_sum TCP_TCP_TA_DATA_STALL_CYCLES_sum"; do
   i=$((i+1))
   rocprofv3 --pmc $set --kernel-trace --output-format csv -d $OUT/pass$i -o pmc -- \
-     python $GRAFT_REPO_ROOT/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-power-probe --no-box-calibration ${BENCH_ARGS} > $OUT/pass$i.log 2>&1
+     python "$REPO"/bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-power-probe --no-box-calibration ${BENCH_ARGS} > $OUT/pass$i.log 2>&1
   echo "pass $i: rc=$?"
 done
