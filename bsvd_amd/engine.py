@@ -62,6 +62,11 @@ _FORMS = {"direct": (0, 0), "wino2": (2, 2), "wino6": (6, 6), "wino26": (6, 6)}
 # (wino_forms.h).  A layer whose bound leaves fp16's range stays on the direct form (PackedNet).
 WINO_G_ROW_SUM = {2: 1.5, 4: 14.0 / 3.0, 6: 2048.0 / 315 + 512.0 / 105 + 128.0 / 35}
 F16_PAIR_LIMIT = 6.0e4          # the same limit arch.BSVD applies to the raw weights (fp16 max 65504)
+# the LOW end of the pair format: lo = fp16(w - hi) is an fp16 subnormal for |w| < 2^-3, so a weight pair resolves 2^-24 ABSOLUTE whatever its
+# size, and a layer's relative error grows as its weights shrink: ~2.6e-8 / std(w) (tests/test_split_model_cpu.py).  Below
+# max |w| = 2^-10 (std ~2e-4: > 1e-4 relative per layer) a rescaled network left the 1e-3 budget on the MI355X
+# (profiles/f16x3_value_probes.txt): PackedNet names such layers once per pack.
+F16X3_SMALL_WEIGHT = 2.0 ** -10
 
 
 def wide_conv_known(name, lib=None):
@@ -189,6 +194,7 @@ class PackedNet:
         self.wino = {}               # {spec.key: transformed pack} of the layers that run on the Winograd kernel
         self.wino_layer_abi = {}     # {spec.key: BsvdConvArgs.wino_m} -- "wino26": F(2,3) for the 128 -> 128 layers, F(6,3) for the wider ones
         self.wino_range_fallback = []    # eligible layers kept on the direct form because max |G g| would leave fp16's range
+        self.small_weight_layers = []    # split-packed layers whose max |w| is below F16X3_SMALL_WEIGHT: (key, max |w|)
         self.tensors = {}
         self.order = {sp.key: i for i, sp in enumerate(net.layers)}      # position in the layer-major walk (tile_order parity)
         edge = set()
@@ -198,7 +204,9 @@ class PackedNet:
             edge = {net.layers[0].key}
         with torch.cuda.device(device):
             # max |w| of every layer the Winograd form could take, in ONE host round trip (a float() per layer is a device sync per layer)
-            cand = [sp for sp in net.layers if self.wino_m and wino_eligible(sp, precision, self.wino_min_cin)]
+            # (in the split mode: of every split-packed layer, for the small-weight notice below)
+            cand = [sp for sp in net.layers if (self.wino_m and wino_eligible(sp, precision, self.wino_min_cin)) or
+                    (precision == "f16x3" and sp.key not in edge)]
             self._wmax = {}
             if cand:
                 mx = torch.stack([state[sp.key + ".weight"].detach().to(device=device, dtype=torch.float32).abs().max()
@@ -233,6 +241,14 @@ class PackedNet:
                                            wp.data_ptr(), bp.data_ptr(), _stream_ptr())
                 _lib.check(rc, "bsvd_pack_weights(%s)" % sp.key)
                 self.tensors[sp.key] = (wp, bp)
+            if precision == "f16x3":
+                self.small_weight_layers = [(sp.key, self._wmax[sp.key]) for sp in net.layers
+                                            if sp.key in self._wmax and 0.0 < self._wmax[sp.key] < F16X3_SMALL_WEIGHT]
+                if self.small_weight_layers:
+                    import warnings
+                    warnings.warn("bsvd_amd: max |weight| below %.3g (2^-10) in %s: an fp16 pair resolves 2^-24 absolute, so these layers "
+                                  "run the split mode at more than 1e-4 relative error (fp16-class from 2^-14 down); "
+                                  "precision='fp32' is exact" % (F16X3_SMALL_WEIGHT, ", ".join("%s (%.3g)" % kv for kv in self.small_weight_layers)))
             # fused network entry: the first conv's weights as the MFMA operand of the second conv's kernel, keyed by the
             # second conv (only DenBlock 1 has a planar entry layer)
             self.head = {}

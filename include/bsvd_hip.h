@@ -38,6 +38,10 @@ extern "C" {
  * three fp16 MFMAs (hi*hi + lo*hi + hi*lo, fp32 accumulate).  fp32-class accuracy (2-4e-5 max-abs on bsvd_c64) at
  * several times the fp32-MFMA rate.  BSVD_F16 (plain fp16) is reserved and not implemented: it misses the 1e-3
  * parity bar (1-3e-2 measured). */
+// "fp32-class" holds for weights around init scale.  lo is an fp16 SUBNORMAL for |v| < 2^-3 (kept by conversions and MFMAs, asserted in
+// tests/test_gpu_range.py), so a pair resolves 2^-24 absolute whatever its size and a layer's relative error is about 2.6e-8 / std(w):
+// 6e-7 at std 0.03, 1e-5 at 2^-4 of that, 1e-4 at 2^-8, plain-fp16 class (2e-3) at 2^-12; a stored output resolves 2^-25 absolute.
+// DESIGN.md 4.1b has the table measured on the MI355X.
 enum { BSVD_F32 = 0, BSVD_F16 = 1, BSVD_F16X3 = 2 };
 enum { BSVD_ACT_NONE = 0, BSVD_ACT_RELU = 1, BSVD_ACT_RELU6 = 2 }; /* get_act_function, bsvd_arch.py:185-192 */
 enum {

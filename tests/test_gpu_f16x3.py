@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+import split_model as S
 from helpers import load_golden, bsvd_keys, state_for, maxabs
 from oracle_exec import OracleExecutor
 from seeded import seeded_state
@@ -105,6 +106,15 @@ def test_layer_split_vs_oracle(cin, cout, stride, tsm, act, epi, T, H, W):
         err = maxabs(got.numpy(), want.numpy())
         print("layer %s max-abs %.3e (|y| max %.1f)" % ((cin, cout, stride, tsm, epi), err, float(want.abs().max())))
         assert err < TIGHT
+        # ... and against the three-pass model of the mode within the bound of tests/test_gpu_split_passes.py (the flat tolerance above is
+        # 20-50x the honest error of these layers: a fault in one chunk's lo half passes it)
+        hv = lambda h, i: None if h is None else Halo(S.pairs(h.t)[i], h.pstride, h.coff)
+        hh = lambda h: None if h is None else (hv(h, 0), hv(h, 1))
+        model = S.direct_three_pass(sp, *S.pairs(x), st["l.weight"], st["l.bias"], hh(hp), hh(hn), extra, eps, ecs)
+        cerr = S.chain_err(sp, xq, st["l.weight"], st["l.bias"], halo_prev=hp, halo_next=hn, extra=extra, extra_pstride=eps, extra_cstride=ecs)
+        need = S.needed(got, model, cerr)
+        print("    vs the three-pass model: needs margin %.3f of %d" % (need, S.M_DIRECT))
+        assert need <= S.M_DIRECT, need
 
 
 FAT_CASES = [
@@ -139,6 +149,18 @@ def test_fat_tile_with_waves_below_the_image(cin, cout, tsm, act, epi, T, H, W):
     assert err < TIGHT
     # the rows next to the dead half tile, separately (a wrong barrier count or a skipped store would show here first)
     assert maxabs(got.numpy()[:, -8:], want.numpy()[:, -8:]) < TIGHT
+    # ... and against the three-pass model within the bound of tests/test_gpu_split_passes.py, on the first and the last 512 columns (all
+    # rows, the dead half tile's neighbours included; the float32 chain of the yardstick runs on the CPU)
+    k = 2 if epi == 1 else 1
+    for x0, x1, o0 in ((0, 513, 0), (W - 513, W, 1)):
+        xc = x[:, :, x0:x1].contiguous()
+        ec = None if extra is None else extra[:, :, 2 * x0:2 * x1].contiguous()
+        model = S.direct_three_pass(sp, *S.pairs(xc), st["l.weight"], st["l.bias"], None, None, ec, eps, 1)[:, :, k * o0:k * (o0 + 512)]
+        chain, ref = S.fp32_chain(sp, from_split(to_split(xc)), st["l.weight"], st["l.bias"], extra=ec, extra_pstride=eps, extra_cstride=1)
+        cerr = float((chain - ref)[:, :, k * o0:k * (o0 + 512)].abs().max())
+        need = S.needed(got[:, :, k * (x0 + o0):k * (x0 + o0 + 512)], model, cerr)
+        print("    columns %d..%d vs the three-pass model: needs margin %.3f of %d" % (x0 + o0, x0 + o0 + 512, need, S.M_DIRECT))
+        assert need <= S.M_DIRECT, need
 
 
 def _module(st, mode="clip"):

@@ -155,7 +155,6 @@ def test_v_output_layer_equals_to_v_of_its_fp32_output(cin, cout, tsm, act, T, H
     if edge.any():
         err = np.abs(got[edge] - want[edge]).max()
         assert err <= 4e-6 * max(1.0, np.abs(want).max()), err
-        assert np.abs(got[edge] - want[edge]).max() > 0 or True
 
 
 def test_abi_refuses_what_the_transformed_domain_cannot_do():

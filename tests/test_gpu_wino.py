@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import torch
 
+import split_model as S
 from helpers import maxabs
 from oracle_exec import OracleExecutor
 from seeded import seeded_state
@@ -78,6 +79,14 @@ def test_wino_layer_vs_oracle(wide_conv, cin, cout, tsm, act, epi, T, H, W):
         err = maxabs(got.numpy(), want.numpy())
         print("%s layer %s max-abs %.3e (|y| max %.1f)" % (wide_conv, (cin, cout, tsm, epi, T, H, W), err, float(want.abs().max())))
         assert err < TIGHT
+        # ... and against the model of the form (pairs of TRANSFORMED values, three passes) within the bound of tests/test_gpu_split_passes.py
+        # (the product forms: the measurement variants that run these cases from tests/measure_driver.py keep the tolerance above)
+        if wide_conv in PRODUCT_FORMS:
+            m = int(wide_conv[4])
+            kw = dict(halo_prev=hp, halo_next=hn, extra=extra, extra_pstride=eps, extra_cstride=1)
+            need = S.needed(got, S.wino_model(sp, xq, st["l.weight"], m, st["l.bias"], **kw), S.wino_err(sp, xq, st["l.weight"], m, st["l.bias"], **kw))
+            print("    vs the Winograd model: needs margin %.3f of %d" % (need, S.M_WINO[m]))
+            assert need <= S.M_WINO[m], need
 
 
 def _conv_with_code(gex, sp, x, code, hp=None, hn=None):
