@@ -456,9 +456,6 @@ static int conv3x3_impl(const BsvdConvArgs *a, void *stream, char *name, int nam
                      (a->epilogue == BSVD_EPI_PS_ADD && !a->w_wino_packed))) {
         set_error("bsvd_conv3x3: y_f32 needs BSVD_F16X3 and a PLAIN NHWC layer (direct or Winograd form) or a PS_ADD layer of the Winograd form"); return -21;
     }
-#ifdef BSVD_ABLATE
-    if (const char *e = getenv("BSVD_ABLATE")) p.ablate = atoi(e);
-#endif
     if ((((uintptr_t)p.w) & 15) != 0) { set_error("bsvd_conv3x3: w_packed / w_wino_packed must be 16-byte aligned"); return -13; }
     if (a->w_wino_packed) {      // Winograd form of a wide layer: explicit request, no silent fall-back to the direct kernel
         if (a->x_planar_ch > 0 || a->head_w_packed) { set_error("bsvd_conv3x3: w_wino_packed: not with a planar / fused entry"); return -19; }

@@ -43,38 +43,6 @@
 #include <type_traits>
 #include "bsvd_internal.h"
 
-// tuning knobs (compile-time; the defaults are the measured best)
-#ifndef BSVD_TUNE_ALIGN
-#define BSVD_TUNE_ALIGN 1      // 1: 256-B aligned LDS patch row pitch (conflict-free A reads; +0.5 % in interleaved A/B)
-#endif
-#ifndef BSVD_TUNE_FAT_OCC
-#define BSVD_TUNE_FAT_OCC 2        // waves/SIMD the 128-accumulator tiles are compiled for
-#endif
-#ifndef BSVD_TUNE_NARROW_OCC
-#define BSVD_TUNE_NARROW_OCC 3     // waves/SIMD the 128-px x 32-ch wave tile is compiled for (3: 168 VGPRs + a 12-byte spill; 2: no spill)
-#endif
-#ifndef BSVD_ABL
-#define BSVD_ABL 0             // TIMING-ONLY ablations of the prefetching K loop (results are wrong): 1 no chunk barrier, 2 no patch slices, 4 no weight loads, 8 half the weight loads (lo := hi), 16 all weight loads from two L1-resident slabs, 32 split epilogue without its stores, 64 split epilogue without the conversion, 128 split epilogue storing lane-contiguous 2-KB runs, 256 pixel fragments read from LDS once per chunk instead of once per tap
-#endif
-#ifndef BSVD_TUNE_ZSKIP
-#define BSVD_TUNE_ZSKIP 1      // 128-accumulator split tiles leave the all-zero temporal-shift chunks of a clip's first / last frame out of the K loop
-#endif
-#ifndef BSVD_TUNE_SKIP_DEAD
-#define BSVD_TUNE_SKIP_DEAD 1  // 128-accumulator (LITE) tiles: waves entirely below the image issue no fragment reads / MFMAs
-#endif
-#ifndef BSVD_TUNE_APFL
-#define BSVD_TUNE_APFL 1       // prefetch of the next tap's fragments into the SAME registers (see LITE): bit 0 the 128-accumulator tiles (r03: 20.11 -> 19.56 ms per C1 clip), bit 1 the narrow 64-channel tile (5.05 -> 5.10), bit 2 the exit tile (=), bit 3 the stride-2 tiles (2.38 -> 2.42: third wave per SIMD lost)
-#endif
-#ifndef BSVD_TUNE_APF
-#define BSVD_TUNE_APF 1        // split DBUF tiles that request the NEXT tap's pixel fragments in the middle of the current tap: 0 none, 1 the exit tile (NT == 1), 2 all, 3 fat tiles
-#endif
-
-// patch-slice register ring of the K loop: loaded into slot tap % 3, stored one tap later (two taps later: -0.1 %, r02)
-#define BSVD_SLICE_D 1
-#define S_OLD0 s2
-#define S_OLD1 s0
-#define S_OLD2 s1
-
 namespace bsvd {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -83,15 +51,15 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 // MT x NT = 32x32 MFMA tiles per wave (a wave covers 2*MT rows x 16 cols of pixels and 32*NT channels),
-// WM x WN = waves per workgroup along pixels / channels, RING = depth of the weight register ring (2: one step
-// ahead, 3: two steps ahead).
-template <int MT_, int NT_, int WM_, int WN_, int STRIDE_, int RING_ = 3, bool DBUF_ = true>
+// WM x WN = waves per workgroup along pixels / channels.  (The fast path's weight register ring is 3 deep -- two steps
+// ahead -- in every tile.)
+template <int MT_, int NT_, int WM_, int WN_, int STRIDE_, bool DBUF_ = true>
 struct ConvCfg {
     static constexpr bool DBUF = DBUF_;   // double-buffered LDS patch (next chunk prefetched during the taps)
-    static constexpr int MT = MT_, NT = NT_, WM = WM_, WN = WN_, STRIDE = STRIDE_, RING = RING_;
+    static constexpr int MT = MT_, NT = NT_, WM = WM_, WN = WN_, STRIDE = STRIDE_;
     static constexpr int TH = 2 * MT * WM, TW = 16;
     static_assert(WM * WN == 4, "4 waves per workgroup");
-    static_assert(RING == 2 || RING == 3, "");
+    static constexpr bool ACC128 = MT * NT >= 8;      // 128 accumulator registers per lane (the fat tile <4,2,2,2,1>)
     static constexpr int BN = WN * NT * 32;
     static constexpr int PH = (TH - 1) * STRIDE + 3;
     static constexpr int PW = (TW - 1) * STRIDE + 3;
@@ -118,8 +86,8 @@ struct ConvCfg {
     // LDS row pitch of the patch.  Stride 1: rounded up to a multiple of 256 B so that the two pixel rows one
     // ds_read_b128 lane group touches land on complementary 16-B slots (conflict-free A reads; PMC showed 48 % of the
     // LDS cycles were bank conflicts with the packed 1440-B pitch).  Not for the 256-px x 64-ch tile at 3 workgroups
-    // per CU, whose double-buffered patch would no longer fit three times into 160 KiB.
-    static constexpr bool ALIGN_ROWS = QPL || (BSVD_TUNE_ALIGN && STRIDE == 1 && !(MT == 2 && WM == 4));
+    // per CU, whose double-buffered patch would no longer fit three times into 160 KiB.  (+0.5 % in interleaved A/B)
+    static constexpr bool ALIGN_ROWS = QPL || (STRIDE == 1 && !(MT == 2 && WM == 4));
     static constexpr int ROWP = ALIGN_ROWS ? ((PW * PS * 4 + 255) / 256 * 256) / 4 : PW * PS;   // floats
     // float offset of the 16-B channel quad `quad` of patch pixel (prow, pcol)
     __host__ __device__ static constexpr int lds_off(int prow, int pcol, int quad)
@@ -146,7 +114,9 @@ struct ConvCfg {
     static_assert(NSLICE <= 7, "slices are loaded at taps 0..6 and stored two taps later (2..8)");
     // workgroups per CU the LDS footprint admits (160 KiB) -> register budget for __launch_bounds__
     static constexpr int OCC_LDS = LDS_BYTES > 80 * 1024 ? 1 : (LDS_BYTES > 53 * 1024 ? 2 : 3);
-    static constexpr int OCC = (MT * NT >= 8) ? BSVD_TUNE_FAT_OCC : (MT == 4 && NT == 1 && OCC_LDS > BSVD_TUNE_NARROW_OCC) ? BSVD_TUNE_NARROW_OCC : OCC_LDS;   // 128 accumulator registers (AGPRs) + <= 128 VGPRs: two waves per SIMD
+    // 128 accumulator registers (AGPRs) + <= 128 VGPRs: two waves per SIMD.  (The 128-px x 32-ch wave tile stays at the 3 its LDS
+    // admits: 168 VGPRs + a 12-byte spill; compiled for 2 it would have none and lose the third wave.)
+    static constexpr int OCC = ACC128 ? 2 : OCC_LDS;
 };
 
 struct SrcSel {            // per-frame sources of the temporal-shift gather (wave uniform)
@@ -224,11 +194,6 @@ __device__ __forceinline__ f32x4 buf_load4(__amdgpu_buffer_rsrc_t r, unsigned vo
 {
     return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
 }
-// (cache policy of the activation loads: nt / sc1 nt are slower -- nt also drops the halo rows from the L2; r03)
-__device__ __forceinline__ f32x4 buf_load4_act(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff)
-{
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
-}
 
 struct ChunkSrc {          // wave-uniform description of one 16-channel chunk's source
     __amdgpu_buffer_rsrc_t rs;
@@ -244,31 +209,22 @@ struct ChunkSrc {          // wave-uniform description of one 16-channel chunk's
 };
 
 // ------------------------------------------------------------------------------------------------------
-#ifndef BSVD_TUNE_FAT_MIN_WGS
-#define BSVD_TUNE_FAT_MIN_WGS 800   // smallest grid (in 256-px x 128-ch workgroups) that takes the fat split tile (r02: 1020-workgroup launches -- 256-ch layers of a 1080p frame, upc1 of a 540x960 frame -- are 1-3 % faster fat; 510-540 are not)
-#endif
-#ifndef BSVD_TUNE_S2F32_OCC
-#define BSVD_TUNE_S2F32_OCC 2      // waves/SIMD the exact-fp32 stride-2 kernel is compiled for (3 = 168 VGPRs + a 20-B spill: 2.3 % slower)
-#endif
 // Refill of the split-fp16 stride-2 tile's single LDS patch buffer: a REGISTER DOUBLE BUFFER -- chunk cb + 1 is requested at the boundary before
 // chunk cb and waits in 36 VGPRs (flattened items: all 256 lanes carry a piece); a boundary is barrier + ds_write + barrier: 2.29 ms per clip for
-// the four stride-2 launches.  Measured and removed (knob BSVD_TUNE_S2_PAIR 0 / 1 / 3, all bit-identical): load -> store at every
+// the four stride-2 launches.  Measured and removed (the S2_PAIR variants 0 / 1 / 3, all bit-identical): load -> store at every
 // boundary 2.36-2.46; both 16-channel chunks of a 128-byte line fetched at once, the odd one held in registers 2.61 (and requested one chunk period
 // ahead: 2.49) -- these halve the memory-side line fetches (2.04x -> 1.1x of the input) and are SLOWER: the re-fetched half lines come from the
 // Infinity Cache, the tile lives on occupancy and on not waiting at its boundaries.
-constexpr int S2_HOLD_OCC = 2;     // waves/SIMD the register-holding stride-2 tile is compiled for
-#ifndef BSVD_TUNE_FOLD8_OCC
-#define BSVD_TUNE_FOLD8_OCC 3      // waves/SIMD of the split-fp16 fold-8 instantiation (c32-sized networks): 3 = 168 VGPRs + a 20-byte spill in the
-                                   // chunk loop's preheader (outside the taps), 2 = no spill
-#endif
-template <class C, int PREC, bool MIXF = false>
+// waves/SIMD a kernel is compiled for.  (The split-fp16 fold-8 instantiation of the c32-sized networks keeps the 3 of its tile: 168 VGPRs + a
+// 20-byte spill in the chunk loop's preheader, outside the taps.)
+template <class C, int PREC>
 constexpr int occ_of()
 {
-    if (MIXF && PREC == 1 && C::OCC > BSVD_TUNE_FOLD8_OCC) return BSVD_TUNE_FOLD8_OCC;
     // exact-fp32 stride 2 (single patch buffer): the refill holds the whole 17x33 patch in registers (72 VGPRs) -> 2 waves/SIMD
-    if (C::STRIDE == 2 && PREC == 0 && C::OCC > BSVD_TUNE_S2F32_OCC) return BSVD_TUNE_S2F32_OCC;
-    // split-fp16 single-buffer tile with the odd chunk of every 128-byte line held in registers (72 VGPRs): 2 waves/SIMD
-    if (!C::DBUF && PREC == 1 && C::OCC > S2_HOLD_OCC) return S2_HOLD_OCC;
+    // (3 = 168 VGPRs + a 20-B spill: 2.3 % slower)
+    if (C::STRIDE == 2 && PREC == 0 && C::OCC > 2) return 2;
+    // split-fp16 single-buffer tile with the next chunk held in registers (see the refill note above): 2 waves/SIMD
+    if (!C::DBUF && PREC == 1 && C::OCC > 2) return 2;
     return C::OCC;
 }
 
@@ -302,6 +258,25 @@ __device__ __forceinline__ void tl_stamp(int slot, int k)
 #define TLP_WAIT_MARK(k, a, b)
 #define TLP_FLUSH()
 #endif
+// ------------------------------------------------------------------------------------------------------
+struct TileId { int f, ty, tx, ct; };      // frame, tile row / column, output-channel tile
+
+// block -> (frame, tile_y, tile_x, cout tile); XCD-aware: block b runs on XCD b%8, give each XCD
+// a contiguous range of logical tiles so that halo/weight re-reads hit that XCD's L2.
+__device__ __forceinline__ TileId decode_tile(const ConvParams &p)
+{
+    const int nblk = gridDim.x, bid = blockIdx.x;
+    const int xcd = bid & 7, q8 = nblk >> 3, r8 = nblk & 7;
+    int lid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+    if (p.flip) lid = nblk - 1 - lid;     // reverse walk: start with the tiles the producer wrote last (still in the Infinity Cache)
+    TileId t;
+    t.ct = lid % p.nct; lid /= p.nct;
+    t.tx = lid % p.ntx; lid /= p.ntx;
+    t.ty = lid % p.nty;
+    t.f = lid / p.nty;
+    return t;
+}
+
 // HEADF (fused network entry, BsvdConvArgs.head_w_packed): p.x is the caller's planar fp32 input; the tile computes the
 // first conv's output (head_cin -> Cin channels, act, zero outside the image) on its own 18 x 18 patch with MFMAs
 // (K = 9 taps x 4 channels, padded to 48) straight into the LDS patch buffers, a pair of 16-channel chunks at a time, and
@@ -311,9 +286,17 @@ __device__ __forceinline__ void tl_stamp(int slot, int k)
 // chunk by chunk through a third LDS buffer -- a pair of 16-channel chunks at a time, straight into the two patch buffers of the main
 // conv, and the Cin-channel tensor between the two convs never exists in HBM.  See pre_pair below and DESIGN.md 4.1e.
 template <class C, bool FAST, int PREC, bool MIXF = false, bool HEADF = false, bool PREF = false>
-__global__ __launch_bounds__(256, (PREF ? 2 : occ_of<C, PREC, MIXF>())) void conv3x3_kernel(const ConvParams p)
+__global__ __launch_bounds__(256, (PREF ? 2 : occ_of<C, PREC>())) void conv3x3_kernel(const ConvParams p)
 {
+    // ---- tile families: every compile-time choice below is made by one of these names
     constexpr bool FRONT = HEADF || PREF;      // the main conv's input chunks are produced inside the tile, not loaded
+    constexpr bool FAT = PREC == 1 && C::ACC128;       // the 128-accumulator split tile (wide layers, large grids)
+    constexpr bool REGPF = PREC == 1 && !C::DBUF;      // the single-buffer split tile (stride 2): register double buffer, see occ_of
+    constexpr bool APF = PREC == 1 && C::DBUF && (C::NT == 1 || FAT);      // K loop that requests tap k+1's pixel fragments inside tap k
+    constexpr bool LITE = FAT;                 // ... into the SAME registers (no second fragment set); see the APF loop
+    constexpr bool ZSKIP = FAST && FAT && !MIXF;       // all-zero temporal-shift chunks are left out of the K loop
+    static_assert(!FAT || (C::DBUF && C::STRIDE == 1 && !FRONT), "the fat tile is a plain double-buffered stride-1 tile");
+    static_assert(!FRONT || APF, "both fused fronts run NT == 1 tiles: only the APF loop knows them");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float *const patch_buf = smem;                              // 2 x PATCH_FLOATS
 
@@ -325,20 +308,11 @@ __global__ __launch_bounds__(256, (PREF ? 2 : occ_of<C, PREC, MIXF>())) void con
     const int wm = wid / C::WN, wn = wid % C::WN;
     const int li = lane & 31, lh = lane >> 5;
 
-    // ---- block -> (frame, tile_y, tile_x, cout tile); XCD-aware: block b runs on XCD b%8, give each XCD
-    //      a contiguous range of logical tiles so that halo/weight re-reads hit that XCD's L2.
-    const int nblk = gridDim.x, bid = blockIdx.x;
-    const int xcd = bid & 7, q8 = nblk >> 3, r8 = nblk & 7;
-    int lid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
-    if (p.flip) lid = nblk - 1 - lid;     // reverse walk: start with the tiles the producer wrote last (still in the Infinity Cache)
-    const int ct = lid % p.nct; lid /= p.nct;
-    const int tx = lid % p.ntx; lid /= p.ntx;
-    const int ty = lid % p.nty;
-    const int f = lid / p.nty;
-
-    const int oy0 = ty * C::TH, ox0 = tx * C::TW;     // output tile origin
+    const TileId t = decode_tile(p);
+    const int f = t.f;
+    const int oy0 = t.ty * C::TH, ox0 = t.tx * C::TW;     // output tile origin
     const int iy0 = oy0 * C::STRIDE - 1, ix0 = ox0 * C::STRIDE - 1;   // patch origin in the input
-    const int n0 = ct * C::BN;
+    const int n0 = t.ct * C::BN;
 
     SrcSel s;
     s.cur = p.x + (int64_t)f * p.x_fs;
@@ -352,8 +326,6 @@ __global__ __launch_bounds__(256, (PREF ? 2 : occ_of<C, PREC, MIXF>())) void con
     // is all zeros, so its chunks are left out of the K loop: chunk_src / load_b below take LIVE chunk / step indices and map
     // them (i -> i + zs_a, then + zs_c from zs_b on).  Adding exact zero products leaves an fp32 accumulator bit for bit as it
     // was, so the output is identical; a 10-frame clip saves 2/10 x 1/8 of the MFMAs of its 16 temporal-fusion layers.
-    constexpr bool ZSKIP = BSVD_TUNE_ZSKIP && FAST && PREC == 1 && !MIXF && !FRONT && C::DBUF && C::RING == 3 && C::STRIDE == 1 &&
-                           (BSVD_TUNE_APFL & 1) && C::MT * C::NT >= 8;
     int ncb = p.Cin >> 4;
     [[maybe_unused]] int zs_a = 0, zs_b = 0, zs_c = 0;
     if constexpr (ZSKIP) {
@@ -469,12 +441,11 @@ __global__ __launch_bounds__(256, (PREF ? 2 : occ_of<C, PREC, MIXF>())) void con
             vb[nt] = nb0 + 32 * nt < p.Cout ? (unsigned)(lh * p.Cout + nb0 + 32 * nt) * 16u : BSVD_OOB;
         auto load_b = [&](int step, f32x4 (&b)[C::NT][2]) {
             if constexpr (ZSKIP) step = step + 9 * zs_a + (step >= 9 * zs_b ? 9 * zs_c : 0);
-            const unsigned so = (BSVD_ABL & 16) ? (unsigned)(step & 1) * slab_bytes : (unsigned)step * slab_bytes;   // 16: timing only, L1-resident weights
+            const unsigned so = (unsigned)step * slab_bytes;
 #pragma unroll
             for (int nt = 0; nt < C::NT; ++nt) {
                 b[nt][0] = buf_load4(rs_w, vb[nt], so);
-                if constexpr (BSVD_ABL & 8) b[nt][1] = b[nt][0];      // timing only: half the weight stream, realistic operands
-                else b[nt][1] = buf_load4(rs_w, vb[nt], so + g_bytes);
+                b[nt][1] = buf_load4(rs_w, vb[nt], so + g_bytes);
             }
         };
 
@@ -511,7 +482,7 @@ __global__ __launch_bounds__(256, (PREF ? 2 : occ_of<C, PREC, MIXF>())) void con
                     }
                 }
                 const unsigned voff = ok ? (unsigned)(gy * p.W + gx) * c.ps4 + pq * 16u : BSVD_OOB;
-                v[i] = buf_load4_act(c.rs, voff, c.soff);
+                v[i] = buf_load4(c.rs, voff, c.soff);      // (cache policy of the activation loads: nt / sc1 nt are slower -- nt also drops the halo rows from the L2; r03)
             }
         };
         auto slice_store = [&](float *pb, int row0, const f32x4 (&v)[C::P]) {
@@ -527,9 +498,8 @@ __global__ __launch_bounds__(256, (PREF ? 2 : occ_of<C, PREC, MIXF>())) void con
         f32x4 b0[C::NT][2], b1[C::NT][2], b2[C::NT][2];
         if constexpr (!PREF) {          // (fused pair: the main conv's first slabs are requested at the end of every pre_pair instead)
             load_b(0, b0);
-            if constexpr (C::RING == 3) load_b(1, b1);
+            load_b(1, b1);
         }
-        if constexpr ((BSVD_ABL & 4) != 0) load_b(2, b2);     // (timing only: the ring keeps these three slabs for the whole tile)
         // whole patch in flight at once, then published: one HBM latency per tile instead of one per slice
         auto fill_patch = [&](const ChunkSrc &c, float *pb) {
             // G slices in flight at once, then published.  Everything at once where the registers are there (prologue of
@@ -548,8 +518,7 @@ __global__ __launch_bounds__(256, (PREF ? 2 : occ_of<C, PREC, MIXF>())) void con
                     if (g0 + sl < C::NSLICE) slice_store(pb, (g0 + sl) * C::ROWS_PER_SLICE, v[sl]);
             }
         };
-        // Single-buffer split tile (stride 2): register double buffer -- chunk cb + 1 in flight during chunk cb (see S2_HOLD_OCC above).
-        constexpr bool REGPF = !C::DBUF && PREC == 1;
+        // REGPF, the single-buffer split tile (stride 2): register double buffer -- chunk cb + 1 in flight during chunk cb (see occ_of above).
         // items: the patch flattened to (row, column, 16-byte quad) items, 256 per pass -- the row-slice map above keeps only 132 of 256 lanes busy
         // on the 33-pixel rows of this tile, which would double the registers the held chunk costs
         constexpr int PNITEM = C::PH * C::ROW_ITEMS, PNI = (PNITEM + 255) / 256;
@@ -573,7 +542,6 @@ __global__ __launch_bounds__(256, (PREF ? 2 : occ_of<C, PREC, MIXF>())) void con
             }
         };
         // the flattened item map: all 256 lanes carry a 16-byte piece per load instruction (9 items = the whole 17 x 33 patch)
-        constexpr bool FLAT = REGPF;
         auto prefetch_hold = [&](int cbn) {            // REGPF: request chunk cbn into registers; it is published at the next boundary
 #pragma unroll
             for (int i = 0; i < PNI; ++i) {
@@ -690,7 +658,7 @@ __global__ __launch_bounds__(256, (PREF ? 2 : occ_of<C, PREC, MIXF>())) void con
             for (int i = 0; i < SNI; ++i) {
                 unsigned voff; int lo; bool inp;
                 pre_item(i, voff, lo, inp);
-                if constexpr (PREF) phold[i] = buf_load4_act(r, voff, (unsigned)ci * 64u);
+                if constexpr (PREF) phold[i] = buf_load4(r, voff, (unsigned)ci * 64u);
             }
         };
         [[maybe_unused]] auto pre_publish = [&]() {
@@ -852,7 +820,7 @@ __global__ __launch_bounds__(256, (PREF ? 2 : occ_of<C, PREC, MIXF>())) void con
                 *reinterpret_cast<u32x4 *>(rawp + e * 16) = o;
             }
         }
-        else if constexpr (FLAT) fill_flat(chunk_src(0), patch_buf);
+        else if constexpr (REGPF) fill_flat(chunk_src(0), patch_buf);
         else fill_patch(chunk_src(0), patch_buf);
         if constexpr (REGPF) prefetch_hold(1);
         __syncthreads();
@@ -863,8 +831,6 @@ __global__ __launch_bounds__(256, (PREF ? 2 : occ_of<C, PREC, MIXF>())) void con
                 if constexpr (REGPF) {
                     publish_hold(patch_buf);
                     prefetch_hold(cb + 2);
-                } else if constexpr (FLAT) {
-                    fill_flat(cn, patch_buf);
                 } else {
                     fill_patch(cn, patch_buf);
                 }
@@ -881,14 +847,15 @@ __global__ __launch_bounds__(256, (PREF ? 2 : occ_of<C, PREC, MIXF>())) void con
         // tap with its operands already in registers.  Same MFMAs in the same order on the same accumulators: bit-identical.
         // Measured r02 (interleaved A/B, ms per clip): fat 128-accumulator tile 20.05 -> 20.31 (SLOWER: its two waves per SIMD already
         // alternate load and MFMA phases, and the scheduling fences cost more than the exposed latency), 64-channel tile 6.33 =,
-        // the 32-channel exit tile 0.63 -> 0.58.  Default: the exit tile only.
-        constexpr bool APF = PREC == 1 && (C::DBUF || ((BSVD_TUNE_APFL & 8) && C::STRIDE == 2)) && C::RING == 3 &&
-                             (((BSVD_TUNE_APFL & 8) && C::STRIDE == 2) || BSVD_TUNE_APF == 2 || (BSVD_TUNE_APF == 1 && C::NT == 1) || (BSVD_TUNE_APF == 3 && C::MT * C::NT >= 8) ||
-                              ((BSVD_TUNE_APFL & 1) && C::MT * C::NT >= 8));
-        // LITE: no second register set at all -- `lo` of tap k+1 is requested after pass 1 of tap k (as above), `hi` of tap k+1
+        // the 32-channel exit tile 0.63 -> 0.58.  So this double-buffered form runs on the NT == 1 tiles only.
+        // LITE (the FAT tile): no second register set at all -- `lo` of tap k+1 is requested after pass 1 of tap k (as above), `hi` of tap k+1
         // after pass 3 of tap k into the registers its MFMAs have just read; pass 1 of tap k+1 (8 MFMAs) covers that latency.
-        constexpr bool LITE = ((BSVD_TUNE_APFL & 1) && C::MT * C::NT >= 8) || ((BSVD_TUNE_APFL & 2) && C::MT == 4 && C::NT == 1) || ((BSVD_TUNE_APFL & 8) && C::STRIDE == 2) ||
-                              ((BSVD_TUNE_APFL & 4) && C::MT == 2 && C::NT == 1);
+        // Measured r03 (ms per C1 clip): the 128-accumulator tiles 20.11 -> 19.56; the narrow 64-channel tile 5.05 -> 5.10,
+        // the exit tile =, the stride-2 tiles 2.38 -> 2.42 (third wave per SIMD lost): FAT only.
+        //
+        // ---- K loop of the APF tiles: the split double-buffered tiles with 32-channel waves (NT == 1: the 64-channel, exit and fused-front
+        //      tiles; two fragment sets) and the FAT tile (LITE: one set).  Nine unrolled taps per chunk, one barrier per chunk; the next
+        //      chunk's patch arrives in row slices during the taps, or -- FRONT -- is computed into both buffers at every other boundary.
         if constexpr (APF) {
             auto load_hi = [&](const float *pc, int ky, int kx, f32x4 (&h)[C::MT]) {
 #pragma unroll
@@ -911,8 +878,8 @@ __global__ __launch_bounds__(256, (PREF ? 2 : occ_of<C, PREC, MIXF>())) void con
             // its own loop: it stages its share of every chunk and meets the chunk barriers, but reads no fragments and issues
             // no MFMAs.  (Guarding the reads / MFMAs of the common loop with a wave-uniform branch instead cost every wave its
             // cross-tap schedule: 19.49 -> 19.83 ms per C1 clip.)
-            // (never with the fused entry: its live loop has the head_pair barriers the staging-only loop lacks)
-            const bool wlive = (BSVD_TUNE_SKIP_DEAD && LITE && !FRONT) ? oy0 + 2 * C::MT * wm < p.Ho : true;
+            // (LITE tiles only, so never with a fused front: their live loop has barriers the staging-only loop lacks)
+            const bool wlive = LITE ? oy0 + 2 * C::MT * wm < p.Ho : true;
             if (!wlive) {
                 for (int cb = 0; cb < ncb; ++cb) {
                     ChunkSrc cn = chunk_src(cb + 1 < ncb ? cb + 1 : cb);
@@ -932,8 +899,8 @@ __global__ __launch_bounds__(256, (PREF ? 2 : occ_of<C, PREC, MIXF>())) void con
                         __syncthreads();
                     }
                 }
-                const float *pcur = patch_buf + (C::DBUF ? (cb & 1) * C::PATCH_FLOATS : 0);
-                [[maybe_unused]] float *pnext = patch_buf + (C::DBUF ? ((cb + 1) & 1) * C::PATCH_FLOATS : 0);
+                const float *pcur = patch_buf + (cb & 1) * C::PATCH_FLOATS;
+                [[maybe_unused]] float *pnext = patch_buf + ((cb + 1) & 1) * C::PATCH_FLOATS;
                 ChunkSrc cn = chunk_src(cb + 1 < ncb ? cb + 1 : cb);
                 if (cb + 1 >= ncb) cn.rs = make_rsrc(s.cur, 0u);
                 [[maybe_unused]] f32x4 s0[C::P], s1[C::P], s2[C::P];
@@ -942,67 +909,61 @@ __global__ __launch_bounds__(256, (PREF ? 2 : occ_of<C, PREC, MIXF>())) void con
                 f32x4 hiA[C::MT], hiB[C::MT], loA[C::MT], loB[C::MT];
                 load_hi(pcur, 0, 0, hiA);
                 load_lo(pcur, 0, 0, loA);
+                // both register rings rotate statically: weights b0 -> b1 -> b2 (filled two steps ahead); patch slices s0 -> s1 -> s2, loaded into
+                // slot tap % 3 and stored one tap later (two taps later: -0.1 %, r02)
 #define BSVD_APF_TAP(T, HC, LC, HN, LN, BCUR, BFILL, SNEW, SOLD)                                                           \
                 {                                                                                                        \
-                    if constexpr (!(BSVD_ABL & 4)) load_b(step + 2 < nsteps ? step + 2 : nsteps - 1, BFILL);             \
-                    if constexpr (C::DBUF && !FRONT && !(BSVD_ABL & 2)) slice_load(cn, (T) * C::ROWS_PER_SLICE, SNEW);    /* rows >= PH: zeros */ \
+                    load_b(step + 2 < nsteps ? step + 2 : nsteps - 1, BFILL);                                            \
+                    if constexpr (!FRONT) slice_load(cn, (T) * C::ROWS_PER_SLICE, SNEW);    /* rows >= PH: zeros */      \
                     __builtin_amdgcn_sched_barrier(0);                                                                   \
                     pass(LC, BCUR, 0);                                                      /* hi(w) x lo(x) */           \
                     __builtin_amdgcn_sched_barrier(0);                                                                   \
-                    if constexpr ((T) < 8 && !(BSVD_ABL & 256)) {                                                        \
+                    if constexpr ((T) < 8) {                                                                             \
                         load_lo(pcur, ((T) + 1) / 3, ((T) + 1) % 3, LN);                                                 \
                         if constexpr (!LITE) load_hi(pcur, ((T) + 1) / 3, ((T) + 1) % 3, HN);                            \
                     }                                                                                                    \
                     __builtin_amdgcn_sched_barrier(0);                                      /* reads stay HERE: 16 MFMAs of cover */ \
                     pass(HC, BCUR, 1);                                                      /* lo(w) x hi(x) */           \
                     pass(HC, BCUR, 0);                                                      /* hi(w) x hi(x) */           \
-                    if constexpr (LITE && (T) < 8 && !(BSVD_ABL & 256)) {                                                \
+                    if constexpr (LITE && (T) < 8) {                                                                     \
                         __builtin_amdgcn_sched_barrier(0);                                                               \
                         load_hi(pcur, ((T) + 1) / 3, ((T) + 1) % 3, HN);                                                 \
                         __builtin_amdgcn_sched_barrier(0);                                                               \
                     }                                                                                                    \
-                    if constexpr (C::DBUF && !FRONT && !(BSVD_ABL & 2))                                                  \
-                        if ((T) >= BSVD_SLICE_D && (T) <= C::NSLICE - 1 + BSVD_SLICE_D) slice_store(pnext, ((T) - BSVD_SLICE_D) * C::ROWS_PER_SLICE, SOLD); \
+                    if constexpr (!FRONT)                                                                                \
+                        if ((T) >= 1 && (T) <= C::NSLICE) slice_store(pnext, ((T) - 1) * C::ROWS_PER_SLICE, SOLD);        \
                     ++step;                                                                                              \
                 }
                 if constexpr (LITE) {
-                    BSVD_APF_TAP(0, hiA, loA, hiA, loA, b0, b2, s0, S_OLD0)
-                    BSVD_APF_TAP(1, hiA, loA, hiA, loA, b1, b0, s1, S_OLD1)
-                    BSVD_APF_TAP(2, hiA, loA, hiA, loA, b2, b1, s2, S_OLD2)
-                    BSVD_APF_TAP(3, hiA, loA, hiA, loA, b0, b2, s0, S_OLD0)
-                    BSVD_APF_TAP(4, hiA, loA, hiA, loA, b1, b0, s1, S_OLD1)
-                    BSVD_APF_TAP(5, hiA, loA, hiA, loA, b2, b1, s2, S_OLD2)
-                    BSVD_APF_TAP(6, hiA, loA, hiA, loA, b0, b2, s0, S_OLD0)
-                    BSVD_APF_TAP(7, hiA, loA, hiA, loA, b1, b0, s1, S_OLD1)
-                    BSVD_APF_TAP(8, hiA, loA, hiA, loA, b2, b1, s2, S_OLD2)
+                    BSVD_APF_TAP(0, hiA, loA, hiA, loA, b0, b2, s0, s2)
+                    BSVD_APF_TAP(1, hiA, loA, hiA, loA, b1, b0, s1, s0)
+                    BSVD_APF_TAP(2, hiA, loA, hiA, loA, b2, b1, s2, s1)
+                    BSVD_APF_TAP(3, hiA, loA, hiA, loA, b0, b2, s0, s2)
+                    BSVD_APF_TAP(4, hiA, loA, hiA, loA, b1, b0, s1, s0)
+                    BSVD_APF_TAP(5, hiA, loA, hiA, loA, b2, b1, s2, s1)
+                    BSVD_APF_TAP(6, hiA, loA, hiA, loA, b0, b2, s0, s2)
+                    BSVD_APF_TAP(7, hiA, loA, hiA, loA, b1, b0, s1, s0)
+                    BSVD_APF_TAP(8, hiA, loA, hiA, loA, b2, b1, s2, s1)
                 } else {
-                BSVD_APF_TAP(0, hiA, loA, hiB, loB, b0, b2, s0, S_OLD0)
-                BSVD_APF_TAP(1, hiB, loB, hiA, loA, b1, b0, s1, S_OLD1)
-                BSVD_APF_TAP(2, hiA, loA, hiB, loB, b2, b1, s2, S_OLD2)
-                BSVD_APF_TAP(3, hiB, loB, hiA, loA, b0, b2, s0, S_OLD0)
-                BSVD_APF_TAP(4, hiA, loA, hiB, loB, b1, b0, s1, S_OLD1)
-                BSVD_APF_TAP(5, hiB, loB, hiA, loA, b2, b1, s2, S_OLD2)
-                BSVD_APF_TAP(6, hiA, loA, hiB, loB, b0, b2, s0, S_OLD0)
-                BSVD_APF_TAP(7, hiB, loB, hiA, loA, b1, b0, s1, S_OLD1)
-                BSVD_APF_TAP(8, hiA, loA, hiB, loB, b2, b1, s2, S_OLD2)
+                BSVD_APF_TAP(0, hiA, loA, hiB, loB, b0, b2, s0, s2)
+                BSVD_APF_TAP(1, hiB, loB, hiA, loA, b1, b0, s1, s0)
+                BSVD_APF_TAP(2, hiA, loA, hiB, loB, b2, b1, s2, s1)
+                BSVD_APF_TAP(3, hiB, loB, hiA, loA, b0, b2, s0, s2)
+                BSVD_APF_TAP(4, hiA, loA, hiB, loB, b1, b0, s1, s0)
+                BSVD_APF_TAP(5, hiB, loB, hiA, loA, b2, b1, s2, s1)
+                BSVD_APF_TAP(6, hiA, loA, hiB, loB, b0, b2, s0, s2)
+                BSVD_APF_TAP(7, hiB, loB, hiA, loA, b1, b0, s1, s0)
+                BSVD_APF_TAP(8, hiA, loA, hiB, loB, b2, b1, s2, s1)
                 }
 #undef BSVD_APF_TAP
-                if constexpr (!(BSVD_ABL & 1)) __syncthreads();
-                if constexpr (!C::DBUF) refill_single(cb, cn);
+                __syncthreads();
             }
             }
         } else {
-        if constexpr (PREF) { pre_all(); zero_acc(); }
+        // ---- K loop of the other fast tiles (!APF): exact fp32, and the split tiles with 64-channel waves below 128 accumulators
+        //      (<2,2,2,2,1>, the fold-8 <2,2,4,1,1>) or a single patch buffer (REGPF).  Three taps per trip of a rolled ky loop, all
+        //      fragments of a tap read in front of its MFMAs; single-buffer tiles refill the patch behind the chunk's barrier.
         for (int cb = 0; cb < ncb; ++cb) {
-            if constexpr (FRONT) {
-                // both patch buffers are free here (the barrier that ended chunk cb - 1): fill them with chunks cb, cb + 1
-                if ((cb & 1) == 0) {
-                    if constexpr (HEADF) head_pair(cb >> 1);
-                    else if (cb == 0) pre_store(std::integral_constant<int, 0>{}, step);
-                    else pre_store(std::integral_constant<int, 1>{}, step);
-                    __syncthreads();
-                }
-            }
             const float *pcur = patch_buf + (C::DBUF ? (cb & 1) * C::PATCH_FLOATS : 0);
             float *pnext = patch_buf + (C::DBUF ? ((cb + 1) & 1) * C::PATCH_FLOATS : 0);
             // next chunk's source; after the last chunk a zero-size descriptor turns the slice loads into no-ops
@@ -1014,34 +975,22 @@ __global__ __launch_bounds__(256, (PREF ? 2 : occ_of<C, PREC, MIXF>())) void con
 #pragma unroll 1
             for (int ky = 0; ky < 3; ++ky) {
                 // three taps per trip so that both register rings rotate statically:
-                //   weights  b0 -> b1 -> b2 (filled RING-1 steps ahead),  slices  s0 -> s1 -> s2 (stored two steps later)
+                //   weights  b0 -> b1 -> b2 (filled two steps ahead),  slices  s0 -> s1 -> s2 (stored one step later)
 #define BSVD_TAP(KX, BCUR, BFILL, SNEW, SOLD)                                                                  \
                 {                                                                                              \
                     const int tap = ky * 3 + (KX);                                                             \
                     f32x4 a[C::MT][2];                                                                         \
                     load_a(pcur, ky, (KX), a);                                                                 \
-                    load_b(step + C::RING - 1 < nsteps ? step + C::RING - 1 : nsteps - 1, BFILL);              \
-                    if constexpr (C::DBUF && !FRONT) slice_load(cn, tap * C::ROWS_PER_SLICE, SNEW);   /* rows >= PH: zeros */ \
+                    load_b(step + 2 < nsteps ? step + 2 : nsteps - 1, BFILL);                                  \
+                    if constexpr (C::DBUF) slice_load(cn, tap * C::ROWS_PER_SLICE, SNEW);   /* rows >= PH: zeros */ \
                     mfma32(a, BCUR);                                                                           \
-                    if constexpr (C::DBUF && !FRONT)                                                           \
-                        if (tap >= BSVD_SLICE_D && tap <= C::NSLICE - 1 + BSVD_SLICE_D) slice_store(pnext, (tap - BSVD_SLICE_D) * C::ROWS_PER_SLICE, SOLD); \
+                    if constexpr (C::DBUF)                                                                     \
+                        if (tap >= 1 && tap <= C::NSLICE) slice_store(pnext, (tap - 1) * C::ROWS_PER_SLICE, SOLD); \
                     ++step;                                                                                    \
                 }
-                if constexpr (C::RING == 3) {
-                    BSVD_TAP(0, b0, b2, s0, S_OLD0)
-                    BSVD_TAP(1, b1, b0, s1, S_OLD1)
-                    BSVD_TAP(2, b2, b1, s2, S_OLD2)
-                } else {      // 2-deep ring: period 2 does not divide 3 taps -> alternate the roles by trip parity
-                    if (((cb + ky) & 1) == 0) {      // step parity: step = 9 cb + 3 ky + kx
-                        BSVD_TAP(0, b0, b1, s0, S_OLD0)
-                        BSVD_TAP(1, b1, b0, s1, S_OLD1)
-                        BSVD_TAP(2, b0, b1, s2, S_OLD2)
-                    } else {
-                        BSVD_TAP(0, b1, b0, s0, S_OLD0)
-                        BSVD_TAP(1, b0, b1, s1, S_OLD1)
-                        BSVD_TAP(2, b1, b0, s2, S_OLD2)
-                    }
-                }
+                BSVD_TAP(0, b0, b2, s0, s2)
+                BSVD_TAP(1, b1, b0, s1, s0)
+                BSVD_TAP(2, b2, b1, s2, s1)
 #undef BSVD_TAP
             }
             __syncthreads();   // one barrier per 16-channel chunk (9 taps, 288 MFMAs per wave)
@@ -1050,6 +999,8 @@ __global__ __launch_bounds__(256, (PREF ? 2 : occ_of<C, PREC, MIXF>())) void con
         }
     } else {
         // ============================================================================= GENERIC path
+        // ---- K loop of the !FAST kernels (exact fp32 only: any fold / alignment / frame size).  Per-element gather with 64-bit offsets,
+        //      weights one step ahead, the next chunk's patch spread over the nine taps of a rolled loop.
         const int64_t slab_stride = (int64_t)16 * p.Cout;           // floats per (chunk, tap) weight slab
         const float *wl = p.w + ((int64_t)lh * p.Cout + nb0) * 4;
         const int64_t g_off = (int64_t)8 * p.Cout;
@@ -1103,7 +1054,7 @@ __global__ __launch_bounds__(256, (PREF ? 2 : occ_of<C, PREC, MIXF>())) void con
     }
 
     TL(2);
-    if constexpr (BSVD_TUNE_SKIP_DEAD && FAST && PREC == 1 && (BSVD_TUNE_APFL & 1) && C::MT * C::NT >= 8 && C::DBUF && C::RING == 3) {
+    if constexpr (FAST && FAT) {
         // a wave entirely below the image (see wlive in the K loop) has nothing to store; no workgroup barrier follows
 #ifndef BSVD_TIMELINE
         if (oy0 + 2 * C::MT * wm >= p.Ho) return;
@@ -1398,17 +1349,8 @@ __global__ __launch_bounds__(256, (PREF ? 2 : occ_of<C, PREC, MIXF>())) void con
                         hi[j] = (_Float16)vs;
                         lo[j] = lo_keep((_Float16)__builtin_fmaf((float)hi[j], -1.0f, vs));
                     }
-                    if constexpr ((BSVD_ABL & 32) != 0) {      // timing only: conversion kept alive, stores never executed
-                        if (p.Cout < 0) { *reinterpret_cast<f32x4 *>(dst) = __builtin_bit_cast(f32x4, hi); *reinterpret_cast<f32x4 *>(dst + 8) = __builtin_bit_cast(f32x4, lo); }
-                    } else if constexpr ((BSVD_ABL & 128) != 0) {  // timing only: the same bytes as fully coalesced 2-KB runs per wave and item
-                        float *d2 = p.y + (int64_t)f * 0 + ((int64_t)((blockIdx.x % (gridDim.x - gridDim.x / 16)) * 4 + wid) * NITEM + i) * 512 + elane * 8;   // (stays inside the tensor: edge tiles fold back)
-                        *reinterpret_cast<f32x4 *>(d2) = __builtin_bit_cast(f32x4, hi); *reinterpret_cast<f32x4 *>(d2 + 4) = __builtin_bit_cast(f32x4, lo);
-                    } else if constexpr ((BSVD_ABL & 64) != 0) {   // timing only: stores kept, no split conversion
-                        *reinterpret_cast<f32x4 *>(dst) = f32x4{v[0], v[1], v[2], v[3]}; *reinterpret_cast<f32x4 *>(dst + 8) = f32x4{v[4], v[5], v[6], v[7]};
-                    } else {
                     *reinterpret_cast<f32x4 *>(dst) = __builtin_bit_cast(f32x4, hi);
                     *reinterpret_cast<f32x4 *>(dst + 8) = __builtin_bit_cast(f32x4, lo);
-                    }
                 } else {
                     float *dst = t.dst;
                     *reinterpret_cast<f32x4 *>(dst) = f32x4{v[0], v[1], v[2], v[3]};
@@ -1489,13 +1431,13 @@ static int launch_pref(const ConvParams &p, hipStream_t stream, char *name, int 
     else { set_error("bsvd_conv3x3: no fused-pair kernel for this tile"); return -20; }
 }
 
-static bool fast_ok(const ConvParams &p, bool honour_force_generic = true)
+static bool fast_ok(const ConvParams &p)
 {
     // FAST needs: 16-B aligned vector gather (vec_ok), single-source 16-channel chunks (fold % 16 == 0) and
-    // 32-bit byte offsets inside one frame / the packed weights.  (ablate == 8: timing builds force GENERIC.)
+    // 32-bit byte offsets inside one frame / the packed weights.
     const bool fold_ok = (p.fold & 15) == 0 || (p.fold == 8 && p.Cout <= 64);     // fold 8: mixed chunk 0 in the 64-channel tile
     return p.vec_ok && fold_ok && (int64_t)p.H * p.W * p.Cin * 4 < 0x7fffffffLL &&
-           (int64_t)p.Cin * 9 * p.Cout * 4 < 0x7fffffffLL && !(honour_force_generic && p.ablate == 8);
+           (int64_t)p.Cin * 9 * p.Cout * 4 < 0x7fffffffLL;
 }
 
 template <class C>
@@ -1512,10 +1454,10 @@ int launch_conv3x3(const ConvParams &p, int stride, hipStream_t stream, char *na
     if (p.prec == 1) {
         // split16.  Wide layers: 128-px x 64-ch wave tiles (half the weight bytes per MFMA, twice the step length) at ONE
         // wave per SIMD with the full 512-register file: 430 vs 414 TFLOP/s for the 64x64 tile at 3 waves/SIMD.  (At 2
-        // waves/SIMD the same tile needs > 256 registers and spills in the main loop: 10x slower.  <4,1,2,2,1,3> for
-        // the 64-channel layers: no gain over <2,2,4,1,1,3>.)  Stride 2: single patch buffer -> 3 workgroups/CU
+        // waves/SIMD the same tile needs > 256 registers and spills in the main loop: 10x slower.  <4,1,2,2,1> for
+        // the 64-channel layers: no gain over <2,2,4,1,1>.)  Stride 2: single patch buffer -> 3 workgroups/CU
         // instead of 1 (175 -> 287 TFLOP/s).
-        if (!fast_ok(p, false)) {
+        if (!fast_ok(p)) {
             // say WHICH requirement failed: the split kernel has no generic (per-element gather / 64-bit offset) variant
             if ((int64_t)p.H * p.W * p.Cin * 4 >= 0x7fffffffLL)
                 set_error("bsvd_conv3x3: BSVD_F16X3 addresses one frame with 32-bit byte offsets: H*W*Cin*4 = %lld bytes >= 2 GiB "
@@ -1531,17 +1473,17 @@ int launch_conv3x3(const ConvParams &p, int stride, hipStream_t stream, char *na
         }
         if (p.head_w) {                  // fused network entry (validated by the ABI layer): the 64-channel tile with the first conv inside
             if (stride != 1 || p.fold != 0 || p.Cout > 64 || (p.Cin & 31)) { set_error("bsvd_conv3x3: fused entry needs stride 1, fold 0, Cin %% 32 == 0, Cout <= 64"); return -18; }
-            return launch_headf<ConvCfg<4, 1, 2, 2, 1, 3>>(p, stream, name, name_len);
+            return launch_headf<ConvCfg<4, 1, 2, 2, 1>>(p, stream, name, name_len);
         }
         if (p.y_planar_ch > 0) {         // network exit: 256 px x 32 ch tiles, planar fp32 epilogue
             if (stride != 1 || p.fold != 0 || p.Cout > 32) { set_error("bsvd_conv3x3: planar split output needs stride 1, fold 0, Cout <= 32"); return -16; }
             if (p.pre_w && p.Cin > 64) { set_error("bsvd_conv3x3: fused pair needs Cin = 32 or 64 (two 32-channel pairs of the first conv)"); return -20; }
-            if (p.pre_w) return launch_pref<ConvCfg<2, 1, 4, 1, 1, 3>>(p, stream, name, name_len);       // fused pair: out0 -> exit
-            return launch_cfg<ConvCfg<2, 1, 4, 1, 1, 3>, true, 1>(p, stream, name, name_len);
+            if (p.pre_w) return launch_pref<ConvCfg<2, 1, 4, 1, 1>>(p, stream, name, name_len);       // fused pair: out0 -> exit
+            return launch_cfg<ConvCfg<2, 1, 4, 1, 1>, true, 1>(p, stream, name, name_len);
         }
         if (p.pre_w) {                   // fused 64-channel pair (validated by the ABI layer): the narrow tile with the first conv inside
             if (stride != 1 || p.fold != 0 || p.Cout > 64 || (p.Cin & 31) || p.Cin > 64) { set_error("bsvd_conv3x3: fused pair needs stride 1, fold 0, Cin = 32 or 64, Cout <= 64"); return -20; }
-            return launch_pref<ConvCfg<4, 1, 2, 2, 1, 3>>(p, stream, name, name_len);
+            return launch_pref<ConvCfg<4, 1, 2, 2, 1>>(p, stream, name, name_len);
         }
         if (stride == 2) {
             // (the tile's register double buffer reads every chunk from the frame itself: a stride-2 layer with a temporal shift -- none exists in the
@@ -1558,30 +1500,33 @@ int launch_conv3x3(const ConvParams &p, int stride, hipStream_t stream, char *na
             //  frames/s: a workgroup with half the MFMAs pays the same prologue and epilogue.  profiles/r06k_stride2_small_grid_*.txt)
             // (tools/kernel_resources.sh shows a 68-byte private segment for <4,1,1,4,2>: a reservation only -- the kernel's ISA contains no scratch, flat-scratch or
             //  private buffer instruction; 154 VGPRs, three workgroups per CU)
-            return launch_cfg<ConvCfg<4, 1, 1, 4, 2, 3, false>, true, 1>(p, stream, name, name_len);
+            return launch_cfg<ConvCfg<4, 1, 1, 4, 2, false>, true, 1>(p, stream, name, name_len);
         }
         // The fat tiles run one workgroup per CU, so they need a grid of several rounds of 256; small launches
         // (streaming mode: one frame per launch) keep the 64x64 tiles at 3 workgroups per CU.
         const int64_t fat_wide = (int64_t)p.frames * ((p.Ho + 15) / 16) * ((p.Wo + 15) / 16) * ((p.Cout + 127) / 128);
-        const int fat_min = p.fat_min_wgs > 0 ? p.fat_min_wgs : BSVD_TUNE_FAT_MIN_WGS;      // BsvdConvArgs.fat_min_wgs (0 = the measured default); no hidden state
+        // smallest grid (in 256-px x 128-ch workgroups) that takes the fat split tile (r02: 1020-workgroup launches -- 256-ch layers of a 1080p frame,
+        // upc1 of a 540x960 frame -- are 1-3 % faster fat; 510-540 are not)
+        constexpr int FAT_MIN_WGS = 800;
+        const int fat_min = p.fat_min_wgs > 0 ? p.fat_min_wgs : FAT_MIN_WGS;      // BsvdConvArgs.fat_min_wgs (0 = the measured default); no hidden state
         if (p.Cout > 64) {
             // wave tile of the 256-px x 128-ch workgroup: 128 px x 64 ch (256 px x 32 ch -- half the weight bytes per MFMA, twice the pixel-fragment
             // reads -- 19.21 -> 19.60 ms, r03); small grids (single-frame launches): 128 px x 128 ch workgroups (256 px x 64 ch: 291 -> 281 frames/s, r03)
-            if (fat_wide >= fat_min) return launch_cfg<ConvCfg<4, 2, 2, 2, 1, 3>, true, 1>(p, stream, name, name_len);
-            return launch_cfg<ConvCfg<2, 2, 2, 2, 1, 3>, true, 1>(p, stream, name, name_len);
+            if (fat_wide >= fat_min) return launch_cfg<ConvCfg<4, 2, 2, 2, 1>, true, 1>(p, stream, name, name_len);
+            return launch_cfg<ConvCfg<2, 2, 2, 2, 1>, true, 1>(p, stream, name, name_len);
         }
-        if (p.fold == 8) return launch_cfg<ConvCfg<2, 2, 4, 1, 1, 3>, true, 1, true>(p, stream, name, name_len);   // c32-sized nets
+        if (p.fold == 8) return launch_cfg<ConvCfg<2, 2, 4, 1, 1>, true, 1, true>(p, stream, name, name_len);   // c32-sized nets
         // the 64-channel layers: 128-px x 32-ch wave tiles (<4,1,2,2,1>, 2 waves per SIMD) instead of 64 px x 64 ch at 3 waves per SIMD: half the weight
         // bytes per MFMA (the 64 x 64 tile pulled 4 KB of weights per wave and tap through the L1: ~42 B/clk/CU of its 64), twice the pixel-fragment
         // reads -- a loss with the padded LDS layout (r01), a 7 % gain with the conflict-free quad-planar one (r03: 6.42 -> 5.94 ms per clip).
         // (512-px fat tiles were tried: 9.6 vs 6.8 ms)
-        return launch_cfg<ConvCfg<4, 1, 2, 2, 1, 3>, true, 1>(p, stream, name, name_len);
+        return launch_cfg<ConvCfg<4, 1, 2, 2, 1>, true, 1>(p, stream, name, name_len);
     }
     // exact fp32.  Cout <= 64 (the 540x960-level layers of bsvd_c64): 256 px x 64 ch tiles; wider layers: 128 px x 128 ch.
     // Stride 2 always takes the 128 x 128 tile with a single patch buffer (its 17x33 input patch is what bounds LDS).
     if (stride == 1)
         return p.Cout > 64 ? launch_f32<ConvCfg<2, 2, 2, 2, 1>>(p, stream, name, name_len) : launch_f32<ConvCfg<2, 2, 4, 1, 1>>(p, stream, name, name_len);
-    return launch_f32<ConvCfg<2, 2, 2, 2, 2, 3, false>>(p, stream, name, name_len);
+    return launch_f32<ConvCfg<2, 2, 2, 2, 2, false>>(p, stream, name, name_len);
 }
 
 }  // namespace bsvd

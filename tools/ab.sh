@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B of compile-time tuning variants ON THE GPU BOX, interleaved in one session (box-to-box variance is large).
-# usage: tools/ab.sh "<flags A>" "<flags B>" ...   e.g.  tools/ab.sh "" "-DBSVD_TUNE_D=2" "-DBSVD_TUNE_ALIGN=1"
+# usage: tools/ab.sh "<flags A>" "<flags B>" ...   e.g.  tools/ab.sh "" "-DBSVD_WX_TAIL=1" "-DBSVD_WX_TAIL=0"
 cd $GRAFT_REPO_ROOT
 i=0
 for f in "$@"; do

@@ -15,7 +15,7 @@ import collections, csv, glob, json, os, re, sys
 
 def kernel_key(name):
     """rocprof kernel name -> the variant names bench.py uses (LaunchTimer.variant)."""
-    m = re.search(r"conv3x3_kernel<bsvd::ConvCfg<(\d+), (\d+), (\d+), (\d+), (\d+), \d+(?:, (?:true|false))?>, (true|false), (\d)(?:, (true|false))?(?:, (true|false))?(?:, (true|false))?>", name)
+    m = re.search(r"conv3x3_kernel<bsvd::ConvCfg<(\d+), (\d+), (\d+), (\d+), (\d+)(?:, \d+)?(?:, (?:true|false))?>, (true|false), (\d)(?:, (true|false))?(?:, (true|false))?(?:, (true|false))?>", name)
     if m:
         mt, nt, wm, wn, st, fast, prec, mix, headf, pref = m.groups()
         planar = "[planar out]" if (mt, nt, wm, wn) == ("2", "1", "4", "1") and prec == "1" else ""     # the exit tile's only use
