@@ -19,7 +19,27 @@ void set_error(const char *fmt, ...)
 }
 
 // ---------------------------------------------------------------------------------------------
-// weight pre-pack: OIHW fp32 -> [Cin_pad/16][9][4][Cout_pad][4]
+// weight pre-pack.  A PixelShuffle layer (ps) is packed sub-pixel major -- packed channel np = [4 sub-pixels][Cout_pad / 4] <- source
+// channel 4 ch + sub -- so that the 8 channels a lane stores land in one output pixel.
+// The bias in that channel order: the first Cout_pad elements of every pack kernel's sweep write it.
+__device__ __forceinline__ void pack_bias(int64_t i, const float *__restrict__ bias, int ps, int Cout, int Cout_pad, float *__restrict__ bp)
+{
+    const int Cq_pad = Cout_pad >> 2, Cq = Cout >> 2;
+    if (bp && i < Cout_pad) {
+        int nb = (int)i;
+        bool okb;
+        if (ps) {
+            const int sub = nb / Cq_pad, ch = nb - sub * Cq_pad;
+            okb = ch < Cq;
+            nb = 4 * ch + sub;
+        } else {
+            okb = nb < Cout;
+        }
+        bp[i] = (okb && bias) ? bias[nb] : 0.f;
+    }
+}
+
+// OIHW fp32 -> [Cin_pad/16][9][4][Cout_pad][4]
 __global__ void pack_weights_kernel(const float *__restrict__ w, const float *__restrict__ bias, int Cin, int Cout,
                                     int Cin_pad, int Cout_pad, int ps, float *__restrict__ wp,
                                     float *__restrict__ bp)
@@ -44,18 +64,7 @@ __global__ void pack_weights_kernel(const float *__restrict__ w, const float *__
             ok = ok && np < Cout;
         }
         wp[i] = ok ? w[((int64_t)n * Cin + c) * 9 + tap] : 0.f;
-        if (bp && i < Cout_pad) {
-            int nb = (int)i;
-            bool okb;
-            if (ps) {
-                const int sub = nb / Cq_pad, ch = nb - sub * Cq_pad;
-                okb = ch < Cq;
-                nb = 4 * ch + sub;
-            } else {
-                okb = nb < Cout;
-            }
-            bp[i] = (okb && bias) ? bias[nb] : 0.f;
-        }
+        pack_bias(i, bias, ps, Cout, Cout_pad, bp);
     }
 }
 
@@ -88,19 +97,8 @@ __global__ void pack_weights_split_kernel(const float *__restrict__ w, const flo
         float v = ok ? w[((int64_t)n * Cin + c) * 9 + tap] : 0.f;
         v = fminf(fmaxf(v, -65504.f), 65504.f);        // fp16 range: saturate, never an (inf, NaN) pair (hosts refuse such weights first)
         const _Float16 hi = (_Float16)v;
-        wp[i] = part ? lo_keep((_Float16)(v - (float)hi)) : hi;
-        if (bp && i < Cout_pad) {
-            int nb = (int)i;
-            bool okb;
-            if (ps) {
-                const int sub = nb / Cq_pad, ch = nb - sub * Cq_pad;
-                okb = ch < Cq;
-                nb = 4 * ch + sub;
-            } else {
-                okb = nb < Cout;
-            }
-            bp[i] = (okb && bias) ? bias[nb] : 0.f;
-        }
+        wp[i] = part ? (_Float16)(v - (float)hi) : hi;
+        pack_bias(i, bias, ps, Cout, Cout_pad, bp);
     }
 }
 
@@ -141,19 +139,8 @@ __global__ void pack_weights_wino_kernel(const float *__restrict__ w, const floa
         // such a layer on the direct form (engine.PackedNet tests max |w| x the form's largest |G| row sum against fp16's range)
         u = u > 65504.0 ? 65504.0 : (u < -65504.0 ? -65504.0 : u);
         const _Float16 hi = (_Float16)u;
-        wp[i] = part ? lo_keep((_Float16)(u - (double)hi)) : hi;
-        if (bp && i < Cout_pad) {
-            int nb = (int)i;
-            bool okb;
-            if (ps) {
-                const int sub = nb / Cq_pad, ch = nb - sub * Cq_pad;
-                okb = ch < Cq;
-                nb = 4 * ch + sub;
-            } else {
-                okb = nb < Cout;
-            }
-            bp[i] = (okb && bias) ? bias[nb] : 0.f;
-        }
+        wp[i] = part ? (_Float16)(u - (double)hi) : hi;
+        pack_bias(i, bias, ps, Cout, Cout_pad, bp);
     }
 }
 
@@ -271,7 +258,7 @@ __global__ void pack_head_weights_kernel(const float *__restrict__ w, const floa
         const _Float16 hi = (_Float16)v;
         _Float16 *dst = wp + ((int64_t)(ps * 64 + lane)) * 16;
         dst[j] = hi;
-        dst[8 + j] = lo_keep((_Float16)(v - (float)hi));
+        dst[8 + j] = (_Float16)(v - (float)hi);
     }
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < Cmid_pad; i += gridDim.x * blockDim.x)
         bp[i] = (bias && i < Cmid) ? bias[i] : 0.f;
@@ -460,12 +447,8 @@ static int conv3x3_impl(const BsvdConvArgs *a, void *stream, char *name, int nam
     if (a->w_wino_packed) {      // Winograd form of a wide layer: explicit request, no silent fall-back to the direct kernel
         if (a->x_planar_ch > 0 || a->head_w_packed) { set_error("bsvd_conv3x3: w_wino_packed: not with a planar / fused entry"); return -19; }
         if (const char *why = wino_unsupported(p, a->stride)) { set_error("bsvd_conv3x3: w_wino_packed (F(%d,3)): %s", a->wino_m, why); return -19; }
-#ifdef BSVD_MEASURE
-        if (p.wino_m >= 10 && p.wino_m < 20) {        // the all-positions-per-wave kernel (conv3x3_wino.hip) knows fp16 pairs only
-            if (a->x_f32 || a->y_f32) { set_error("bsvd_conv3x3: x_f32 / y_f32 are not available for wino_m %d", p.wino_m); return -21; }
-            return launch_wino(p, (hipStream_t)stream, name, name_len);
-        }
-#endif
+        // the all-positions-per-wave kernel (conv3x3_wino.hip, measurement builds) knows fp16 pairs only
+        if (p.wino_m >= 10 && p.wino_m < 20 && (a->x_f32 || a->y_f32)) { set_error("bsvd_conv3x3: x_f32 / y_f32 are not available for wino_m %d", p.wino_m); return -21; }
         return launch_winox(p, (hipStream_t)stream, name, name_len);
     }
     if (a->pre_w_packed) {       // fused pair of plain stride-1 convs: explicit request, never a silent two-launch fall-back

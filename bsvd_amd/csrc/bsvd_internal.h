@@ -46,7 +46,7 @@ struct ConvParams {
     int32_t x_v, y_v, v_wg;
     // Winograd form of the wide split-fp16 layers (BsvdConvArgs.w_wino_packed): w then points at the transformed pack
     int32_t fat_min_wgs;     // BsvdConvArgs.fat_min_wgs (0 = default): smallest grid that takes the 128-accumulator split tile
-    int32_t wino_m;          // 0 = direct convolution; 2 | 4 | 6 = F(wino_m, 3) along x (conv3x3_winox.hip); 12 | 14 = the all-positions-per-wave kernel (conv3x3_wino.hip)
+    int32_t wino_m;          // 0 = direct convolution; 2 | 4 | 6 = F(wino_m, 3) along x (conv3x3_winox.hip); 12 = the all-positions-per-wave kernel (conv3x3_wino.hip)
 };
 
 // Transformed-domain layout (include/bsvd_hip.h, BsvdConvArgs.x_v / y_v): a frame is [row][tile of 8 groups][16-channel chunk] BLOCKS of
@@ -57,24 +57,6 @@ __host__ __device__ constexpr int v_block_floats(int m) { return ((m + 2) * 4 * 
 
 void set_error(const char *fmt, ...);
 
-// Experiment knob: keep only the top BSVD_TUNE_LO_BITS mantissa bits of the `lo` half of a split16 pair (10 = all;
-// -1 = lo := 0).  Probes how much of the power-limited split kernel's energy is operand toggling.
-#ifndef BSVD_TUNE_LO_BITS
-#define BSVD_TUNE_LO_BITS 10
-#endif
-__host__ __device__ inline _Float16 lo_keep(_Float16 lo)
-{
-#if BSVD_TUNE_LO_BITS >= 10
-    return lo;
-#elif BSVD_TUNE_LO_BITS < 0
-    return (_Float16)0.f;
-#else
-    unsigned short u = __builtin_bit_cast(unsigned short, lo);
-    u &= (unsigned short)~((1u << (10 - BSVD_TUNE_LO_BITS)) - 1u);
-    return __builtin_bit_cast(_Float16, u);
-#endif
-}
-
 // fp16 range of the split mode.  Every value is carried as hi = fp16(v), lo = fp16(v - hi); a conversion that overflows to +-inf turns
 // the pair into (inf, NaN) and every product it meets into NaN.  The stores of the direct kernel clamp to +-65504 first (v_med3_f32),
 // but the Winograd kernel converts TRANSFORMED values -- sums of up to 2x (F(2,3)), 3x (F(4,3)), 4.7x (F(6,3)) the activation range --
@@ -84,20 +66,12 @@ __host__ __device__ inline _Float16 lo_keep(_Float16 lo)
 // (65504, 131008] a pair still represents v, at lo's own 11-bit precision (relative error <= 2^-13 instead of 2^-22: graceful), and
 // beyond it saturates -- no instruction, no inf, no NaN from finite inputs.  Set once at kernel entry by every kernel that produces
 // fp16 pairs; MFMAs (fp32 results) are not affected.  Verified on MI355X: tests/test_gpu_range.py.
-#ifndef BSVD_FP16_OVFL
-#define BSVD_FP16_OVFL 1
-#endif
 // The split STORES keep their explicit clamp to +-65504 (one v_med3_f32 per value of a layer without a bounded activation): a stored pair
-// then always has |lo| <= ulp(hi) / 2, i.e. full pair precision, whatever produced it.  0 = rely on the saturating conversions alone
-// (A/B knob: the epilogues do not wait for these instructions, r03 / r05 records).
-#ifndef BSVD_EPI_CLAMP
-#define BSVD_EPI_CLAMP 1
-#endif
+// then always has |lo| <= ulp(hi) / 2, i.e. full pair precision, whatever produced it.  (The clamp-free form, relying on the saturating conversions alone, was A/B-ed and
+// bought nothing: the epilogues do not wait for these instructions, r03 / r05 records.)
 __device__ __forceinline__ void fp16_saturate_on()
 {
-#if BSVD_FP16_OVFL
     __builtin_amdgcn_s_setreg((0 << 11) | (23 << 6) | 1 /* hwreg(HW_REG_MODE, 23, 1) */, 1);
-#endif
 }
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is a per-device property of a kernel: remember, per device, the largest

@@ -618,7 +618,7 @@ __global__ __launch_bounds__(256, (PREF ? 2 : occ_of<C, PREC>())) void conv3x3_k
                         float v = hacc[8 * h + j] + bia[h][j >> 2][j & 3];
                         v = inside ? __builtin_amdgcn_fmed3f(v, vlo, vhi) : 0.f;
                         hi[j] = (_Float16)v;
-                        lo[j] = lo_keep((_Float16)(v - (float)hi[j]));
+                        lo[j] = (_Float16)(v - (float)hi[j]);
                     }
                     float *dst = patch_buf + h * C::PATCH_FLOATS + C::lds_off(py, px, lh);
                     if (m < NPIX) {
@@ -785,7 +785,7 @@ __global__ __launch_bounds__(256, (PREF ? 2 : occ_of<C, PREC>())) void conv3x3_k
                         float v = pacc[PAIR][j][8 * h + k] + bia[h][k >> 2][k & 3];
                         v = px_in ? __builtin_amdgcn_fmed3f(v, vlo, vhi) : 0.f;
                         hi[k] = (_Float16)v;
-                        lo[k] = lo_keep((_Float16)__builtin_fmaf((float)hi[k], -1.0f, v));
+                        lo[k] = (_Float16)__builtin_fmaf((float)hi[k], -1.0f, v);
                     }
                     float *dst = patch_buf + h * C::PATCH_FLOATS + d_p;
                     if (px_st) {
@@ -811,7 +811,7 @@ __global__ __launch_bounds__(256, (PREF ? 2 : occ_of<C, PREC>())) void conv3x3_k
                     float v = (ok && c < p.head_cin) ? xin[c * plane + (int64_t)gy * p.W + gx] : 0.f;
                     v = __builtin_amdgcn_fmed3f(v, -65504.f, 65504.f);      // fp16 range guard like every split store: saturate, never an inf / NaN pair
                     h4[c] = (_Float16)v;
-                    l4[c] = lo_keep((_Float16)(v - (float)h4[c]));
+                    l4[c] = (_Float16)(v - (float)h4[c]);
                 }
                 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
                 u32x4 o;
@@ -1338,7 +1338,7 @@ __global__ __launch_bounds__(256, (PREF ? 2 : occ_of<C, PREC>())) void conv3x3_k
                     *reinterpret_cast<f32x4 *>(dst + 4) = f32x4{v[4], v[5], v[6], v[7]};
                 } else if constexpr (PREC == 1) {
                     float *dst = t.dst;
-                    constexpr bool bounded = (ACT == BSVD_ACT_RELU6 && EPI == BSVD_EPI_PLAIN) || !BSVD_EPI_CLAMP;
+                    constexpr bool bounded = (ACT == BSVD_ACT_RELU6 && EPI == BSVD_EPI_PLAIN);
                     f16x8 hi, lo;
                     // (lo = fp16(v - hi) as inline-asm v_fma_mix{lo,hi}_f16 was tried in r03: 12 instead of 20 conversion instructions
                     //  per 8 channels, bit-identical, 64-channel tile 6.22 -> 6.18 ms per clip but the fat tile 19.74 -> 19.87 -- and an
@@ -1347,7 +1347,7 @@ __global__ __launch_bounds__(256, (PREF ? 2 : occ_of<C, PREC>())) void conv3x3_k
                     for (int j = 0; j < 8; ++j) {        // fp16 range guard: saturate instead of inf/NaN pairs
                         const float vs = bounded ? v[j] : __builtin_amdgcn_fmed3f(v[j], -65504.f, 65504.f);
                         hi[j] = (_Float16)vs;
-                        lo[j] = lo_keep((_Float16)__builtin_fmaf((float)hi[j], -1.0f, vs));
+                        lo[j] = (_Float16)__builtin_fmaf((float)hi[j], -1.0f, vs);
                     }
                     *reinterpret_cast<f32x4 *>(dst) = __builtin_bit_cast(f32x4, hi);
                     *reinterpret_cast<f32x4 *>(dst + 8) = __builtin_bit_cast(f32x4, lo);

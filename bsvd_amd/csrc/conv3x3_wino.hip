@@ -1,5 +1,5 @@
 // conv3x3_wino.hip -- the wide stride-1 layers of the split-fp16 (BSVD_F16X3) mode as a 1-D Winograd F(M,3) convolution
-// along x, M = 2 or 4, for gfx950 (MI355X).  See wino_forms.h for the forms and DESIGN.md §4.1d for the design record.
+// along x, M = 2, for gfx950 (MI355X).  See wino_forms.h for the forms and DESIGN.md §4.1d for the design record.
 //
 // Why: the direct 3-pass split kernel (conv3x3_mfma.hip) runs at the package power cap with the matrix pipe 0.75 busy; what is
 // left is issuing fewer MFMAs.  Along x, F(4,3) turns the 9 tap-GEMMs of a 3x3 conv into 6 positions x 3 rows of GEMMs over a
@@ -7,12 +7,12 @@
 //
 //   y[f] = epilogue( act( conv3x3( gather(x[f-1], x[f], x[f+1], fold) ) + bias ) )        (same contract as bsvd_conv3x3)
 //
-// Work split.  A *sub-tile* is 16 px x SR rows of output (SR = 8 for F(2,3), 16 for F(4,3)) = two 32-"group" MFMA tiles
+// Work split.  A *sub-tile* is 16 px x SR rows of output (SR = 8 for F(2,3)) = two 32-"group" MFMA tiles
 // (a group = M consecutive output pixels of a row: GW = 16 / M groups per sub-tile row, RM = 32 / GW rows per MFMA tile).
 // Workgroup = 4 waves = 2 sub-tiles (waves 0-1 / 2-3) x 2 halves of 128 output channels; a wave owns, for EVERY transformed
-// position xi < A = M + 2, 2 x 2 MFMA tiles (64 groups x 64 channels): A * 64 accumulator registers (256 / 384), one wave per
-// SIMD.  hipcc keeps at most 256 accumulator registers in AGPRs; for F(4,3) positions 4 and 5 are therefore accumulated by
-// inline-asm MFMAs pinned to arch VGPRs (HYB).
+// position xi < A = M + 2, 2 x 2 MFMA tiles (64 groups x 64 channels): A * 64 = 256 accumulator registers, one wave per
+// SIMD.  (F(4,3) needs 384, more than hipcc keeps in AGPRs: its instantiation -- positions 4 and 5 accumulated by inline-asm MFMAs
+// pinned to arch VGPRs, 264 B of scratch -- never passed parity and was removed; git has it, last present in a864482.)
 //
 // K loop: 16-channel chunks; per chunk A x 3 steps (xi, ky) of 12 MFMAs (3 split passes x 2 x 2 tiles).
 //   * group operand V[xi]: the transformed activations of the chunk, double-buffered in LDS as planes
@@ -27,19 +27,14 @@
 // Epilogue: AT in fp32 on the accumulators, then the direct kernel's split epilogue per output column j < M (wave-private LDS
 // transposition so that 4 adjacent lanes write one pixel's 128 contiguous bytes; bias, activation, PixelShuffle + skip add).
 // MEASUREMENT VARIANT: compiled into measurement builds only (-DBSVD_MEASURE, tools/build_measure.sh); the product library
-// does not contain this kernel.  Kept as the record of the first design of DESIGN.md 4.1d (wino_m 12 / 14).
+// does not contain this kernel.  Kept as the record of the first design of DESIGN.md 4.1d (wino_m 12).
 #ifdef BSVD_MEASURE
 #include <stdio.h>
 #include <type_traits>
 #include "bsvd_internal.h"
 #include "wino_forms.h"
 
-#ifndef BSVD_WINO_OOB
 #define BSVD_WINO_OOB 0x7fffffffu
-#endif
-#ifndef BSVD_WINO_ZSKIP
-#define BSVD_WINO_ZSKIP 1       // leave the all-zero temporal-shift chunks of a clip's first / last frame out of K (bit-identical)
-#endif
 
 namespace bsvd {
 
@@ -80,11 +75,11 @@ struct WinoCfg {
     static constexpr int LPR = ((NITEM + NR - 1) / NR + 15) / 16 * 16;   // lanes per round (16-lane ds_write groups stay whole)
     static_assert(LPR <= 256 && NITEM_SUB % 16 == 0 && (NSLOT * 2) % 16 == 0, "");
     static constexpr int NS = 3 * A;             // steps per chunk
-    static constexpr int CPS = M == 4 ? 1 : 2;   // channels of an item transformed per step
+    static constexpr int CPS = 2;                // channels of an item transformed per step
     static constexpr int CSTEPS = 4 / CPS;       // steps one round's transform is spread over
     static constexpr int WIN = A - CSTEPS;       // steps between a round's loads and its first transform step
     static_assert(WIN >= 0 && LDS_BYTES <= 160 * 1024 && 4 * 32 * 36 * 4 <= LDS_BYTES, "");
-    static constexpr bool HYB = A * 64 > 256;    // positions >= 4 accumulate in arch VGPRs through inline-asm MFMAs
+    static_assert(A * 64 <= 256, "every position's accumulators in AGPRs");
 };
 
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void *ptr, unsigned bytes)
@@ -153,8 +148,8 @@ __global__ __launch_bounds__(256, 1) void wino_kernel(const ConvParams p)
     else                  { nxt = p.halo_next; next_ps = p.halo_next_ps; next_co = p.halo_next_co; }
 
     int ncb = p.Cin >> 4;
-    int zs_a = 0, zs_b = 1 << 20, zs_c = 0;
-    if (BSVD_WINO_ZSKIP && p.fold >= 16) {
+    int zs_a = 0, zs_b = 1 << 20, zs_c = 0;      // the all-zero temporal-shift chunks of a clip's first / last frame stay out of K (bit-identical)
+    if (p.fold >= 16) {
         const int f16 = p.fold >> 4;
         zs_b = f16;
         if (nxt == nullptr) zs_a = f16;
@@ -247,7 +242,7 @@ __global__ __launch_bounds__(256, 1) void wino_kernel(const ConvParams p)
             for (int i = 0; i < A; ++i) {
                 const _Float16 hh = (_Float16)v[i];
                 vh[i][c] = hh;
-                vl[i][c] = lo_keep((_Float16)(v[i] - (float)hh));
+                vl[i][c] = (_Float16)(v[i] - (float)hh);
             }
         }
     };
@@ -332,16 +327,12 @@ __global__ __launch_bounds__(256, 1) void wino_kernel(const ConvParams p)
                         // pass 0: hi(w) x lo(v), 1: lo(w) x hi(v), 2: hi(w) x hi(v)
                         const f16x8 bv = __builtin_bit_cast(f16x8, b[nt][pass == 1 ? 1 : 0]);
                         const f16x8 av = __builtin_bit_cast(f16x8, a[mt][pass == 0 ? 1 : 0]);
-                        if constexpr (C::HYB && XI >= 4)
-                            asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(acc[XI][mt][nt]) : "v"(bv), "v"(av));
-                        else
-                            acc[XI][mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bv, av, acc[XI][mt][nt], 0, 0, 0);
+                        acc[XI][mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bv, av, acc[XI][mt][nt], 0, 0, 0);
                     }
             ++step;
         });
         __syncthreads();
     }
-    if constexpr (C::HYB) asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");     // asm MFMA results -> VALU reads (the compiler does not see the hazard)
 
     // ---- epilogue
     const bool mylive = wpx ? slive[1] : slive[0];
@@ -430,7 +421,7 @@ __global__ __launch_bounds__(256, 1) void wino_kernel(const ConvParams p)
                             for (int k = 0; k < 8; ++k) {
                                 const float vs = bounded ? v[k] : __builtin_amdgcn_fmed3f(v[k], -65504.f, 65504.f);
                                 hi[k] = (_Float16)vs;
-                                lo[k] = lo_keep((_Float16)__builtin_fmaf((float)hi[k], -1.0f, vs));
+                                lo[k] = (_Float16)__builtin_fmaf((float)hi[k], -1.0f, vs);
                             }
                             *reinterpret_cast<f32x4 *>(dst) = __builtin_bit_cast(f32x4, hi);
                             *reinterpret_cast<f32x4 *>(dst + 8) = __builtin_bit_cast(f32x4, lo);
@@ -476,7 +467,7 @@ static int launch_wino_m(const ConvParams &pin, hipStream_t stream, char *name, 
 
 int launch_wino(const ConvParams &p, hipStream_t stream, char *name, int name_len)
 {
-    return launch_wino_m<2>(p, stream, name, name_len);      // (F(4,3) on this kernel -- 264 B of scratch, never parity-green -- is not instantiated)
+    return launch_wino_m<2>(p, stream, name, name_len);
 }
 
 }  // namespace bsvd

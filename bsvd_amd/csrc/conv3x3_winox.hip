@@ -36,13 +36,7 @@
 #include "wino_forms.h"
 
 #define BSVD_WX_OOB 0x7fffffffu
-#ifndef BSVD_WX_PERSIST_MIN
-#define BSVD_WX_PERSIST_MIN (1 << 20)   // tiles per CU from which F(2,3) launches take the persistent form.  Measured SLOWER: never, by default
-#endif
 #define BSVD_CUS 256       // MI355X: 256 CUs, one 8-wave workgroup of this kernel each (the tile choice of small grids, launch_winox)
-#ifndef BSVD_WX_ABL
-#define BSVD_WX_ABL 0      // TIMING-ONLY ablations (results wrong): 1 no transform in the K loop, 2 no MFMA steps, 4 no epilogue finish, 8 no chunk barrier, 16 transform without its global loads (constant operands: also removes operand toggling), 32 transform without its LDS stores, 64 the K loop re-transforms the prologue's raw registers (no activation loads in the loop, realistic operand values), 128 the transformed-domain epilogue without its plane stores, 256 without its edge-record stores, 512 no patch pass behind it
-#endif
 
 namespace bsvd {
 
@@ -85,6 +79,17 @@ __host__ __device__ __forceinline__ WxGrid wx_grid(int nty, int ntx, int nct, in
     g.nreg = g.fold ? nct * ntx * (nty - 1) : nct * ntx * nty;
     g.per_frame = g.fold ? g.nreg + nct * ((ntx + 1) >> 1) : g.nreg;
     return g;
+}
+
+// XCD-aware tile walk: workgroup b runs on XCD b % 8 and every XCD owns one contiguous range of the launch's tile list
+struct WxRange { int first, count; };
+__device__ __forceinline__ WxRange wx_xcd_range(int ntiles, int xcd)
+{
+    const int q8 = ntiles >> 3, r8 = ntiles & 7;
+    WxRange r;
+    r.first = xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8;
+    r.count = q8 + (xcd < r8 ? 1 : 0);
+    return r;
 }
 
 template <int M_, int NH_, int NTW_, int MT_ = 4, bool PERSIST_ = false, bool FOLD_ = false>
@@ -162,7 +167,6 @@ __device__ __forceinline__ float dec_pair(unsigned h, unsigned l, const MixConst
 __device__ __forceinline__ void split_pair(float v0, float v1, unsigned &hp, unsigned &lp, const MixConst &k)
 {
     typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
-    static_assert(BSVD_TUNE_LO_BITS >= 10, "the mixed-precision split keeps all bits of the lo halves");
     const f16x2_t hv = {(_Float16)v0, (_Float16)v1};                                  // v_cvt_pk_f16_f32 (round to nearest even)
     hp = __builtin_bit_cast(unsigned, hv);
 #if BSVD_WX_MIXASM
@@ -174,9 +178,7 @@ __device__ __forceinline__ void split_pair(float v0, float v1, unsigned &hp, uns
     // tests/measure_driver.py (`mixasm`).
     asm("v_fma_mixlo_f16 %0, %1, %2, %3 op_sel_hi:[1,0,0]\n\t"
         "v_fma_mixhi_f16 %0, %1, %2, %4 op_sel:[1,0,0] op_sel_hi:[1,0,0]"
-#if BSVD_WX_MIXASM != 2      // (2: without the trailing wait state -- A/B of its cost only)
         "\n\ts_nop 0"
-#endif
         : "=&v"(lp) : "v"(hp), "s"(k.mone), "v"(v0), "v"(v1));
 #else
     const f16x2_t lv = {(_Float16)__builtin_fmaf((float)hv[0], k.mone, v0), (_Float16)__builtin_fmaf((float)hv[1], k.mone, v1)};
@@ -264,8 +266,8 @@ __device__ __forceinline__ void winox_tile(const ConvParams &p)
     const WxGrid G = wx_grid(p.nty, p.ntx, p.nct, p.Ho, FG != 0);
     const int ntiles = p.frames * G.per_frame;
     const int bid = blockIdx.x, xcd = bid & 7;
-    const int q8 = ntiles >> 3, r8 = ntiles & 7;
-    const int xcd_first = xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8, xcd_count = q8 + (xcd < r8 ? 1 : 0);
+    const WxRange xr = wx_xcd_range(ntiles, xcd);
+    const int xcd_first = xr.first, xcd_count = xr.count;
     const int xcd_wgs = ((int)gridDim.x - xcd + 7) >> 3;      // workgroups of this launch on this XCD (== xcd_count when not persistent)
     // (XV: a "pixel" of the byte arithmetic below is one (row, group, position) slot: v_wg groups x A positions per row)
     const unsigned hw = XV ? (unsigned)p.H * (unsigned)(p.v_wg >> 3) * ((unsigned)v_block_floats(M) / 16u) : (unsigned)p.H * (unsigned)p.W;
@@ -320,7 +322,7 @@ __device__ __forceinline__ void winox_tile(const ConvParams &p)
     //  registers -- 140 v_writelane / 2200 v_readlane -- and spills ~20 vector registers; a scratch reload in the epilogue waits, through
     //  the in-order vmcnt, for the previous round's stores.  A tile table in LDS read back with v_readfirstlane removed the scalar spills
     //  and cost more than it saved (the reads' lgkmcnt(0) waits sit inside the MFMA steps).  Measured 6-13 % slower than one tile per
-    //  workgroup; kept for the record, never selected: BSVD_WX_PERSIST_MIN.)
+    //  workgroup; kept for the record, run by measurement builds only (wino_m 62).)
     auto next_tile = [&]() __attribute__((always_inline)) {
         // (an L2 prefetch for the CU's next workgroup from here -- the requests behind a tile's last chunk sent to the tile 32 / 64 places
         //  further down the XCD's list -- is 3.7 % slower: DESIGN 4.1d, removed knob BSVD_WX_PFNEXT)
@@ -442,10 +444,7 @@ __device__ __forceinline__ void winox_tile(const ConvParams &p)
 #pragma unroll
         for (int i = 0; i < A; ++i) {
             const unsigned voff = (unsigned)(gx0 + i) < (unsigned)p.W ? base + (unsigned)i * c.ps4 : BSVD_WX_OOB;
-            if constexpr (BSVD_WX_ABL & 16) {
-#pragma unroll
-                for (int k = 0; k < NDW; ++k) { r.h[i][k] = 0x3c003c00u ^ (voff & 0x00ff00ffu); r.l[i][k] = 0x1c001c00u; }
-            } else if constexpr (CH == 4) {
+            if constexpr (CH == 4) {
                 const u32x2 hv = buf_load2(c.rs, voff, c.soff), lv = buf_load2(c.rs, voff, c.soff + 32u);
                 r.h[i][0] = hv[0]; r.h[i][NDW - 1] = hv[1]; r.l[i][0] = lv[0]; r.l[i][NDW - 1] = lv[1];
             } else {
@@ -494,7 +493,7 @@ __device__ __forceinline__ void winox_tile(const ConvParams &p)
             for (int i = 0; i < A; ++i) {
                 unsigned hp, lp;
                 split_pair(v[0][i], v[1][i], hp, lp, mixk);
-                if (active && !((BSVD_WX_ABL & 32) && hp == 0x12345678u)) {
+                if (active) {
                     *reinterpret_cast<unsigned *>(dst + i * 4 * C::PLANE + cp * 4) = hp;
                     *reinterpret_cast<unsigned *>(dst + i * 4 * C::PLANE + 2 * C::PLANE + cp * 4) = lp;
                 }
@@ -682,21 +681,21 @@ __device__ __forceinline__ void winox_tile(const ConvParams &p)
             //  would be zeros from zero-size descriptors, a whole transform phase per tile for nothing)
             constexpr bool TS_FIN = !PERSIST, TS_LD = TS_FIN && M == 2;      // (F(6,3) with the request skip too: 25 spills)
             if constexpr (XP & 1) if (!TS_FIN || cb + 1 < ncb) chunk_finish(cb + 1, pnext, setv, PAll{}, tl);
-            if constexpr (XP & 2) if (!(BSVD_WX_ABL & 64) && (!TS_LD || cb + 1 + PP < ncb)) chunk_load(cb + 1 + PP, setv, PAll{}, tl);
+            if constexpr (XP & 2) if (!TS_LD || cb + 1 + PP < ncb) chunk_load(cb + 1 + PP, setv, PAll{}, tl);
         };
         // (one copy of the MFMA steps between two conditional transforms: an if / else with the phases in opposite orders made the
         //  register allocator carry the accumulators in two register sets and spill 60-260 registers)
         [[maybe_unused]] const unsigned long long t0 = WXT_NOW();
         using XFin = std::integral_constant<int, 3>;
-        if (!(BSVD_WX_ABL & 1) && phase != 0) xform(XFin{});
+        if (phase != 0) xform(XFin{});
         __builtin_amdgcn_sched_barrier(0);
         [[maybe_unused]] const unsigned long long t1 = WXT_NOW();
-        if (!(BSVD_WX_ABL & 2)) mfma_phase(std::integral_constant<int, C::MT>{});
+        mfma_phase(std::integral_constant<int, C::MT>{});
         __builtin_amdgcn_sched_barrier(0);
         [[maybe_unused]] const unsigned long long t2 = WXT_NOW();
-        if (!(BSVD_WX_ABL & 1) && phase == 0) xform(XFin{});
+        if (phase == 0) xform(XFin{});
         [[maybe_unused]] const unsigned long long t3 = WXT_NOW();
-        if (!(BSVD_WX_ABL & 8)) __syncthreads();
+        __syncthreads();
 #ifdef BSVD_WX_TL
         { const unsigned long long t4 = WXT_NOW(); tl_acc[0] += t1 - t0; tl_acc[1] += t2 - t1; tl_acc[2] += t3 - t2; tl_acc[3] += t4 - t3; }
 #endif
@@ -779,8 +778,7 @@ __device__ __forceinline__ void winox_tile(const ConvParams &p)
             __syncthreads();
             if constexpr (YV) {
             [&]() __attribute__((always_inline)) {
-            static_assert(!YV || EPI == BSVD_EPI_PLAIN || true, "");
-            if (part >= C::NPART || (BSVD_WX_ABL & 4)) return;
+            if (part >= C::NPART) return;
             // one finisher wave per (block, half of the MFMA tile's rows): sidx = part, part + NPART, ..
 #pragma unroll
             for (int s0 = 0; s0 < 2; s0 += C::NPART) {
@@ -839,13 +837,13 @@ __device__ __forceinline__ void winox_tile(const ConvParams &p)
 #pragma unroll
                     for (int x = 0; x < A; ++x) vv[x][k] = vout[x];
                 }
-                if (live && g == 0 && !(BSVD_WX_ABL & 256)) {
+                if (live && g == 0) {
                     *reinterpret_cast<f32x4 *>(erow) = f32x4{vv[0][0], vv[0][1], vv[0][2], vv[0][3]};
                     *reinterpret_cast<f32x4 *>(erow + 4) = f32x4{vv[0][4], vv[0][5], vv[0][6], vv[0][7]};
                     *reinterpret_cast<f32x4 *>(erow + 2 * p.Cout) = f32x4{d[1][0], d[1][1], d[1][2], d[1][3]};
                     *reinterpret_cast<f32x4 *>(erow + 2 * p.Cout + 4) = f32x4{d[1][4], d[1][5], d[1][6], d[1][7]};
                 }
-                if (live && g == 7 && !(BSVD_WX_ABL & 256)) {
+                if (live && g == 7) {
                     *reinterpret_cast<f32x4 *>(erow + p.Cout) = f32x4{vv[A - 1][0], vv[A - 1][1], vv[A - 1][2], vv[A - 1][3]};
                     *reinterpret_cast<f32x4 *>(erow + p.Cout + 4) = f32x4{vv[A - 1][4], vv[A - 1][5], vv[A - 1][6], vv[A - 1][7]};
                     *reinterpret_cast<f32x4 *>(erow + 3 * p.Cout) = f32x4{d[M][0], d[M][1], d[M][2], d[M][3]};
@@ -858,7 +856,7 @@ __device__ __forceinline__ void winox_tile(const ConvParams &p)
                     unsigned hp[4], lp[4];
 #pragma unroll
                     for (int c = 0; c < 4; ++c) split_pair(vv[x][2 * c], vv[x][2 * c + 1], hp[c], lp[c], mixk);
-                    if (live && !((BSVD_WX_ABL & 128) && hp[0] != 0x12345678u)) {
+                    if (live) {
                         *reinterpret_cast<f32x4 *>(vrow + x * 128) = __builtin_bit_cast(f32x4, u32x4_t{hp[0], hp[1], hp[2], hp[3]});
                         *reinterpret_cast<f32x4 *>(vrow + x * 128 + 64) = __builtin_bit_cast(f32x4, u32x4_t{lp[0], lp[1], lp[2], lp[3]});
                     }
@@ -868,7 +866,7 @@ __device__ __forceinline__ void winox_tile(const ConvParams &p)
             } else
             [&]() __attribute__((always_inline)) {
             // finish
-            if (part >= C::NPART || (BSVD_WX_ABL & 4)) return;
+            if (part >= C::NPART) return;
             constexpr int JN = M / C::NPART;             // columns per finisher
             const int j0 = part * JN;
 #pragma unroll
@@ -938,13 +936,13 @@ __device__ __forceinline__ void winox_tile(const ConvParams &p)
                         *reinterpret_cast<f32x4 *>(dst + 4) = f32x4{v[4], v[5], v[6], v[7]};
                     } else
                     if (live) {
-                        constexpr bool bounded = (ACT == BSVD_ACT_RELU6 && EPI == BSVD_EPI_PLAIN) || !BSVD_EPI_CLAMP;
+                        constexpr bool bounded = (ACT == BSVD_ACT_RELU6 && EPI == BSVD_EPI_PLAIN);
                         f16x8 hi, lo;
 #pragma unroll
                         for (int k = 0; k < 8; ++k) {
                             const float vs = bounded ? v[k] : __builtin_amdgcn_fmed3f(v[k], -65504.f, 65504.f);
                             hi[k] = (_Float16)vs;
-                            lo[k] = lo_keep((_Float16)__builtin_fmaf((float)hi[k], -1.0f, vs));
+                            lo[k] = (_Float16)__builtin_fmaf((float)hi[k], -1.0f, vs);
                         }
                         *reinterpret_cast<f32x4 *>(dst) = __builtin_bit_cast(f32x4, hi);
                         *reinterpret_cast<f32x4 *>(dst + 8) = __builtin_bit_cast(f32x4, lo);
@@ -986,11 +984,7 @@ __global__ __launch_bounds__((XCfg<M, NH, NTW, MT, PERSIST>::NTHREADS), (XCfg<M,
     winox_tile<M, NH, NTW, MT, PERSIST, XF, XCfg<M, NH, NTW, MT, PERSIST>::TR, 0, YV>(p);
 }
 
-#ifndef BSVD_WX_TAIL
-#define BSVD_WX_TAIL 2     // 16-row tile grids whose last row band has <= 8 live rows: 0 nothing special, 1 that band runs the 8-row body, 2 (F(2,3); F(6,3)'s
-                           // transform buffers do not fit two more patch rows: 1) that band is walked by folded tiles, two of its tiles per workgroup
-#endif
-constexpr bool wx_tail_folds(int m) { return BSVD_WX_TAIL == 2 && m == 2; }
+constexpr bool wx_tail_folds(int m) { return m == 2; }
 
 // 16-row tile grid whose LAST row band has <= 8 live rows (Ho mod 16 in 1..8: the 135-row layers of a 540 x 960 frame, the 120-row ones of
 // 480 x 856): those workgroups run the 8-row body -- the same instruction sequence per output (bit-identical, like the 8-row tile of
@@ -1004,8 +998,7 @@ __global__ __launch_bounds__((XCfg<M, NH, NTW, 4, false>::NTHREADS), (XCfg<M, NH
     const WxGrid G = wx_grid(p.nty, p.ntx, p.nct, p.Ho, FOLDS);
     const int ntiles = p.frames * G.per_frame;
     const int bid = blockIdx.x, xcd = bid & 7;
-    const int q8 = ntiles >> 3, r8 = ntiles & 7;
-    int lid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+    int lid = wx_xcd_range(ntiles, xcd).first + (bid >> 3);
     if (p.flip) lid = ntiles - 1 - lid;
     if constexpr (FOLDS) {
         if (G.fold && lid % G.per_frame >= G.nreg) winox_tile<M, NH, NTW, 4, false, XF, 16, 2>(p);
@@ -1098,7 +1091,7 @@ static int launch_winox_cfg(const ConvParams &pin, hipStream_t stream, char *nam
     p.ntx = (p.Wo + C::TWPX - 1) / C::TWPX;
     p.nty = (p.Ho + C::TR - 1) / C::TR;
     p.nct = (p.Cout + C::BN - 1) / C::BN;
-    constexpr bool TAILK = BSVD_WX_TAIL && MT == 4 && !PERSIST && C::NTHREADS == 512 && (M == 2 || M == 6);
+    constexpr bool TAILK = MT == 4 && !PERSIST && C::NTHREADS == 512 && (M == 2 || M == 6);
     const int64_t nblk = (int64_t)p.frames * wx_grid(p.nty, p.ntx, p.nct, p.Ho, TAILK && wx_tail_folds(M) && XF != 2 && !YV).per_frame;
     if (nblk <= 0 || nblk > 0x7fffffff) { set_error("bsvd_conv3x3: grid of %lld workgroups", (long long)nblk); return -1; }
     // the product's 16-row tile launches are ALL this kernel (one symbol per form in a profile): a grid without such a band never takes
@@ -1117,33 +1110,95 @@ static int launch_winox_cfg(const ConvParams &pin, hipStream_t stream, char *nam
         hipLaunchKernelGGL((winox_kernel<M, NH, NTW, MT, PERSIST, XF, YV>), dim3(grid), dim3(C::NTHREADS), C::LDS_BYTES, stream, p);
     }
     const int rc = (int)hipGetLastError();
-    if constexpr (YV && !(BSVD_WX_ABL & 512)) { if (rc == 0) return launch_v_patch<M>(p, stream); }
+    if constexpr (YV) { if (rc == 0) return launch_v_patch<M>(p, stream); }
     return rc;
 }
 
-// Which wino_m codes this build runs.  Product: 2 / 6 (F(2,3) / F(6,3), each picking the half-height tile for grids that do not fill the
-// chip) and 42 / 46 (the same forms, never on the half-height tile: launches that share the chip with another graph branch).  A measurement
-// build (-DBSVD_MEASURE, tools/build_measure.sh -> build/measure/libbsvd_hip.so; never the product library) adds F(4,3), the 4-wave
-// workgroup, the forced tiles, the persistent form and the all-positions-per-wave kernel of conv3x3_wino.hip -- same arithmetic per form,
-// kept for the records in DESIGN.md 4.1d and for tests/measure_driver.py.
-static bool wino_code_known(int m)
+// The half-height choice of the codes that pick their tile (2, 6).  Small grids (single-frame launches of the stream schedules): one 8-wave
+// workgroup per CU, so the launch takes ceil(workgroups / 256) rounds -- 270 workgroups (256 -> 256 at 135 x 240) cost two full rounds for
+// 1.05 rounds of work.  The half-height tile has twice the workgroups and computes every output with the same instruction sequence
+// (bit-identical: stream == clip stays bitwise), at ~0.87 of the full tile's efficiency (10 patch rows per 8, prologue / epilogue per tile).
+// C4: the form's 16-row configuration.
+template <class C4>
+static bool wx_half_tile(const ConvParams &p)
 {
-    if (m == 2 || m == 6 || m == 42 || m == 46) return true;
+    auto fill = [](int64_t n) { return (double)n / (double)(((n + BSVD_CUS - 1) / BSVD_CUS) * BSVD_CUS); };
+    const int ntx4 = (p.Wo + C4::TWPX - 1) / C4::TWPX, nct4 = (p.Cout + C4::BN - 1) / C4::BN;
+    const int64_t per_row = (int64_t)p.frames * ntx4 * nct4;
+    // (the 16-row grid as it is launched: a short last row band of F(2,3) folds -- 256 -> 256 on ONE 135 x 240 frame is 240 + 16 = 256 workgroups, one round)
+    const int64_t n4 = (int64_t)p.frames * wx_grid((p.Ho + 15) / 16, ntx4, nct4, p.Ho, wx_tail_folds(C4::M) && !p.x_v).per_frame, n2 = per_row * ((p.Ho + 7) / 8);
+    return n4 < 8 * BSVD_CUS && 0.87 * fill(n2) > fill(n4);
+}
+
+template <int M, int NH, int NTW>
+static int wx_by_grid(const ConvParams &p, hipStream_t stream, char *name, int name_len)
+{
+    if (wx_half_tile<XCfg<M, NH, NTW, 4>>(p)) return launch_winox_cfg<M, NH, NTW, 2>(p, stream, name, name_len);
+    return launch_winox_cfg<M, NH, NTW>(p, stream, name, name_len);
+}
+
+template <int M, int NH, int NTW, int MT = 4>
+static int wx_fixed(const ConvParams &p, hipStream_t stream, char *name, int name_len)
+{
+    return launch_winox_cfg<M, NH, NTW, MT>(p, stream, name, name_len);
+}
+
 #ifdef BSVD_MEASURE
-    if (m == 4 || m == 12 || m == 22 || m == 32 || m == 36 || m == 52 || m == 62) return true;      // (14 = F(4,3) all positions per wave: fails parity, not offered)
+// the persistent form whatever the grid: small grids on 8 workgroups, so that every one walks several tiles
+static int wx_persistent(const ConvParams &p, hipStream_t stream, char *name, int name_len)
+{
+    using C4 = XCfg<2, 2, 2, 4>;
+    const int64_t n4 = (int64_t)p.frames * ((p.Wo + C4::TWPX - 1) / C4::TWPX) * ((p.Cout + C4::BN - 1) / C4::BN) * ((p.Ho + 15) / 16);
+    return launch_winox_cfg<2, 2, 2, 4, true>(p, stream, name, name_len, n4 < 2 * BSVD_CUS ? 8 : BSVD_CUS);
+}
 #endif
-    return false;
+
+// The wino_m codes of this build, stated once: wino_unsupported's known-check, its message and launch_winox's dispatch all walk this table.
+// Product: 2 / 6 (F(2,3) / F(6,3), each picking the half-height tile for grids that do not fill the chip) and 42 / 46 (the same forms, never
+// on the half-height tile: launches that share the chip with another graph branch -- the lagged two-chain stream step -- where idle CUs are
+// not idle).  A measurement build (-DBSVD_MEASURE, tools/build_measure.sh -> build/measure/libbsvd_hip.so; never the product library) adds
+// F(4,3), the 4-wave workgroup, the forced tiles, the persistent form and the all-positions-per-wave kernel of conv3x3_wino.hip -- same
+// arithmetic per form, kept for the records in DESIGN.md 4.1d and for tests/measure_driver.py.
+struct WinoCode { int code; int (*launch)(const ConvParams &, hipStream_t, char *, int); };
+static const WinoCode WINO_CODES[] = {
+    {2, wx_by_grid<2, 2, 2>},
+    {42, wx_fixed<2, 2, 2>},
+    {46, wx_fixed<6, 1, 2>},
+    {6, wx_by_grid<6, 1, 2>},
+#ifdef BSVD_MEASURE
+    {22, wx_fixed<2, 1, 2>},        // 4-wave workgroups, two per CU
+    {32, wx_fixed<2, 2, 2, 2>},     // the half-height tile whatever the grid
+    {52, wx_fixed<2, 2, 2>},        // one tile per workgroup whatever the grid (A/B of the persistent form)
+    {62, wx_persistent},
+    {4, wx_fixed<4, 2, 1>},
+    {36, wx_fixed<6, 1, 2, 2>},     // F(6,3) on the half-height tile whatever the grid
+    {12, launch_wino},              // all positions per wave, conv3x3_wino.hip (14, its F(4,3), never passed parity and is gone)
+#endif
+};
+
+static const WinoCode *wino_code(int m)
+{
+    for (const WinoCode &c : WINO_CODES) if (c.code == m) return &c;
+    return nullptr;
+}
+
+static const char *wino_codes_message()
+{
+    static char msg[320];
+    static const bool once = [] {
+        int n = snprintf(msg, sizeof msg, "wino_m must be one of this build's codes:");
+        for (const WinoCode &c : WINO_CODES) n += snprintf(msg + n, sizeof msg - n, " %d", c.code);
+        snprintf(msg + n, sizeof msg - n, " (2 / 6: F(2,3) / F(6,3); 42 / 46: the same forms, never on the half-height tile; every other code exists in measurement builds, -DBSVD_MEASURE, only)");
+        return true;
+    }();
+    (void)once;
+    return msg;
 }
 
 const char *wino_unsupported(const ConvParams &p, int stride)
 {
     if (p.prec != 1) return "dtype must be BSVD_F16X3";
-    if (!wino_code_known(p.wino_m))
-#ifdef BSVD_MEASURE
-        return "wino_m must be 2 or 6 (42 / 46: never the half-height tile; measurement build: 4, 12, 22, 32, 36, 52, 62)";
-#else
-        return "wino_m must be 2 or 6 (42 / 46: the same forms, never on the half-height tile); the other codes exist in measurement builds (-DBSVD_MEASURE) only";
-#endif
+    if (!wino_code(p.wino_m)) return wino_codes_message();
     if (stride != 1) return "stride must be 1";
     if (p.epilogue == BSVD_EPI_RESID || p.y_planar_ch > 0 || p.head_w) return "only PLAIN / PS_ADD NHWC layers";
     if ((p.fold & 15) != 0) return "fold must be a multiple of 16";
@@ -1160,51 +1215,9 @@ const char *wino_unsupported(const ConvParams &p, int stride)
 
 int launch_winox(const ConvParams &p, hipStream_t stream, char *name, int name_len)
 {
-    // F(2,3) / F(6,3).  Small grids (single-frame launches of the stream schedules): one 8-wave workgroup per CU, so the launch takes
-    // ceil(workgroups / 256) rounds -- 270 workgroups (256 -> 256 at 135 x 240) cost two full rounds for 1.05 rounds of work.
-    // The half-height tile has twice the workgroups and computes every output with the same instruction sequence (bit-identical:
-    // stream == clip stays bitwise), at ~0.87 of the full tile's efficiency (10 patch rows per 8, prologue / epilogue per tile).
-    // 42 / 46: never the half-height tile -- launches that share the chip with another graph branch (the lagged two-chain stream
-    // step): idle CUs are not idle there.
-    auto fill = [](int64_t n) { return (double)n / (double)(((n + BSVD_CUS - 1) / BSVD_CUS) * BSVD_CUS); };
-    switch (p.wino_m) {
-    case 2:
-    case 42: {
-        using C4 = XCfg<2, 2, 2, 4>;
-        const int ntx4 = (p.Wo + C4::TWPX - 1) / C4::TWPX, nct4 = (p.Cout + C4::BN - 1) / C4::BN;
-        const int64_t per_row = (int64_t)p.frames * ntx4 * nct4;
-        // (the 16-row grid as it is launched: a short last row band folds -- 256 -> 256 on ONE 135 x 240 frame is 240 + 16 = 256 workgroups, one round)
-        const int64_t n4 = (int64_t)p.frames * wx_grid((p.Ho + 15) / 16, ntx4, nct4, p.Ho, wx_tail_folds(2) && !p.x_v).per_frame, n2 = per_row * ((p.Ho + 7) / 8);
-        if (p.wino_m == 2 && n4 < 8 * BSVD_CUS && 0.87 * fill(n2) > fill(n4)) return launch_winox_cfg<2, 2, 2, 2>(p, stream, name, name_len);
-#ifdef BSVD_MEASURE
-        // (large grids as 256 persistent workgroups, the transform pipeline running across tile boundaries: built, bit-identical, 6-13 %
-        //  slower, DESIGN 4.1d -- only a measurement build with -DBSVD_WX_PERSIST_MIN=<tiles per CU> ever selects it)
-        if (n4 >= (int64_t)BSVD_WX_PERSIST_MIN * BSVD_CUS) return launch_winox_cfg<2, 2, 2, 4, true>(p, stream, name, name_len);
-#endif
-        return launch_winox_cfg<2, 2, 2>(p, stream, name, name_len);
-    }
-    case 46: return launch_winox_cfg<6, 1, 2>(p, stream, name, name_len);
-    case 6: {
-        using C4 = XCfg<6, 1, 2, 4>;
-        const int64_t per_row = (int64_t)p.frames * ((p.Wo + C4::TWPX - 1) / C4::TWPX) * ((p.Cout + C4::BN - 1) / C4::BN);
-        const int64_t n4 = per_row * ((p.Ho + 15) / 16), n2 = per_row * ((p.Ho + 7) / 8);
-        if (n4 < 8 * BSVD_CUS && 0.87 * fill(n2) > fill(n4)) return launch_winox_cfg<6, 1, 2, 2>(p, stream, name, name_len);
-        return launch_winox_cfg<6, 1, 2>(p, stream, name, name_len);
-    }
-#ifdef BSVD_MEASURE
-    case 22: return launch_winox_cfg<2, 1, 2>(p, stream, name, name_len);     // 4-wave workgroups, two per CU
-    case 32: return launch_winox_cfg<2, 2, 2, 2>(p, stream, name, name_len);  // the half-height tile whatever the grid
-    case 52: return launch_winox_cfg<2, 2, 2>(p, stream, name, name_len);     // one tile per workgroup whatever the grid (A/B of the persistent form)
-    case 62: {               // the persistent form whatever the grid: small grids on 8 workgroups, so that every one walks several tiles
-        using C4 = XCfg<2, 2, 2, 4>;
-        const int64_t n4 = (int64_t)p.frames * ((p.Wo + C4::TWPX - 1) / C4::TWPX) * ((p.Cout + C4::BN - 1) / C4::BN) * ((p.Ho + 15) / 16);
-        return launch_winox_cfg<2, 2, 2, 4, true>(p, stream, name, name_len, n4 < 2 * BSVD_CUS ? 8 : BSVD_CUS);
-    }
-    case 4: return launch_winox_cfg<4, 2, 1>(p, stream, name, name_len);
-    case 36: return launch_winox_cfg<6, 1, 2, 2>(p, stream, name, name_len);   // F(6,3) on the half-height tile whatever the grid
-#endif
-    default: set_error("bsvd_conv3x3: wino_m %d is not in this build", p.wino_m); return -19;
-    }
+    if (const WinoCode *c = wino_code(p.wino_m)) return c->launch(p, stream, name, name_len);
+    set_error("bsvd_conv3x3: wino_m %d is not in this build", p.wino_m);
+    return -19;
 }
 
 }  // namespace bsvd

@@ -83,6 +83,32 @@ def test_variant_dry_run_reports_dispatch():
     assert variant(dtype=_lib.BSVD_F16X3, stride=2, Cin=64, fold=16)[0] == -17 and b"plain convs" in lib.bsvd_last_error()
     # transformed-domain tensors are options of the Winograd form
     assert variant(dtype=_lib.BSVD_F16X3, x_v=6)[0] == -22 and variant(dtype=_lib.BSVD_F16X3, y_v=6)[0] == -22
+    # the Winograd launcher's dispatch (expected names: the library as it was before the launcher became one table of codes)
+    def wino(m, **kw):
+        kw = dict(dict(dtype=_lib.BSVD_F16X3, w_wino_packed=256, wino_m=m, H=135, W=240, Cin=256, Cout=256), **kw)
+        return variant(**kw)
+
+    vfe = lib.bsvd_v_frame_elems(135, 240, 256, 6)
+    assert wino(2) == (0, "winox_kernel<F(2,3),2x2>[f16x3]")                    # 10 frames: the 16-row tile
+    assert wino(6) == (0, "winox_kernel<F(6,3),1x2>[f16x3]")
+    assert wino(2, frames=1) == (0, "winox_kernel<F(2,3),2x2>[f16x3]")          # one frame: the folded 16-row grid is one round (240 + 16 workgroups)
+    assert wino(6, frames=1) == (0, "winox_kernel<F(6,3),1x2>[f16x3]")          # 180 workgroups of 16 rows beat 340 of 8
+    assert wino(6, frames=2) == (0, "winox_kernel<F(6,3),1x2>[f16x3][8 rows]")
+    assert wino(2, frames=1, Cin=128, Cout=128) == (0, "winox_kernel<F(2,3),2x2>[f16x3][8 rows]")
+    assert wino(6, frames=1, Cin=128, Cout=128) == (0, "winox_kernel<F(6,3),1x2>[f16x3][8 rows]")
+    assert wino(42, frames=1, Cin=128, Cout=128) == (0, "winox_kernel<F(2,3),2x2>[f16x3]")      # 42 / 46: never the half-height tile
+    assert wino(46, frames=1, Cin=128, Cout=128) == (0, "winox_kernel<F(6,3),1x2>[f16x3]")
+    assert wino(42, frames=1) == (0, "winox_kernel<F(2,3),2x2>[f16x3]") and wino(46, frames=1) == (0, "winox_kernel<F(6,3),1x2>[f16x3]")
+    assert wino(2, x_f32=1) == (0, "winox_kernel<F(2,3),2x2>[f16x3][f32 in]")
+    assert wino(6, x_f32=1) == (0, "winox_kernel<F(6,3),1x2>[f16x3][f32 in]")
+    assert wino(6, x_v=6, x_frame_stride=vfe) == (0, "winox_kernel<F(6,3),1x2>[f16x3][V in]")
+    assert wino(2, x_v=2, frames=1) == (0, "winox_kernel<F(2,3),2x2>[f16x3][8 rows][V in]")      # a transformed-domain input never folds
+    assert wino(6, y_v=6, y_frame_stride=vfe) == (0, "winox_kernel<F(6,3),1x2>[f16x3][V out]")
+    assert wino(2, y_v=2, y_frame_stride=lib.bsvd_v_frame_elems(135, 240, 256, 2))[0] == -19 and b"F(6,3) only" in lib.bsvd_last_error()
+    # the measurement codes are refused by the product library, and the message says where they live
+    for m in (4, 12, 22, 32, 36, 52, 62):
+        assert wino(m)[0] == -19 and b"measurement" in lib.bsvd_last_error(), m
+    assert wino(3)[0] == -19 and wino(14)[0] == -19
     assert lib.bsvd_v_groups(240, 6) == 40 and lib.bsvd_v_groups(214, 6) == 40 and lib.bsvd_v_groups(50, 2) == 32 and lib.bsvd_v_groups(240, 5) == -1
     assert lib.bsvd_v_frame_elems(135, 240, 256, 6) == 135 * 5 * 16 * (8 * 32 + 8) * 4 + 135 * 5 * 4 * 256 and lib.bsvd_v_frame_elems(8, 8, 24, 6) == -1
     # a frame of 2 GiB or more cannot be addressed by the split kernel: the error says so (not "fold")

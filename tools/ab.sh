@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B of compile-time tuning variants ON THE GPU BOX, interleaved in one session (box-to-box variance is large).
-# usage: tools/ab.sh "<flags A>" "<flags B>" ...   e.g.  tools/ab.sh "" "-DBSVD_WX_TAIL=1" "-DBSVD_WX_TAIL=0"
+# usage: tools/ab.sh "<flags A>" "<flags B>" ...   e.g.  tools/ab.sh "" "-DBSVD_WX_MIXASM=0"
 cd $GRAFT_REPO_ROOT
 i=0
 for f in "$@"; do

@@ -1,6 +1,7 @@
 """One conv layer, realistic operands (seeded weights, ReLU6-ranged split16 input produced by a real layer), launched back to back for a few
-seconds (sustained: the power cap applies): ms per launch.  For attributing costs with timing-only ablation builds (BSVD_HIP_LIB=...,
-e.g. -DBSVD_WX_ABL=...): the layer's INPUT stays realistic whatever the ablated kernel writes.
+seconds (sustained: the power cap applies): ms per launch.  For attributing costs with timing-only ablation builds (BSVD_HIP_LIB=...):
+the layer's INPUT stays realistic whatever the ablated kernel writes.  (The Winograd kernel's ablation builds were removed with the commit
+that reworded this line; git has them.)
 usage: BSVD_HIP_LIB=... python tools/debug/layer_loop.py [Cin=128] [Cout=128] [H=270] [W=480] [frames=10] [seconds=3] [stride=1] [tsm=0]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))

@@ -1,5 +1,5 @@
-"""Shader clock and package power (rocm-smi) while ONE wide layer loops back to back: what does a kernel variant (BSVD_HIP_LIB=..., e.g. the
-timing-only ablation builds) run at?   usage: python tools/debug/layer_power.py [form=wino2] [Cin=256] [H=135] [W=240] [frames=10] [seconds=6]"""
+"""Shader clock and package power (rocm-smi) while ONE wide layer loops back to back: what does a kernel variant (BSVD_HIP_LIB=..., e.g. a
+measurement build; the Winograd kernel's timing-only ablation builds were removed with the commit that reworded this line, git has them) run at?   usage: python tools/debug/layer_power.py [form=wino2] [Cin=256] [H=135] [W=240] [frames=10] [seconds=6]"""
 import os, re, subprocess, sys, threading, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import numpy as np

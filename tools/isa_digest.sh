@@ -4,6 +4,8 @@
 #        from its label to its .Lfunc_end) and a last line with the sha256 of the whole normalised assembly file
 # Normalised: comment lines, .file / .ident / .loc / .section / .Ltmp* / .Lfunc* lines, trailing ";" comments and the lines naming
 # __hip_cuid_<hash> (a hash of the source text) are dropped.  Same flags and sources as tools/kernel_resources.sh.
+# ISA_DIGEST_MASK_ORDINAL=1: a body's local labels (.LBB<n>_<block>) lose <n>, the kernel's position in its file -- for a change that only
+# reorders the kernels of a translation unit (the whole-file digest still sees the order).
 ROOT="$(cd "$(dirname "$0")/.." && pwd)"
 OUT=$(mktemp -d)
 SRCS="conv3x3_mfma conv3x3_winox conv3x3_edge_f32 bsvd_abi"
@@ -19,7 +21,7 @@ rc=0
 for src in $SRCS; do
   [ -s $OUT/$src.s ] || { echo "isa_digest: $src.hip did not compile" >&2; cat $OUT/$src.log >&2; rc=1; continue; }
   python3 - $src $OUT/$src.s ${ISA_DIGEST_KEEP:+$ISA_DIGEST_KEEP/$src.norm.s} <<'EOF' || rc=1
-import hashlib, re, subprocess, sys
+import hashlib, os, re, subprocess, sys
 src, path = sys.argv[1], sys.argv[2]
 raw = open(path).read().splitlines()
 kernels = set(re.findall(r'^\s*\.amdhsa_kernel\s+(\S+)', '\n'.join(raw), re.M))
@@ -34,7 +36,7 @@ for l in raw:
     l = re.sub(r'\s*;.*$', '', l.rstrip())
     if not l.strip(): continue
     norm.append(l)
-    if cur is not None: cur[1].append(l.replace(cur[0], '<kernel>'))      # (its own symbol -- label, .amdhsa_kernel -- is not part of a body's digest)
+    if cur is not None: cur[1].append((re.sub(r'\.LBB\d+_', '.LBB_', l) if os.environ.get('ISA_DIGEST_MASK_ORDINAL') else l).replace(cur[0], '<kernel>'))      # (its own symbol -- label, .amdhsa_kernel -- is not part of a body's digest)
 sha = lambda ls: hashlib.sha256(('\n'.join(ls) + '\n').encode()).hexdigest()
 names = subprocess.run(['c++filt'] + [n for n, _ in bodies], capture_output=True, text=True).stdout.splitlines() if bodies else []
 print('== %s: %d kernels' % (src, len(bodies)))
