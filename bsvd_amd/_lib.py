@@ -9,7 +9,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("BSVD_HIP_LIB") or os.path.join(_HERE, "libbsvd_hip.so")   # env override: A/B tuning builds
 
-ABI_VERSION = 11
+ABI_VERSION = 12
 BSVD_F32, BSVD_F16, BSVD_F16X3 = 0, 1, 2
 ACT = {"none": 0, "relu": 1, "relu6": 2}
 EPI_PLAIN, EPI_PS_ADD, EPI_RESID = 0, 1, 2
@@ -60,6 +60,7 @@ class BsvdConvArgs(ctypes.Structure):
         ("pre_cin", ctypes.c_int32), ("pre_act", ctypes.c_int32),
         ("x_f32", ctypes.c_int32), ("y_f32", ctypes.c_int32),
         ("x_v", ctypes.c_int32), ("y_v", ctypes.c_int32),
+        ("out_scale", ctypes.c_float), ("head_out_scale", ctypes.c_float), ("pre_out_scale", ctypes.c_float),
     ]
 
 

@@ -64,6 +64,13 @@ WIDE_CONV_DEFAULT = "wino2"
 # default; fuse_pairs=True takes it.
 FUSE_PAIRS_DEFAULT = False
 F16X3_WEIGHT_LIMIT = 6.0e4      # |folded weight| beyond this cannot be carried as an fp16 pair (fp16 max 65504)
+# Per-layer power-of-two weight scale of the split mode (engine.weight_scale_exponent; BsvdConvArgs.out_scale):
+# weight_scale='auto' packs 2^e w per layer, e chosen so that max |2^e w| sits in [0.5, 1), and undoes the scale on the fp32 accumulator --
+# exact, and the REMEDY for both ends of fp16's range: layers of small weights keep the pairs' 22 bits (no small-weight notice), weights
+# beyond 6e4 neither fall back to fp32 nor leave the Winograd form.  'off' (the default for now: the packs, and with them every bit of every
+# existing result, stay what they were) packs w itself.  Exact-fp32 mode: accepted, does nothing.
+WEIGHT_SCALE = ("off", "auto")
+WEIGHT_SCALE_DEFAULT = "off"
 
 
 class _Slots(nn.Module):
@@ -122,9 +129,11 @@ def _denblock_params(chns, in_ch, out_ch, interm_ch, blind, norm="none"):
 class _HipNet(nn.Module):
     """Shared engine plumbing of the registered arch classes: NetSpec, precision, weight (re)packing, executor."""
 
-    def _init_engine(self, net, precision, clamp, norm='none', wide_conv='auto', fuse_pairs='auto', f32_handover='auto', v_handover='auto'):
+    def _init_engine(self, net, precision, clamp, norm='none', wide_conv='auto', fuse_pairs='auto', f32_handover='auto', v_handover='auto',
+                     weight_scale=WEIGHT_SCALE_DEFAULT):
         if precision not in ("auto", "fp32", "f16x3"):
             raise ValueError("precision must be 'auto', 'fp32' or 'f16x3'")
+        self.weight_scale = weight_scale       # (property: validates, see below)
         if wide_conv == "auto":
             wide_conv = WIDE_CONV_DEFAULT
         from .engine import WIDE_CONV, MEASURE_WIDE_CONV
@@ -178,6 +187,17 @@ class _HipNet(nn.Module):
         self.__dict__["_precision_eff"] = precision
         self._precision_init = precision       # what the request resolved to; a weight-range fallback of 'auto' to fp32 lasts one pack only
 
+    # ``weight_scale`` likewise: the keyword and a later ``model.weight_scale = 'auto'`` are validated alike; the next forward re-packs
+    @property
+    def weight_scale(self):
+        return self.__dict__.get("_weight_scale", WEIGHT_SCALE_DEFAULT)
+
+    @weight_scale.setter
+    def weight_scale(self, weight_scale):
+        if not isinstance(weight_scale, str) or weight_scale not in WEIGHT_SCALE:
+            raise ValueError("weight_scale must be one of %s" % (WEIGHT_SCALE,))
+        self.__dict__["_weight_scale"] = weight_scale
+
     @staticmethod
     def weight_init(m):
         if isinstance(m, nn.Conv2d):
@@ -223,9 +243,9 @@ class _HipNet(nn.Module):
         """what `print(model)` shows besides the parameter holders (profile.py:77 prints the model)"""
         n = self.net
         return ("MI355X engine: chns=%s mid_ch=%d in_ch=%d out_ch=%d act=%s interm_ch=%d blind=%s norm=%s precision=%s "
-                "(requested %s), %d fused conv layers / %d temporal-fusion, %.1f GMAC per 540x960 frame"
+                "(requested %s) weight_scale=%s, %d fused conv layers / %d temporal-fusion, %.1f GMAC per 540x960 frame"
                 % (list(n.chns), n.mid_ch, n.net_in_ch, n.out_ch, n.act, n.interm_ch, n.blind, self.norm, self.precision,
-                   self.precision_requested, len(n.layers), n.shift_num, n.macs_per_frame(540, 960) / 1e9))
+                   self.precision_requested, self.weight_scale, len(n.layers), n.shift_num, n.macs_per_frame(540, 960) / 1e9))
 
     def _tag_owned(self):
         """marks every module of this engine's tree for the registration hooks (see _bump_epoch)"""
@@ -250,7 +270,8 @@ class _HipNet(nn.Module):
                                "running statistics; call .eval() first (DenoisingModel.test and profile.py do: "
                                "denoising_model.py:180, profile.py:80).  Training is out of scope of this engine.")
         require_hip()
-        sig = (self._signature(), str(device), self._precision_init, self.wide_conv, self.fuse_pairs, self.f32_handover, self.v_handover)
+        sig = (self._signature(), str(device), self._precision_init, self.wide_conv, self.fuse_pairs, self.f32_handover, self.v_handover,
+               self.weight_scale)
         if self._packed is None or self._packed_sig != sig:
             # every re-pack starts from the precision the constructor resolved: 'auto' that fell back to exact fp32 because ONE
             # checkpoint's folded weights left fp16's range takes the split mode again when an in-range checkpoint is loaded
@@ -265,7 +286,12 @@ class _HipNet(nn.Module):
                 # cannot be carried as a hi+lo pair.  'auto' falls back to exact fp32, an explicit 'f16x3' refuses.
                 # (Activations beyond +-65504 saturate in the split store; unbounded-ReLU networks fed [0,1] images stay
                 # orders of magnitude below that)
-                wmax = max(float(state[l.key + ".weight"].abs().max()) for l in self.net.layers)
+                # (weight_scale='auto': of the weights that are packed, 2^e w -- below 1 for every finite layer)
+                from .engine import weight_scale_exponent
+                wmax = [float(state[l.key + ".weight"].abs().max()) for l in self.net.layers]
+                if self.weight_scale == "auto":
+                    wmax = [float(np.ldexp(v, weight_scale_exponent(v))) for v in wmax]
+                wmax = max(wmax)
                 if not wmax <= F16X3_WEIGHT_LIMIT:
                     if self.precision_requested == "auto":
                         warnings.warn("bsvd_amd: max |weight| after the BatchNorm fold is %.3g, outside fp16's range: "
@@ -275,7 +301,8 @@ class _HipNet(nn.Module):
                         raise ValueError("precision='f16x3': max |weight| after the BatchNorm fold is %.3g, outside fp16's "
                                          "range (use precision='fp32' or 'auto')" % wmax)
             self._packed = PackedNet(self.net, state, device, self.precision, self.wide_conv, fuse_pairs=self.fuse_pairs,
-                                     f32_handover=self.f32_handover, v_handover=self.v_handover)
+                                     f32_handover=self.f32_handover, v_handover=self.v_handover,
+                                     weight_scale=self.weight_scale == "auto")
             self._packed_sig = sig
             self._exec = HipExecutor(self._packed)
             self._exec_gen = getattr(self, "_exec_gen", 0) + 1
@@ -341,19 +368,24 @@ class BSVD(_HipNet):
                     when the network admits it, else 'fp32'; ``self.precision`` holds the choice).
       norm        : 'none' or 'bn' (the reference default; eval mode only: the BatchNorm layers hold their parameters
                     under the reference's names and are folded into the packed conv weights).
+      weight_scale : 'off' (default) or 'auto': in the split mode pack 2^e w per layer and undo the exact power-of-two scale on the
+                    fp32 accumulator -- the remedy for checkpoints whose layers sit far below the init scale (the small-weight
+                    notice) or beyond fp16's range after a BatchNorm fold (WEIGHT_SCALE above).
     """
 
     def __init__(self, chns=[32, 64, 128], mid_ch=3, shift_input=False, in_ch=4, out_ch=3, norm='bn', act='relu',
                  interm_ch=30, blind=False, pretrain_ckpt='./experiments/pretrained_ckpt/bsvd-64.pth',
                  engine_mode='auto', clamp=None, precision='auto', stream_overlap=True, stream_rings=True,
-                 stream_graphs=True, stream_chunk='auto', wide_conv='auto', fuse_pairs='auto', f32_handover='auto', v_handover='auto'):
+                 stream_graphs=True, stream_chunk='auto', wide_conv='auto', fuse_pairs='auto', f32_handover='auto', v_handover='auto',
+                 weight_scale=WEIGHT_SCALE_DEFAULT):
         super().__init__()
         if shift_input:
             raise NotImplementedError("shift_input=True (CvBlock input stage) is not used by any BSVD config; "
                                       "the reference itself is inconsistent there (SURVEY.md §8a-16)")
         if engine_mode not in ("auto", "clip", "stream"):
             raise ValueError("engine_mode must be 'auto', 'clip' or 'stream'")
-        self._init_engine(make_netspec(chns, mid_ch, in_ch, out_ch, act, interm_ch, blind), precision, clamp, norm, wide_conv, fuse_pairs, f32_handover, v_handover)
+        self._init_engine(make_netspec(chns, mid_ch, in_ch, out_ch, act, interm_ch, blind), precision, clamp, norm, wide_conv, fuse_pairs, f32_handover, v_handover,
+                          weight_scale)
         self.engine_mode = engine_mode
         self.last_mode = None          # schedule the last forward() actually ran ('clip' | 'stream')
         self.stream_overlap = bool(stream_overlap)   # streaming_forward: temp1(step k) and temp2(step k-1) as parallel graph branches
@@ -727,7 +759,7 @@ class TSN(_HipNet):
 
     def __init__(self, num_segments=11, base_model='WNet_multistage', shift_type='TSM', shift_div=8, inplace=False,
                  net2d_opt={}, enable_past_buffer=True, clamp=None, precision='auto', wide_conv='auto', fuse_pairs='auto',
-                 f32_handover='auto', v_handover='auto', **kwargs):
+                 f32_handover='auto', v_handover='auto', weight_scale=WEIGHT_SCALE_DEFAULT, **kwargs):
         super().__init__()
         if base_model != 'WNet_multistage':
             raise NotImplementedError("base_model %r" % (base_model,))
@@ -741,7 +773,8 @@ class TSN(_HipNet):
         self.num_segments = num_segments
         self.enable_past_buffer = enable_past_buffer
         self._init_engine(make_netspec(o['chns'], o['mid_ch'], o['in_ch'], o['out_ch'], o['act'], o['interm_ch'],
-                                       o['blind']), precision, clamp, o['norm'], wide_conv, fuse_pairs, f32_handover, v_handover)
+                                       o['blind']), precision, clamp, o['norm'], wide_conv, fuse_pairs, f32_handover, v_handover,
+                          weight_scale)
         n = self.net
         stages = []
         for args_ in ((o['in_ch'], o['mid_ch'], o['blind']), (o['mid_ch'], o['out_ch'], False)):

@@ -1,5 +1,6 @@
 // bsvd_abi.hip -- C-ABI entry points of libbsvd_hip.so (see include/bsvd_hip.h): argument validation,
 // dispatch, and the small bandwidth-bound helper kernels (weight pre-pack, NCHW<->NHWC, halo pack).
+#include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -366,6 +367,15 @@ const char *bsvd_last_error(void) { return g_err; }
 
 int64_t bsvd_packed_weight_elems(int32_t Cin_pad, int32_t Cout_pad) { return (int64_t)Cin_pad * 9 * Cout_pad; }
 
+// BsvdConvArgs.out_scale / head_out_scale / pre_out_scale: 0 = 1; else a finite, positive, normal, exact power of two
+static bool out_scale_ok(float v, float *resolved)
+{
+    *resolved = v == 0.0f ? 1.0f : v;
+    if (v == 0.0f) return true;
+    int e;
+    return isfinite(v) && v > 0.0f && isnormal(v) && frexpf(v, &e) == 0.5f;
+}
+
 static int conv3x3_impl(const BsvdConvArgs *a, void *stream, char *name, int name_len)
 {
     if (!a) { set_error("bsvd_conv3x3: args is NULL"); return -1; }
@@ -389,6 +399,25 @@ static int conv3x3_impl(const BsvdConvArgs *a, void *stream, char *name, int nam
         if (a->halo_next && a->halo_next_pstride <= 0) { set_error("bsvd_conv3x3: halo_next_pstride"); return -12; }
     }
     ConvParams p;
+    {   // per-layer power-of-two weight scale (ABI v12): checked here, in front of every launch path
+        const struct { const char *nm; float v; float *dst; const void *pack; } sc[3] = {
+            {"out_scale", a->out_scale, &p.out_scale, a->w_wino_packed ? a->w_wino_packed : a->w_packed},
+            {"head_out_scale", a->head_out_scale, &p.head_out_scale, a->head_w_packed},
+            {"pre_out_scale", a->pre_out_scale, &p.pre_out_scale, a->pre_w_packed}};
+        for (const auto &s : sc) {
+            if (!out_scale_ok(s.v, s.dst)) { set_error("bsvd_conv3x3: %s = %g must be 0 (= 1) or a finite, positive, normal power of two", s.nm, (double)s.v); return -23; }
+            if (*s.dst == 1.0f) continue;
+            if (a->dtype != BSVD_F16X3) { set_error("bsvd_conv3x3: %s = %g: the weight scale is an option of BSVD_F16X3", s.nm, (double)s.v); return -23; }
+            if (!s.pack) { set_error("bsvd_conv3x3: %s = %g without the pack it belongs to", s.nm, (double)s.v); return -23; }
+        }
+        if (p.out_scale != 1.0f && a->w_wino_packed && a->wino_m >= 10 && a->wino_m < 20) {
+            set_error("bsvd_conv3x3: out_scale is not available for wino_m %d (the all-positions-per-wave measurement kernel)", a->wino_m); return -23;
+        }
+        // the unfused planar entry runs head_kernel (conv3x3_edge_f32.hip) on an fp32 pack: it has no scale to undo
+        if (p.out_scale != 1.0f && a->x_planar_ch > 0 && !a->head_w_packed) {
+            set_error("bsvd_conv3x3: out_scale = %g is not available for the unfused planar entry (x_planar_ch without head_w_packed: an fp32 pack)", (double)p.out_scale); return -23;
+        }
+    }
     p.x = (const float *)a->x;
     p.halo_prev = a->fold > 0 ? (const float *)a->halo_prev : nullptr;
     p.halo_next = a->fold > 0 ? (const float *)a->halo_next : nullptr;

@@ -1,6 +1,7 @@
 // Internal declarations shared by the translation units of libbsvd_hip.so (not part of the ABI).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 #include <atomic>
 #include "bsvd_hip.h"
@@ -30,10 +31,14 @@ struct ConvParams {
     int32_t y_planar_ch;     // > 0: y is planar [frames][y_planar_ch][H][W] fp32 (split mode: written by the MFMA kernel)
     int32_t y_clamp;         // clamp the planar output to [y_lo, y_hi]
     float y_lo, y_hi;
+    // BsvdConvArgs.out_scale / head_out_scale / pre_out_scale with 0 resolved to 1 (split mode: every epilogue computes fmaf(acc, scale, bias)
+    // where it computed acc + bias): the factor on the accumulator of the main conv / the fused entry's / the fused pair's first conv
+    float out_scale;
     // fused network entry (BsvdConvArgs.head_w_packed): x is the planar fp32 input with head_cin channels
     const void *head_w;
     const float *head_bias;
     int32_t head_cin;
+    float head_out_scale;
     // fused 64-channel pair (BsvdConvArgs.pre_w_packed): x is the FIRST conv's NHWC input with pre_cin channels, pre_w its split pack
     // (pre_cin -> Cin channels), pre_bias [Cin] fp32, pre_act its activation; w / bias / act / epilogue describe the second conv
     const void *pre_w;
@@ -47,7 +52,19 @@ struct ConvParams {
     // Winograd form of the wide split-fp16 layers (BsvdConvArgs.w_wino_packed): w then points at the transformed pack
     int32_t fat_min_wgs;     // BsvdConvArgs.fat_min_wgs (0 = default): smallest grid that takes the 128-accumulator split tile
     int32_t wino_m;          // 0 = direct convolution; 2 | 4 | 6 = F(wino_m, 3) along x (conv3x3_winox.hip); 12 = the all-positions-per-wave kernel (conv3x3_wino.hip)
+    float pre_out_scale;
 };
+// out_scale / head_out_scale / pre_out_scale sit in what used to be padding (behind y_hi, behind head_cin, at the end): the struct keeps its
+// size and every other member its offset, so the kernarg loads of the kernels that do not read them -- the exact-fp32 ones, the edge kernels
+// with arguments behind the struct -- are where they were
+static_assert(sizeof(ConvParams) == 280, "ConvParams is the kernels' kernarg: a size change moves every kernel's loads");
+// ... and a reorder that keeps the size moves them just the same: the three factors and the first member behind each former hole stay put
+static_assert(offsetof(ConvParams, y_hi) == 192 && offsetof(ConvParams, out_scale) == 196 && offsetof(ConvParams, head_w) == 200,
+              "ConvParams: out_scale fills the 4 bytes between y_hi and head_w");
+static_assert(offsetof(ConvParams, head_cin) == 216 && offsetof(ConvParams, head_out_scale) == 220 && offsetof(ConvParams, pre_w) == 224,
+              "ConvParams: head_out_scale fills the 4 bytes between head_cin and pre_w");
+static_assert(offsetof(ConvParams, wino_m) == 272 && offsetof(ConvParams, pre_out_scale) == 276,
+              "ConvParams: pre_out_scale fills the tail padding behind wino_m");
 
 // Transformed-domain layout (include/bsvd_hip.h, BsvdConvArgs.x_v / y_v): a frame is [row][tile of 8 groups][16-channel chunk] BLOCKS of
 // v_block_floats(m): (m + 2) positions x 4 quarters x 8 groups x 16 B (the LDS planes of one patch row of one chunk, 4 KB for F(6,3)) + one

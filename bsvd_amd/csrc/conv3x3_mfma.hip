@@ -615,7 +615,7 @@ __global__ __launch_bounds__(256, (PREF ? 2 : occ_of<C, PREC>())) void conv3x3_k
                     f16x8 hi, lo;
 #pragma unroll
                     for (int j = 0; j < 8; ++j) {
-                        float v = hacc[8 * h + j] + bia[h][j >> 2][j & 3];
+                        float v = __builtin_fmaf(hacc[8 * h + j], p.head_out_scale, bia[h][j >> 2][j & 3]);
                         v = inside ? __builtin_amdgcn_fmed3f(v, vlo, vhi) : 0.f;
                         hi[j] = (_Float16)v;
                         lo[j] = (_Float16)(v - (float)hi[j]);
@@ -782,7 +782,7 @@ __global__ __launch_bounds__(256, (PREF ? 2 : occ_of<C, PREC>())) void conv3x3_k
                     f16x8 hi, lo;
 #pragma unroll
                     for (int k = 0; k < 8; ++k) {
-                        float v = pacc[PAIR][j][8 * h + k] + bia[h][k >> 2][k & 3];
+                        float v = __builtin_fmaf(pacc[PAIR][j][8 * h + k], p.pre_out_scale, bia[h][k >> 2][k & 3]);
                         v = px_in ? __builtin_amdgcn_fmed3f(v, vlo, vhi) : 0.f;
                         hi[k] = (_Float16)v;
                         lo[k] = (_Float16)__builtin_fmaf((float)hi[k], -1.0f, v);
@@ -1109,7 +1109,7 @@ __global__ __launch_bounds__(256, (PREF ? 2 : occ_of<C, PREC>())) void conv3x3_k
 #pragma unroll
                     for (int n = 0; n < 4; ++n) {
                         if (n >= p.y_planar_ch) break;
-                        float v = apply_act(acc[mt][0][n] + (p.bias ? p.bias[n] : 0.f), p.act);
+                        float v = apply_act(__builtin_fmaf(acc[mt][0][n], p.out_scale, p.bias ? p.bias[n] : 0.f), p.act);
                         if (p.epilogue == BSVD_EPI_RESID && n < p.resid_ch) {
                             float base;
                             if (split_base) {          // split16 NHWC base: channel n < 16 lives in chunk 0
@@ -1301,7 +1301,7 @@ __global__ __launch_bounds__(256, (PREF ? 2 : occ_of<C, PREC>())) void conv3x3_k
                 const f32x4 v1 = *reinterpret_cast<const f32x4 *>(sc + m * 36 + q * 8 + 4);
                 TLP_WAIT_MARK(1, v0, v1);
 #pragma unroll
-                for (int j = 0; j < 4; ++j) { v[j] = v0[j] + bq[nt][0][0][j]; v[4 + j] = v1[j] + bq[nt][0][1][j]; }
+                for (int j = 0; j < 4; ++j) { v[j] = __builtin_fmaf(v0[j], p.out_scale, bq[nt][0][0][j]); v[4 + j] = __builtin_fmaf(v1[j], p.out_scale, bq[nt][0][1][j]); }
             } else {
 #pragma unroll
                 for (int j = 0; j < 8; ++j) v[j] = acc[mt][nt][8 * sidx + j] + bq[nt][sidx][j >> 2][j & 3];

@@ -806,7 +806,7 @@ __device__ __forceinline__ void winox_tile(const ConvParams &p)
                     F::output(mm, oo);
 #pragma unroll
                     for (int j = 0; j < M; ++j) {
-                        float v = oo[j] + (k < 4 ? bq0[k] : bq1[k - 4]);
+                        float v = __builtin_fmaf(oo[j], p.out_scale, k < 4 ? bq0[k] : bq1[k - 4]);
                         if constexpr (ACT == BSVD_ACT_RELU6) v = __builtin_amdgcn_fmed3f(v, 0.f, 6.f);
                         else if constexpr (ACT == BSVD_ACT_RELU) v = fmaxf(v, 0.f);
                         d[1 + j][k] = oxg + j < p.Wo ? v : 0.f;
@@ -904,7 +904,7 @@ __device__ __forceinline__ void winox_tile(const ConvParams &p)
                         float s = 0.f;
 #pragma unroll
                         for (int pp = 0; pp < C::NPART; ++pp) s = (part == pp) ? ov[pp * JN + jj][k] : s;
-                        v[k] = s + (k < 4 ? bq0[k] : bq1[k - 4]);
+                        v[k] = __builtin_fmaf(s, p.out_scale, k < 4 ? bq0[k] : bq1[k - 4]);
                         if constexpr (ACT == BSVD_ACT_RELU6) v[k] = __builtin_amdgcn_fmed3f(v[k], 0.f, 6.f);
                         else if constexpr (ACT == BSVD_ACT_RELU) v[k] = fmaxf(v[k], 0.f);
                     }

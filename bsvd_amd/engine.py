@@ -5,6 +5,7 @@ tensor hand-over at the nn.Module boundary.  All arithmetic happens in the hand-
 There is deliberately no CPU path: without a HIP device / the built library this module raises.
 """
 import ctypes
+import math
 import os
 
 import torch
@@ -67,6 +68,18 @@ F16_PAIR_LIMIT = 6.0e4          # the same limit arch.BSVD applies to the raw we
 # max |w| = 2^-10 (std ~2e-4: > 1e-4 relative per layer) a rescaled network left the 1e-3 budget on the MI355X
 # (profiles/f16x3_value_probes.txt): PackedNet names such layers once per pack.
 F16X3_SMALL_WEIGHT = 2.0 ** -10
+
+
+def weight_scale_exponent(wmax):
+    """The per-layer power-of-two weight scale (BsvdConvArgs.out_scale, ABI v12): the integer e with 2^e * wmax in
+    [0.5, 1) -- the binade right below 1, where every weight's pair has hi normal and lo at most three octaves into fp16's subnormals, and
+    where G g of F(6,3) (x 15) is nowhere near fp16's range.  e = 0 for wmax == 0 (and for a non-finite wmax: the range guards refuse
+    those).  Clamped to [-126, 126] so that both 2^e and the epilogue's 2^-e are normal fp32 numbers.  Negative e -- weights beyond 1,
+    a BatchNorm-folded checkpoint beyond 65504 included -- is the top-end fix."""
+    wmax = abs(float(wmax))
+    if wmax == 0.0 or not math.isfinite(wmax):
+        return 0
+    return max(-126, min(126, -math.frexp(wmax)[1]))
 
 
 def wide_conv_known(name, lib=None):
@@ -177,7 +190,7 @@ class PackedNet:
     cf. BSVD.load, bsvd_arch.py:462-474): {spec.key: (w_packed, bias_packed)}."""
 
     def __init__(self, net, state, device, precision="fp32", wide_conv="direct", wino_min_cin=None, fuse_pairs=False, f32_handover=None,
-                 v_handover=None):
+                 v_handover=None, weight_scale=False):
         lib = require_hip()
         if not wide_conv_known(wide_conv, lib):
             if wide_conv in MEASURE_WIDE_CONV:
@@ -195,6 +208,12 @@ class PackedNet:
         self.wino_layer_abi = {}     # {spec.key: BsvdConvArgs.wino_m} -- "wino26": F(2,3) for the 128 -> 128 layers, F(6,3) for the wider ones
         self.wino_range_fallback = []    # eligible layers kept on the direct form because max |G g| would leave fp16's range
         self.small_weight_layers = []    # split-packed layers whose max |w| is below F16X3_SMALL_WEIGHT: (key, max |w|)
+        # per-layer power-of-two weight scale (weight_scale_exponent): every split pack holds 2^e w and its launch undoes the scale on the
+        # fp32 accumulator (BsvdConvArgs.out_scale = 2^-e).  {spec.key: e} of the ordinary packs, {second conv's key: e} of the fused
+        # entry's first-conv packs; both EMPTY without the option: the packs and launches are then what they always were.  A property of the
+        # layer alone, so every schedule stays bit-identical to the others.
+        self.weight_scale = bool(weight_scale) and precision == "f16x3"
+        self.scale_exp, self.head_scale_exp = {}, {}
         self.tensors = {}
         self.order = {sp.key: i for i, sp in enumerate(net.layers)}      # position in the layer-major walk (tile_order parity)
         edge = set()
@@ -212,6 +231,10 @@ class PackedNet:
                 mx = torch.stack([state[sp.key + ".weight"].detach().to(device=device, dtype=torch.float32).abs().max()
                                   if state[sp.key + ".weight"].numel() else torch.zeros((), device=device) for sp in cand]).cpu()
                 self._wmax = {sp.key: float(v) for sp, v in zip(cand, mx)}
+            if self.weight_scale:
+                # the range checks below (Winograd fp16 range, small-weight notice) look at the weights that are PACKED: 2^e w
+                self.scale_exp = {sp.key: weight_scale_exponent(self._wmax[sp.key]) for sp in net.layers if sp.key not in edge}
+                self._wmax = {k: (math.ldexp(v, self.scale_exp[k]) if k in self.scale_exp else v) for k, v in self._wmax.items()}
             for sp in net.layers:
                 w = state[sp.key + ".weight"].detach().to(device=device, dtype=torch.float32).contiguous()
                 b = state.get(sp.key + ".bias")
@@ -220,6 +243,8 @@ class PackedNet:
                 if tuple(w.shape) != (sp.cout, sp.cin, 3, 3):
                     raise ValueError("%s.weight has shape %s, expected %s" % (sp.key, tuple(w.shape), (sp.cout, sp.cin, 3, 3)))
                 bp = torch.empty(sp.cout_pad, dtype=torch.float32, device=device)
+                if self.scale_exp.get(sp.key):
+                    w = torch.ldexp(w, torch.tensor(self.scale_exp[sp.key], device=device))      # exact; the bias stays unscaled
                 form = self._layer_form(sp, w)
                 if form is not None:
                     m, abi = form
@@ -258,6 +283,10 @@ class PackedNet:
                 w = state[sp0.key + ".weight"].detach().to(device=device, dtype=torch.float32).contiguous()
                 b = state.get(sp0.key + ".bias")
                 b = None if b is None else b.detach().to(device=device, dtype=torch.float32).contiguous()
+                if self.weight_scale:
+                    e = weight_scale_exponent(float(w.abs().max()) if w.numel() else 0.0)
+                    self.head_scale_exp[sp3.key] = e
+                    w = torch.ldexp(w, torch.tensor(e, device=device))
                 hw = torch.empty(lib.bsvd_packed_head_weight_bytes(sp0.cout_pad) // 4, dtype=torch.float32, device=device)
                 hb = torch.empty(sp0.cout_pad, dtype=torch.float32, device=device)
                 rc = lib.bsvd_pack_head_weights(w.data_ptr(), b.data_ptr() if b is not None else None, sp0.cin, sp0.cout,
@@ -624,4 +653,12 @@ class HipExecutor:
         # consecutive layers walk their tiles in opposite directions: each starts where its producer finished (Infinity Cache)
         a.tile_order = self.packed.order.get(sp.key, 0) & 1
         a.fat_min_wgs = self.fat_min_wgs
+        # per-layer weight scale: the packs hold 2^e w, the epilogues multiply the accumulator by 2^-e (0.0 = 1: packs without the option)
+        se = getattr(self.packed, "scale_exp", {})
+        if se:
+            a.out_scale = math.ldexp(1.0, -se.get(sp.key, 0))
+            if head is not None:
+                a.head_out_scale = math.ldexp(1.0, -self.packed.head_scale_exp[sp.key])
+            if pre is not None:
+                a.pre_out_scale = math.ldexp(1.0, -se.get(pre.key, 0))
         return a, y

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define BSVD_ABI_VERSION 11
+#define BSVD_ABI_VERSION 12
 
 /* dtype.  BSVD_F32: exact fp32 (v_mfma_f32_32x32x2_f32).  BSVD_F16X3 ("split16"): every fp32 value v is carried as
  * an fp16 pair hi = fp16(v), lo = fp16(v - hi); a 16-channel chunk of a pixel is stored as [hi x16 | lo x16] in the
@@ -41,7 +41,7 @@ extern "C" {
 // "fp32-class" holds for weights around init scale.  lo is an fp16 SUBNORMAL for |v| < 2^-3 (kept by conversions and MFMAs, asserted in
 // tests/test_gpu_range.py), so a pair resolves 2^-24 absolute whatever its size and a layer's relative error is about 2.6e-8 / std(w):
 // 6e-7 at std 0.03, 1e-5 at 2^-4 of that, 1e-4 at 2^-8, plain-fp16 class (2e-3) at 2^-12; a stored output resolves 2^-25 absolute.
-// DESIGN.md 4.1b has the table measured on the MI355X.
+// DESIGN.md 4.1b has the table measured on the MI355X.  The remedy is the per-layer power-of-two weight scale, BsvdConvArgs.out_scale (ABI v12).
 enum { BSVD_F32 = 0, BSVD_F16 = 1, BSVD_F16X3 = 2 };
 enum { BSVD_ACT_NONE = 0, BSVD_ACT_RELU = 1, BSVD_ACT_RELU6 = 2 }; /* get_act_function, bsvd_arch.py:185-192 */
 enum {
@@ -191,6 +191,22 @@ typedef struct BsvdConvArgs {
      * y_v: PLAIN layers of the Winograd kernel whose own form has the same m (the epilogue's pixel groups are the reader's groups);
      * y_frame_stride likewise.  Not with x_f32 / y_f32 on the same tensor.  Anything else returns -22. */
     int32_t x_v, y_v;
+    /* Per-layer power-of-two weight scale (ABI v12, BSVD_F16X3 only).  A weight pair resolves 2^-24 ABSOLUTE (lo is an
+     * fp16 subnormal for |w| < 2^-3), so a layer of small weights loses relative precision, and one of weights beyond 65504 cannot be
+     * packed at all.  The remedy is the caller's: pack 2^e w -- with the unchanged bsvd_pack_weights / bsvd_pack_weights_wino /
+     * bsvd_pack_head_weights; a power-of-two multiple of w is exact in fp32 and G (2^e g) = 2^e G g -- with e chosen so that the layer's
+     * weights sit where a pair has its 22 bits, pass the bias UNSCALED and out_scale = 2^-e.  Every split-mode epilogue computes
+     *     fmaf(acc, out_scale, bias)
+     * in place of acc + bias: one rounding of the exact (acc 2^-e) + bias (barring underflow of acc 2^-e), bit-identical to acc + bias for
+     * out_scale = 1, the same instruction count.  One kernel-uniform factor per conv, never per channel:
+     *   out_scale       the main conv (w_packed / w_wino_packed);
+     *   head_out_scale  the fused entry's first conv (head_w_packed);
+     *   pre_out_scale   the fused pair's first conv (pre_w_packed).
+     * 0.0f means 1.0 (zeroed structs of older callers).  Any other value must be a finite, positive, normal, exact power of two; a value
+     * != 1 additionally needs dtype BSVD_F16X3, head_ / pre_out_scale their pack, and a wino_m code other than the all-positions-per-wave
+     * measurement kernel's (12); out_scale != 1 is refused for the UNFUSED planar entry (x_planar_ch without head_w_packed), whose pack
+     * is plain fp32.  Anything else returns -23 with the reason. */
+    float out_scale, head_out_scale, pre_out_scale;
 } BsvdConvArgs;
 
 int bsvd_abi_version(void);
