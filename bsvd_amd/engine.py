@@ -7,11 +7,12 @@ There is deliberately no CPU path: without a HIP device / the built library this
 import ctypes
 import math
 import os
+import warnings
 
 import torch
 
 from . import _lib
-from .netspec import EPI_PLAIN, EPI_PS_ADD, EPI_RESID  # noqa: F401
+from .netspec import EPI_PLAIN, EPI_PS_ADD, EPI_RESID, out_hwc  # noqa: F401
 from .schedule import Halo  # noqa: F401
 
 
@@ -126,6 +127,11 @@ class VT:
             raise ValueError("bsvd_v_frame_elems(%d, %d, %d, %d)" % (H, W, C, m))
         return int(n)
 
+    @staticmethod
+    def block_units(m):
+        """16-byte units of one block (include/bsvd_hip.h): (m + 2) x 4 x 8 of V + the edge line, per (row, tile of 8 groups, 16-channel chunk)"""
+        return (m + 2) * 32 + 8
+
     @classmethod
     def empty(cls, T, H, W, C, m, device):
         return cls(torch.empty((T, cls.frame_elems(H, W, C, m)), dtype=torch.float32, device=device), H, W, C, m)
@@ -164,10 +170,9 @@ class VT:
     is_cuda = property(lambda self: self.t.is_cuda)
 
     def blocks(self):
-        """[.., H, tiles, C / 16, block floats] view of the frame's blocks (include/bsvd_hip.h: (m + 2) x 4 x 8 units of 16 B + the edge
-        line per (row, tile of 8 groups, 16-channel chunk)), without the producer's edge record behind them"""
+        """[.., H, tiles, C / 16, block floats] view of the frame's blocks (block_units), without the producer's edge record behind them"""
         ntx = _lib.load().bsvd_v_groups(self.W, self.m) // 8
-        blk = ((self.m + 2) * 32 + 8) * 4
+        blk = self.block_units(self.m) * 4
         n = self.H * ntx * (self.C // 16) * blk
         v = self.t[..., :n]
         return v.reshape(*v.shape[:-1], self.H, ntx, self.C // 16, blk)
@@ -216,123 +221,147 @@ class PackedNet:
         self.scale_exp, self.head_scale_exp = {}, {}
         self.tensors = {}
         self.order = {sp.key: i for i, sp in enumerate(net.layers)}      # position in the layer-major walk (tile_order parity)
-        edge = set()
-        if precision == "f16x3":
-            # the entry layer (planar 3/4-channel input) runs on the fp32 VALU kernel and keeps an fp32 pack; every other
-            # layer, the planar-output exit layer included, is split-packed for the MFMA kernel
-            edge = {net.layers[0].key}
+        # the entry layer (planar 3/4-channel input) runs on the fp32 VALU kernel and keeps an fp32 pack; every other
+        # layer, the planar-output exit layer included, is split-packed for the MFMA kernel
+        edge = {net.layers[0].key} if precision == "f16x3" else set()
         with torch.cuda.device(device):
-            # max |w| of every layer the Winograd form could take, in ONE host round trip (a float() per layer is a device sync per layer)
-            # (in the split mode: of every split-packed layer, for the small-weight notice below)
-            cand = [sp for sp in net.layers if (self.wino_m and wino_eligible(sp, precision, self.wino_min_cin)) or
-                    (precision == "f16x3" and sp.key not in edge)]
-            self._wmax = {}
-            if cand:
-                mx = torch.stack([state[sp.key + ".weight"].detach().to(device=device, dtype=torch.float32).abs().max()
-                                  if state[sp.key + ".weight"].numel() else torch.zeros((), device=device) for sp in cand]).cpu()
-                self._wmax = {sp.key: float(v) for sp, v in zip(cand, mx)}
-            if self.weight_scale:
-                # the range checks below (Winograd fp16 range, small-weight notice) look at the weights that are PACKED: 2^e w
-                self.scale_exp = {sp.key: weight_scale_exponent(self._wmax[sp.key]) for sp in net.layers if sp.key not in edge}
-                self._wmax = {k: (math.ldexp(v, self.scale_exp[k]) if k in self.scale_exp else v) for k, v in self._wmax.items()}
-            for sp in net.layers:
-                w = state[sp.key + ".weight"].detach().to(device=device, dtype=torch.float32).contiguous()
-                b = state.get(sp.key + ".bias")
-                if b is not None:
-                    b = b.detach().to(device=device, dtype=torch.float32).contiguous()
-                if tuple(w.shape) != (sp.cout, sp.cin, 3, 3):
-                    raise ValueError("%s.weight has shape %s, expected %s" % (sp.key, tuple(w.shape), (sp.cout, sp.cin, 3, 3)))
-                bp = torch.empty(sp.cout_pad, dtype=torch.float32, device=device)
-                if self.scale_exp.get(sp.key):
-                    w = torch.ldexp(w, torch.tensor(self.scale_exp[sp.key], device=device))      # exact; the bias stays unscaled
-                form = self._layer_form(sp, w)
-                if form is not None:
-                    m, abi = form
-                    n = lib.bsvd_packed_wino_weight_elems(sp.cin_pad, sp.cout_pad, m)
-                    wq = torch.empty(n, dtype=torch.float32, device=device)
-                    rc = lib.bsvd_pack_weights_wino(w.data_ptr(), b.data_ptr() if b is not None else None, sp.cin, sp.cout,
-                                                    sp.cin_pad, sp.cout_pad, 1 if sp.epilogue == EPI_PS_ADD else 0, m,
-                                                    wq.data_ptr(), bp.data_ptr(), _stream_ptr())
-                    _lib.check(rc, "bsvd_pack_weights_wino(%s)" % sp.key)
-                    self.wino[sp.key] = wq
-                    self.wino_layer_abi[sp.key] = abi
-                    self.tensors[sp.key] = (None, bp)
-                    continue
-                n = lib.bsvd_packed_weight_elems(sp.cin_pad, sp.cout_pad)
-                wp = torch.empty(n, dtype=torch.float32, device=device)
-                dt = _lib.BSVD_F16X3 if (precision == "f16x3" and sp.key not in edge) else _lib.BSVD_F32
-                rc = lib.bsvd_pack_weights(w.data_ptr(), b.data_ptr() if b is not None else None, sp.cin, sp.cout,
-                                           sp.cin_pad, sp.cout_pad, 1 if sp.epilogue == EPI_PS_ADD else 0, dt,
-                                           wp.data_ptr(), bp.data_ptr(), _stream_ptr())
-                _lib.check(rc, "bsvd_pack_weights(%s)" % sp.key)
-                self.tensors[sp.key] = (wp, bp)
-            if precision == "f16x3":
-                self.small_weight_layers = [(sp.key, self._wmax[sp.key]) for sp in net.layers
-                                            if sp.key in self._wmax and 0.0 < self._wmax[sp.key] < F16X3_SMALL_WEIGHT]
-                if self.small_weight_layers:
-                    import warnings
-                    warnings.warn("bsvd_amd: max |weight| below %.3g (2^-10) in %s: an fp16 pair resolves 2^-24 absolute, so these layers "
-                                  "run the split mode at more than 1e-4 relative error (fp16-class from 2^-14 down); "
-                                  "precision='fp32' is exact" % (F16X3_SMALL_WEIGHT, ", ".join("%s (%.3g)" % kv for kv in self.small_weight_layers)))
-            # fused network entry: the first conv's weights as the MFMA operand of the second conv's kernel, keyed by the
-            # second conv (only DenBlock 1 has a planar entry layer)
-            self.head = {}
-            blk = getattr(net, "temp1", None)
-            if blk is not None and "inc0" in blk and "inc3" in blk and head_fusable(blk["inc0"], blk["inc3"], precision):
-                sp0, sp3 = blk["inc0"], blk["inc3"]
-                w = state[sp0.key + ".weight"].detach().to(device=device, dtype=torch.float32).contiguous()
-                b = state.get(sp0.key + ".bias")
-                b = None if b is None else b.detach().to(device=device, dtype=torch.float32).contiguous()
-                if self.weight_scale:
-                    e = weight_scale_exponent(float(w.abs().max()) if w.numel() else 0.0)
-                    self.head_scale_exp[sp3.key] = e
-                    w = torch.ldexp(w, torch.tensor(e, device=device))
-                hw = torch.empty(lib.bsvd_packed_head_weight_bytes(sp0.cout_pad) // 4, dtype=torch.float32, device=device)
-                hb = torch.empty(sp0.cout_pad, dtype=torch.float32, device=device)
-                rc = lib.bsvd_pack_head_weights(w.data_ptr(), b.data_ptr() if b is not None else None, sp0.cin, sp0.cout,
-                                                sp0.cout_pad, hw.data_ptr(), hb.data_ptr(), _stream_ptr())
-                _lib.check(rc, "bsvd_pack_head_weights(%s)" % sp0.key)
-                self.head[sp3.key] = (hw, hb, sp0)
-            # plain-fp32 hand-over: producer -> consumer pairs whose consumer runs a product Winograd form and whose producer can store fp32
-            # (a Winograd-form layer, or a PLAIN direct-form split layer: the stride-2 convs).  Decided from the layer forms alone.
-            # ... and the transformed-domain hand-over (BsvdConvArgs.y_v / x_v) where producer and consumer both run F(6,3) and the producer is a
-            # PLAIN layer: {producer key: m}, {consumer key: m}.  It takes precedence over the fp32 hand-over for those pairs.
-            self.f32_out, self.f32_in = set(), set()
-            self.v_out, self.v_in = {}, {}
-            f32 = (F32_HANDOVER_DEFAULT if f32_handover is None else f32_handover) and precision == "f16x3"
-            vh = (V_HANDOVER_DEFAULT if v_handover is None else v_handover) and precision == "f16x3"
-            for blk in (getattr(net, "temp1", None), getattr(net, "temp2", None)):
-                if blk is None:
-                    continue
-                for pn, cn in _SOLE_CONSUMER.items():
-                    if pn in blk and cn in blk:
-                        pr, co = blk[pn], blk[cn]
-                        if pr.out_channels_pad != co.cin_pad:
-                            continue
-                        if vh and self.wino_layer_abi.get(co.key) == V_FORM and self.wino_layer_abi.get(pr.key) == V_FORM and \
-                                pr.epilogue == EPI_PLAIN and pr.stride == 1:
-                            self.v_out[pr.key] = V_FORM
-                            self.v_in[co.key] = V_FORM
-                        elif f32 and self.wino_layer_abi.get(co.key) in (2, 6) and \
-                                (pr.key in self.wino or (pr.epilogue == EPI_PLAIN and pr.key not in edge)):
-                            self.f32_out.add(pr.key)
-                            self.f32_in.add(co.key)
-            # fused 64-channel pairs (BsvdConvArgs.pre_w_packed), keyed by the SECOND conv: both layers keep their ordinary packs (the
-            # first conv's is handed over as pre_w_packed / pre_bias), so a fused and an unfused launch read the same weights
-            self.pairs = {}
-            if fuse_pairs:
-                for blk in (getattr(net, "temp1", None), getattr(net, "temp2", None)):
-                    if blk is None:
-                        continue
-                    for na, nb in (("inc0", "inc3"), ("out0", "out3")):
-                        if na in blk and nb in blk and blk[nb].key not in self.head and pair_fusable(blk[na], blk[nb], precision) \
-                                and self.tensors[blk[na].key][0] is not None and self.tensors[blk[nb].key][0] is not None:
-                            self.pairs[blk[nb].key] = blk[na]
+            self._measure_wmax(net, state, edge)
+            self._pack_layers(lib, net, state, edge)
+            self._warn_small_weights(net)
+            self._pack_head(lib, net, state)
+            self._decide_handover(net, edge, f32_handover, v_handover)
+            self._decide_pairs(net, fuse_pairs)
             # The packed tensors are read from whatever stream a later forward runs on (ClipPipeline's compute stream,
             # the A/B streams of streaming_forward, a graph replay): finish the one-time pack here so no consumer can see
             # half-packed weights.  (The w/b temporaries are consumed by kernels queued on this stream.)
             torch.cuda.current_stream(device).synchronize()
 
+    def _fetch(self, state, key):
+        """``state[key]`` as a contiguous fp32 tensor on the device"""
+        return state[key].detach().to(device=self.device, dtype=torch.float32).contiguous()
+
+    def _fetch_wb(self, state, sp):
+        """(weight, bias or None) of layer ``sp`` on the device"""
+        kb = sp.key + ".bias"
+        return self._fetch(state, sp.key + ".weight"), (self._fetch(state, kb) if state.get(kb) is not None else None)
+
+    def _measure_wmax(self, net, state, edge):
+        """max |w| of every layer the Winograd form could take and, in the split mode, of every split-packed layer (the small-weight
+        notice), in ONE host round trip (a float() per layer is a device sync per layer); then the weight-scale exponents from them."""
+        cand = [sp for sp in net.layers if (self.wino_m and wino_eligible(sp, self.precision, self.wino_min_cin)) or
+                (self.precision == "f16x3" and sp.key not in edge)]
+        self._wmax = {}
+        if cand:
+            mx = torch.stack([self._fetch(state, sp.key + ".weight").abs().max() if state[sp.key + ".weight"].numel()
+                              else torch.zeros((), device=self.device) for sp in cand]).cpu()
+            self._wmax = {sp.key: float(v) for sp, v in zip(cand, mx)}
+        if self.weight_scale:
+            # the range checks (Winograd fp16 range, small-weight notice) look at the weights that are PACKED: 2^e w
+            self.scale_exp = {sp.key: weight_scale_exponent(self._wmax[sp.key]) for sp in net.layers if sp.key not in edge}
+            self._wmax = {k: (math.ldexp(v, self.scale_exp[k]) if k in self.scale_exp else v) for k, v in self._wmax.items()}
+
+    def _pack_layers(self, lib, net, state, edge):
+        """Every layer's pack: the transformed one of its Winograd form (_layer_form), else the direct form's -- split, or fp32 for ``edge``."""
+        device = self.device
+        for sp in net.layers:
+            w, b = self._fetch_wb(state, sp)
+            if tuple(w.shape) != (sp.cout, sp.cin, 3, 3):
+                raise ValueError("%s.weight has shape %s, expected %s" % (sp.key, tuple(w.shape), (sp.cout, sp.cin, 3, 3)))
+            bp = torch.empty(sp.cout_pad, dtype=torch.float32, device=device)
+            if self.scale_exp.get(sp.key):
+                w = torch.ldexp(w, torch.tensor(self.scale_exp[sp.key], device=device))      # exact; the bias stays unscaled
+            form = self._layer_form(sp, w)
+            if form is not None:
+                m, abi = form
+                n = lib.bsvd_packed_wino_weight_elems(sp.cin_pad, sp.cout_pad, m)
+                wq = torch.empty(n, dtype=torch.float32, device=device)
+                rc = lib.bsvd_pack_weights_wino(w.data_ptr(), b.data_ptr() if b is not None else None, sp.cin, sp.cout,
+                                                sp.cin_pad, sp.cout_pad, 1 if sp.epilogue == EPI_PS_ADD else 0, m,
+                                                wq.data_ptr(), bp.data_ptr(), _stream_ptr())
+                _lib.check(rc, "bsvd_pack_weights_wino(%s)" % sp.key)
+                self.wino[sp.key] = wq
+                self.wino_layer_abi[sp.key] = abi
+                self.tensors[sp.key] = (None, bp)
+                continue
+            n = lib.bsvd_packed_weight_elems(sp.cin_pad, sp.cout_pad)
+            wp = torch.empty(n, dtype=torch.float32, device=device)
+            dt = _lib.BSVD_F16X3 if (self.precision == "f16x3" and sp.key not in edge) else _lib.BSVD_F32
+            rc = lib.bsvd_pack_weights(w.data_ptr(), b.data_ptr() if b is not None else None, sp.cin, sp.cout,
+                                       sp.cin_pad, sp.cout_pad, 1 if sp.epilogue == EPI_PS_ADD else 0, dt,
+                                       wp.data_ptr(), bp.data_ptr(), _stream_ptr())
+            _lib.check(rc, "bsvd_pack_weights(%s)" % sp.key)
+            self.tensors[sp.key] = (wp, bp)
+
+    def _warn_small_weights(self, net):
+        """Names, once per pack, the split-packed layers whose max |w| is below F16X3_SMALL_WEIGHT."""
+        if self.precision != "f16x3":
+            return
+        self.small_weight_layers = [(sp.key, self._wmax[sp.key]) for sp in net.layers
+                                    if sp.key in self._wmax and 0.0 < self._wmax[sp.key] < F16X3_SMALL_WEIGHT]
+        if self.small_weight_layers:
+            warnings.warn("bsvd_amd: max |weight| below %.3g (2^-10) in %s: an fp16 pair resolves 2^-24 absolute, so these layers "
+                          "run the split mode at more than 1e-4 relative error (fp16-class from 2^-14 down); "
+                          "precision='fp32' is exact" % (F16X3_SMALL_WEIGHT, ", ".join("%s (%.3g)" % kv for kv in self.small_weight_layers)))
+
+    def _pack_head(self, lib, net, state):
+        """Fused network entry: the first conv's weights as the MFMA operand of the second conv's kernel, keyed by the second conv
+        (only DenBlock 1 has a planar entry layer)."""
+        self.head = {}
+        blk = getattr(net, "temp1", None)
+        if blk is None or "inc0" not in blk or "inc3" not in blk or not head_fusable(blk["inc0"], blk["inc3"], self.precision):
+            return
+        sp0, sp3 = blk["inc0"], blk["inc3"]
+        w, b = self._fetch_wb(state, sp0)
+        if self.weight_scale:
+            e = weight_scale_exponent(float(w.abs().max()) if w.numel() else 0.0)
+            self.head_scale_exp[sp3.key] = e
+            w = torch.ldexp(w, torch.tensor(e, device=self.device))
+        hw = torch.empty(lib.bsvd_packed_head_weight_bytes(sp0.cout_pad) // 4, dtype=torch.float32, device=self.device)
+        hb = torch.empty(sp0.cout_pad, dtype=torch.float32, device=self.device)
+        rc = lib.bsvd_pack_head_weights(w.data_ptr(), b.data_ptr() if b is not None else None, sp0.cin, sp0.cout,
+                                        sp0.cout_pad, hw.data_ptr(), hb.data_ptr(), _stream_ptr())
+        _lib.check(rc, "bsvd_pack_head_weights(%s)" % sp0.key)
+        self.head[sp3.key] = (hw, hb, sp0)
+
+    def _decide_handover(self, net, edge, f32_handover, v_handover):
+        """Plain-fp32 hand-over: producer -> consumer pairs whose consumer runs a product Winograd form and whose producer can store fp32
+        (a Winograd-form layer, or a PLAIN direct-form split layer: the stride-2 convs).  Transformed-domain hand-over (BsvdConvArgs.y_v /
+        x_v) where producer and consumer both run F(6,3) and the producer is a PLAIN layer: {producer key: m}, {consumer key: m}; it takes
+        precedence over the fp32 hand-over for those pairs.  Both decided from the layer forms alone."""
+        self.f32_out, self.f32_in = set(), set()
+        self.v_out, self.v_in = {}, {}
+        f32 = (F32_HANDOVER_DEFAULT if f32_handover is None else f32_handover) and self.precision == "f16x3"
+        vh = (V_HANDOVER_DEFAULT if v_handover is None else v_handover) and self.precision == "f16x3"
+        for blk in (getattr(net, "temp1", None), getattr(net, "temp2", None)):
+            if blk is None:
+                continue
+            for pn, cn in _SOLE_CONSUMER.items():
+                if pn in blk and cn in blk:
+                    pr, co = blk[pn], blk[cn]
+                    if pr.out_channels_pad != co.cin_pad:
+                        continue
+                    if vh and self.wino_layer_abi.get(co.key) == V_FORM and self.wino_layer_abi.get(pr.key) == V_FORM and \
+                            pr.epilogue == EPI_PLAIN and pr.stride == 1:
+                        self.v_out[pr.key] = V_FORM
+                        self.v_in[co.key] = V_FORM
+                    elif f32 and self.wino_layer_abi.get(co.key) in (2, 6) and \
+                            (pr.key in self.wino or (pr.epilogue == EPI_PLAIN and pr.key not in edge)):
+                        self.f32_out.add(pr.key)
+                        self.f32_in.add(co.key)
+
+    def _decide_pairs(self, net, fuse_pairs):
+        """Fused 64-channel pairs (BsvdConvArgs.pre_w_packed), keyed by the SECOND conv: both layers keep their ordinary packs (the
+        first conv's is handed over as pre_w_packed / pre_bias), so a fused and an unfused launch read the same weights."""
+        self.pairs = {}
+        if not fuse_pairs:
+            return
+        for blk in (getattr(net, "temp1", None), getattr(net, "temp2", None)):
+            if blk is None:
+                continue
+            for na, nb in (("inc0", "inc3"), ("out0", "out3")):
+                if na in blk and nb in blk and blk[nb].key not in self.head and pair_fusable(blk[na], blk[nb], self.precision) \
+                        and self.tensors[blk[na].key][0] is not None and self.tensors[blk[nb].key][0] is not None:
+                    self.pairs[blk[nb].key] = blk[na]
 
     def _layer_form(self, sp, w):
         """(F(m,3), wino_m code) of a layer that runs on the Winograd kernel, else None.  A property of the LAYER and its weights only
@@ -348,7 +377,6 @@ class PackedNet:
         wmax = self._wmax[sp.key] if sp.key in self._wmax else (float(w.abs().max()) if w.numel() else 0.0)
         if not wmax * WINO_G_ROW_SUM[m] <= F16_PAIR_LIMIT:
             self.wino_range_fallback.append((sp.key, wmax, m))
-            import warnings
             warnings.warn("bsvd_amd: %s: max |weight| %.3g x %.3g (F(%d,3) weight transform) leaves fp16's range; this layer runs "
                           "the direct form" % (sp.key, wmax, WINO_G_ROW_SUM[m], m))
             return None
@@ -442,16 +470,13 @@ class HipExecutor:
     def out_shape(self, sp, x):
         """(Logical) shape of the NHWC tensor layer ``sp`` produces from NHWC input ``x``."""
         T, H, W, _ = x.shape
-        Ho, Wo = (H - 1) // sp.stride + 1, (W - 1) // sp.stride + 1
-        if sp.epilogue == EPI_PS_ADD:
-            return (T, 2 * Ho, 2 * Wo, sp.cout_pad // 4)
-        return (T, Ho, Wo, sp.cout_pad)
+        return (T,) + out_hwc(sp, H, W)
 
     def out_v(self, sp):
         """m if layer ``sp`` writes its output in the transformed domain (PackedNet.v_out), else 0"""
         if self.force_y_v is not None:
             return self.force_y_v
-        return getattr(self.packed, "v_out", {}).get(sp.key, 0)
+        return self.packed.v_out.get(sp.key, 0)
 
     def empty_out(self, sp, x, frames=None):
         """Uninitialised output tensor of layer ``sp`` for input ``x`` -- a torch tensor, or a VT where the layer writes the transformed domain"""
@@ -478,47 +503,41 @@ class HipExecutor:
         write the planar [T,channels,H,W] result directly (last layer).  out: optional preallocated (contiguous,
         e.g. a frame range of a larger tensor) destination instead of a fresh allocation."""
         a, y = self.build_args(sp, x, halo_prev, halo_next, extra, extra_pstride, extra_cstride, x_planar, y_planar, out)
+        self._issue(a, sp.key, sp.key)
+        return y
+
+    def _issue(self, a, label, variant_key):
+        """One launch of filled args: the library's name of the kernel first when record_variants asks (a dry run), then the launch,
+        its check and the counter.  conv / conv_pair_fused / conv_head_fused each end here and never in one another: a profiler
+        that wraps the three on the instance (bench.py) sees every launch exactly once."""
         if self.record_variants:
             buf = ctypes.create_string_buffer(96)
-            _lib.check(self.lib.bsvd_conv3x3_variant(ctypes.byref(a), buf, 96), "bsvd_conv3x3_variant(%s)" % sp.key)
+            _lib.check(self.lib.bsvd_conv3x3_variant(ctypes.byref(a), buf, 96), "bsvd_conv3x3_variant(%s)" % variant_key)
             self.last_variant = buf.value.decode()
         rc = self.lib.bsvd_conv3x3(ctypes.byref(a), _stream_ptr())
-        _lib.check(rc, "bsvd_conv3x3(%s)" % sp.key)
+        _lib.check(rc, "bsvd_conv3x3(%s)" % label)
         self.launches += 1
-        return y
 
     def fuse_head(self, S):
         """True if block ``S``'s entry pair inc0 -> inc3 runs as one launch (see head_fusable)"""
-        return "inc3" in S and S["inc3"].key in getattr(self.packed, "head", {})
+        return "inc3" in S and S["inc3"].key in self.packed.head
 
     def fuse_pair(self, S, na, nb):
         """True if block ``S``'s layers na -> nb run as one launch (see pair_fusable; PackedNet(fuse_pairs=True))"""
-        return nb in S and getattr(self.packed, "pairs", {}).get(S[nb].key) is S.get(na)
+        return nb in S and self.packed.pairs.get(S[nb].key) is S.get(na)
 
     def conv_pair_fused(self, spa, spb, x, extra=None, extra_pstride=0, extra_cstride=1, y_planar=None, out=None):
         """Two plain convs in one launch: x NHWC split16 -> epilogue(act(conv(act(conv(x, spa)), spb))); the tensor between them
         never exists in HBM."""
         a, y = self.build_args(spb, x, None, None, extra, extra_pstride, extra_cstride, False, y_planar, out, pre=spa)
-        if self.record_variants:
-            buf = ctypes.create_string_buffer(96)
-            _lib.check(self.lib.bsvd_conv3x3_variant(ctypes.byref(a), buf, 96), "bsvd_conv3x3_variant(%s)" % spb.key)
-            self.last_variant = buf.value.decode()
-        rc = self.lib.bsvd_conv3x3(ctypes.byref(a), _stream_ptr())
-        _lib.check(rc, "bsvd_conv3x3(%s + %s)" % (spa.key, spb.key))
-        self.launches += 1
+        self._issue(a, "%s + %s" % (spa.key, spb.key), spb.key)
         return y
 
     def conv_head_fused(self, sp0, sp3, x, out=None):
         """InputCvBlock in one launch: x planar [T,C,H,W] -> act(conv(act(conv(x, sp0)), sp3)) as NHWC split16; the
         intermediate tensor never exists in HBM."""
         a, y = self.build_args(sp3, x, x_planar=True, out=out, head=sp0)
-        if self.record_variants:
-            buf = ctypes.create_string_buffer(96)
-            _lib.check(self.lib.bsvd_conv3x3_variant(ctypes.byref(a), buf, 96), "bsvd_conv3x3_variant(%s)" % sp3.key)
-            self.last_variant = buf.value.decode()
-        rc = self.lib.bsvd_conv3x3(ctypes.byref(a), _stream_ptr())
-        _lib.check(rc, "bsvd_conv3x3(%s + %s)" % (sp0.key, sp3.key))
-        self.launches += 1
+        self._issue(a, "%s + %s" % (sp0.key, sp3.key), sp3.key)
         return y
 
     @staticmethod
@@ -539,6 +558,43 @@ class HipExecutor:
             if t is not None and (not t.is_cuda or t.dtype != torch.float32 or t.device != x.device):
                 raise ValueError("%s: %s must be a float32 tensor on %s (got %s on %s)"
                                  % (sp.key, name, x.device, t.dtype, t.device))
+        T, H, W = self._args_input(a, sp, x, x_planar, head, pre)
+        xv = self._check_domain(sp, x, halo_prev, halo_next)
+        yv = self.out_v(sp) if (y_planar is None and pre is None and head is None) else 0
+        y = self._args_output(a, sp, x.device, (T, H, W), y_planar, yv, out, alloc)
+        wp, bp = self.packed.tensors[sp.key]
+        a.x = x.data_ptr()
+        if sp.tsm:
+            a.fold = sp.fold
+            if halo_prev is not None:
+                a.halo_prev, a.halo_prev_pstride, a.halo_prev_coff = halo_prev.t.data_ptr(), halo_prev.pstride, halo_prev.coff
+            if halo_next is not None:
+                a.halo_next, a.halo_next_pstride, a.halo_next_coff = halo_next.t.data_ptr(), halo_next.pstride, halo_next.coff
+        a.bias_packed = bp.data_ptr()
+        yf = self.force_y_f32 if self.force_y_f32 is not None else sp.key in self.packed.f32_out
+        xf = self.force_x_f32 if self.force_x_f32 is not None else sp.key in self.packed.f32_in
+        if yf and not yv:
+            a.y_f32 = 1
+        if xf and wp is None and not xv:
+            a.x_f32 = 1
+        a.x_v, a.y_v = xv, yv
+        if wp is not None:
+            a.w_packed = wp.data_ptr()
+        else:
+            self._args_wino(a, sp, x, xv, H, W, halo_prev, halo_next, shared_chip)
+        self._args_residual(a, sp, extra, extra_pstride, extra_cstride, y_planar)
+        a.frames, a.H, a.W = T, H, W
+        a.Cin, a.Cout = sp.cin_pad, sp.cout_pad
+        a.stride = sp.stride
+        a.act, a.epilogue, a.dtype = _lib.ACT[sp.act], sp.epilogue, self.dtype
+        # consecutive layers walk their tiles in opposite directions: each starts where its producer finished (Infinity Cache)
+        a.tile_order = self.packed.order.get(sp.key, 0) & 1
+        a.fat_min_wgs = self.fat_min_wgs
+        self._args_scale(a, sp, head, pre)
+        return a, y
+
+    def _args_input(self, a, sp, x, x_planar, head, pre):
+        """The input mode -- fused entry, planar, fused pair or NHWC: checks x against it, fills the mode's fields; returns (T, H, W)."""
         if x_planar and head is not None:
             T, C, H, W = x.shape
             hw, hb, sp0 = self.packed.head[sp.key]
@@ -565,14 +621,22 @@ class HipExecutor:
             if cin_pad != sp.cin_pad:
                 raise ValueError("%s: input has %d channels, layer expects %d" % (sp.key, cin_pad, sp.cin_pad))
             a.x_frame_stride = x.frame_stride if isinstance(x, VT) else H * W * cin_pad
+        return T, H, W
+
+    def _check_domain(self, sp, x, halo_prev, halo_next):
+        """The input lives in the domain the pack expects (VT or pixels) and its halos in the same one; returns x's m (0: pixels)."""
         xv = x.m if isinstance(x, VT) else 0
-        if xv != getattr(self.packed, "v_in", {}).get(sp.key, 0) and self.force_y_v is None:
+        if xv != self.packed.v_in.get(sp.key, 0) and self.force_y_v is None:
             raise ValueError("%s: the pack expects a %s input, got a %s one" % (sp.key, "transformed-domain" if not xv else "pixel-domain",
                                                                                "transformed-domain" if xv else "pixel-domain"))
         for nm, h in (("halo_prev", halo_prev), ("halo_next", halo_next)):
             if h is not None and isinstance(h.t, VT) != bool(xv):
                 raise ValueError("%s: %s and the input must live in the same domain" % (sp.key, nm))
-        Ho, Wo = (H - 1) // sp.stride + 1, (W - 1) // sp.stride + 1
+        return xv
+
+    def _args_output(self, a, sp, device, thw, y_planar, yv, out, alloc):
+        """The output's shape (planar exit, PixelShuffle or plain NHWC; a VT where yv), its tensor -- ``out``, a fresh one, or None -- and fields."""
+        T, H, W = thw
         if y_planar is not None:
             yc, clamp = y_planar
             if sp.cout_pad != 16 or yc != sp.cout or sp.stride != 1 or sp.tsm or sp.epilogue == EPI_PS_ADD:
@@ -581,55 +645,42 @@ class HipExecutor:
             a.y_planar_ch = yc
             if clamp is not None:
                 a.y_clamp, a.y_lo, a.y_hi = 1, float(clamp[0]), float(clamp[1])
-        elif sp.epilogue == EPI_PS_ADD:
-            yshape = (T, 2 * Ho, 2 * Wo, sp.cout_pad // 4)
         else:
-            yshape = (T, Ho, Wo, sp.cout_pad)
-        yv = self.out_v(sp) if (y_planar is None and pre is None and head is None) else 0
+            yshape = (T,) + out_hwc(sp, H, W)
         if out is not None:
             if tuple(out.shape) != yshape or not out.is_contiguous() or out.dtype != torch.float32 or (out.m if isinstance(out, VT) else 0) != yv:
                 raise ValueError("%s: out has shape %s, expected contiguous %s%s" % (sp.key, tuple(out.shape), yshape, " in the transformed domain" if yv else ""))
             y = out
         elif alloc:
-            y = VT.empty(yshape[0], yshape[1], yshape[2], yshape[3], yv, x.device) if yv else torch.empty(yshape, dtype=torch.float32, device=x.device)
+            y = VT.empty(yshape[0], yshape[1], yshape[2], yshape[3], yv, device) if yv else torch.empty(yshape, dtype=torch.float32, device=device)
         else:
             y = None
             if yv:
                 raise ValueError("%s: a transformed-domain output needs its tensor" % sp.key)
-        wp, bp = self.packed.tensors[sp.key]
-        a.x = x.data_ptr()
-        if sp.tsm:
-            a.fold = sp.fold
-            if halo_prev is not None:
-                a.halo_prev, a.halo_prev_pstride, a.halo_prev_coff = halo_prev.t.data_ptr(), halo_prev.pstride, halo_prev.coff
-            if halo_next is not None:
-                a.halo_next, a.halo_next_pstride, a.halo_next_coff = halo_next.t.data_ptr(), halo_next.pstride, halo_next.coff
-        a.bias_packed = bp.data_ptr()
-        yf = self.force_y_f32 if self.force_y_f32 is not None else sp.key in getattr(self.packed, "f32_out", ())
-        xf = self.force_x_f32 if self.force_x_f32 is not None else sp.key in getattr(self.packed, "f32_in", ())
-        if yf and not yv:
-            a.y_f32 = 1
-        if xf and wp is None and not xv:
-            a.x_f32 = 1
-        a.x_v, a.y_v = xv, yv
-        if wp is not None:
-            a.w_packed = wp.data_ptr()
-        else:
-            # the Winograd kernel has no generic gather: validate what it needs HERE, before anything is issued or captured
-            # (the library would answer -19 in the middle of a forward)
-            for nm, h in (("halo_prev", halo_prev), ("halo_next", halo_next)):
-                if sp.tsm and h is not None:
-                    if h.t.data_ptr() % 16 or h.pstride % 4 or h.coff % 4:
-                        raise ValueError("%s: the Winograd form needs a 16-byte aligned %s (pointer %% 16, pstride %% 4, coff %% 4 elements); "
-                                         "got pstride %d, coff %d" % (sp.key, nm, h.pstride, h.coff))
-                    span = (H * (self.lib.bsvd_v_groups(W, xv) // 8) * (((xv + 2) * 32 + 8) // 16) if xv else H * W) * h.pstride * 4
-                    if span >= 2 ** 31 - 1:
-                        raise ValueError("%s: %s spans %d bytes >= 2 GiB (32-bit byte offsets inside one frame)" % (sp.key, nm, span))
-            if x.data_ptr() % 16:
-                raise ValueError("%s: the Winograd form needs a 16-byte aligned input" % sp.key)
-            a.w_wino_packed, a.wino_m = self.packed.wino[sp.key].data_ptr(), self.packed.wino_layer_abi[sp.key]
-            if shared_chip and a.wino_m in (2, 6):
-                a.wino_m += 40        # never the half-height tile
+        if y is not None:
+            a.y = y.data_ptr()
+        a.y_frame_stride = y.frame_stride if yv else yshape[1] * yshape[2] * yshape[3]
+        return y
+
+    def _args_wino(self, a, sp, x, xv, H, W, halo_prev, halo_next, shared_chip):
+        """A Winograd-form layer: the kernel has no generic gather, so what it needs is validated HERE, before anything is issued or captured
+        (the library would answer -19 in the middle of a forward); then its pack and form."""
+        for nm, h in (("halo_prev", halo_prev), ("halo_next", halo_next)):
+            if sp.tsm and h is not None:
+                if h.t.data_ptr() % 16 or h.pstride % 4 or h.coff % 4:
+                    raise ValueError("%s: the Winograd form needs a 16-byte aligned %s (pointer %% 16, pstride %% 4, coff %% 4 elements); "
+                                     "got pstride %d, coff %d" % (sp.key, nm, h.pstride, h.coff))
+                span = (H * (self.lib.bsvd_v_groups(W, xv) // 8) * (VT.block_units(xv) // 16) if xv else H * W) * h.pstride * 4
+                if span >= 2 ** 31 - 1:
+                    raise ValueError("%s: %s spans %d bytes >= 2 GiB (32-bit byte offsets inside one frame)" % (sp.key, nm, span))
+        if x.data_ptr() % 16:
+            raise ValueError("%s: the Winograd form needs a 16-byte aligned input" % sp.key)
+        a.w_wino_packed, a.wino_m = self.packed.wino[sp.key].data_ptr(), self.packed.wino_layer_abi[sp.key]
+        if shared_chip and a.wino_m in (2, 6):
+            a.wino_m += 40        # never the half-height tile
+
+    def _args_residual(self, a, sp, extra, extra_pstride, extra_cstride, y_planar):
+        """The epilogue's second operand (skip tensor of a PixelShuffle layer, base of the residual layer) and its strides."""
         if extra is not None:
             a.extra = extra.data_ptr()
             a.extra_frame_stride = extra[0].numel()
@@ -639,26 +690,13 @@ class HipExecutor:
         elif sp.epilogue == EPI_RESID:
             raise ValueError("%s: the residual layer needs its base tensor" % sp.key)
         a.resid_ch = min(3, sp.cout) if sp.epilogue == EPI_RESID else 0
-        if y is not None:
-            a.y = y.data_ptr()
-        a.y_frame_stride = 1
-        for d in yshape[1:]:
-            a.y_frame_stride *= d
-        if yv:
-            a.y_frame_stride = y.frame_stride
-        a.frames, a.H, a.W = T, H, W
-        a.Cin, a.Cout = sp.cin_pad, sp.cout_pad
-        a.stride = sp.stride
-        a.act, a.epilogue, a.dtype = _lib.ACT[sp.act], sp.epilogue, self.dtype
-        # consecutive layers walk their tiles in opposite directions: each starts where its producer finished (Infinity Cache)
-        a.tile_order = self.packed.order.get(sp.key, 0) & 1
-        a.fat_min_wgs = self.fat_min_wgs
-        # per-layer weight scale: the packs hold 2^e w, the epilogues multiply the accumulator by 2^-e (0.0 = 1: packs without the option)
-        se = getattr(self.packed, "scale_exp", {})
+
+    def _args_scale(self, a, sp, head, pre):
+        """Per-layer weight scale: the packs hold 2^e w, the epilogues multiply the accumulator by 2^-e (0.0 = 1: packs without the option)."""
+        se = self.packed.scale_exp
         if se:
             a.out_scale = math.ldexp(1.0, -se.get(sp.key, 0))
             if head is not None:
                 a.head_out_scale = math.ldexp(1.0, -self.packed.head_scale_exp[sp.key])
             if pre is not None:
                 a.pre_out_scale = math.ldexp(1.0, -se.get(pre.key, 0))
-        return a, y

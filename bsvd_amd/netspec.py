@@ -58,6 +58,15 @@ class ConvSpec:
         return self.cin * self.cout * 9 * ho * wo
 
 
+def out_hwc(sp, H, W):
+    """(Ho, Wo, C) of the NHWC tensor layer ``sp`` writes for an H x W input: the stride first, then PixelShuffle
+    (twice the height and width, a quarter of the padded channels)."""
+    Ho, Wo = (H - 1) // sp.stride + 1, (W - 1) // sp.stride + 1
+    if sp.epilogue == EPI_PS_ADD:
+        return 2 * Ho, 2 * Wo, sp.cout_pad // 4
+    return Ho, Wo, sp.cout_pad
+
+
 def norm_key_after(conv_key):
     """state_dict prefix of the normalisation layer that follows conv ``conv_key`` in the reference when norm != 'none'
     (InputCvBlock convblock.1/.4, DownBlock convblock.1, MemCvBlock b1/b2, OutputCvBlock convblock.1; the UpBlock conv

@@ -37,6 +37,7 @@ def planar_ok(ex, net):
 
 
 def _fused_head(ex, S):
+    """does block S's entry pair inc0 -> inc3 run as one launch (engine.head_fusable)?  A plain test executor need not know the question"""
     fn = getattr(ex, "fuse_head", None)
     return bool(fn and fn(S))
 

@@ -26,11 +26,12 @@ The host logic is executor-agnostic: with a plain executor (tests/oracle_exec.py
 layer, which is how the ring lifetimes are tested without a GPU.
 """
 import ctypes
-from collections import OrderedDict
+from collections import OrderedDict, namedtuple
 
 import torch
 
-from .schedule import _DenBlockStream
+from .netspec import out_hwc
+from .schedule import _DenBlockStream, _fused_head, _fused_pair
 
 RING_PERIOD = 10            # every ring depth divides it -> the steady-state signature has period 10
 _DEPTHS = (1, 2, 5, 10)
@@ -49,25 +50,33 @@ def ring_depth(name, is_handover=False, is_exit=False):
     return min(d for d in _DEPTHS if d >= need)
 
 
+def _ring_layout(net, H, W, chunk):
+    """(name, sp, slot shape, depth) of every layer's output ring, both DenBlocks in layer order: [chunk, Ho, Wo, C] NHWC, the exit layer
+    planar [chunk, out_ch, H, W] (what the caller gets a copy of)"""
+    for blk in (net.temp1, net.temp2):
+        h, w = H, W
+        for name, sp in blk.items():
+            h, w, c = out_hwc(sp, h, w)
+            exit_ = blk is net.temp2 and name == "out3"
+            yield name, sp, ((chunk, sp.cout, h, w) if exit_ else (chunk, h, w, c)), ring_depth(name, blk is net.temp1 and name == "out3", exit_)
+
+
 def ring_bytes_estimate(net, H, W, chunk=1, v_keys=()):
     """Device bytes StreamEngine(net, ..., H, W, chunk) allocates for its rings (fp32 words; split16 is the same size; the layers in
     ``v_keys`` write the transformed domain: (m + 2) / m = 4 / 3 of the pixels' bytes for F(6,3), group padding and the edge record on top)."""
     total = 10 * chunk * net.net_in_ch * H * W
-    for blk in (net.temp1, net.temp2):
-        h, w = H, W
-        for name, sp in blk.items():
-            ho, wo = (h - 1) // sp.stride + 1, (w - 1) // sp.stride + 1
-            if sp.epilogue == 1:
-                n, h, w = 4 * ho * wo * (sp.cout_pad // 4), 2 * ho, 2 * wo
-            else:
-                n, h, w = ho * wo * sp.cout_pad, ho, wo
-            exit_ = blk is net.temp2 and name == "out3"
-            if exit_:
-                n = sp.cout * ho * wo
-            if sp.key in v_keys:
-                n = int(n * 1.45)
-            total += n * chunk * ring_depth(name, blk is net.temp1 and name == "out3", exit_)
+    for name, sp, shape, depth in _ring_layout(net, H, W, chunk):
+        n = shape[1] * shape[2] * shape[3]
+        if sp.key in v_keys:
+            n = int(n * 1.45)
+        total += n * chunk * depth
     return 4 * total
+
+
+# One recorded launch: the arguments of HipExecutor.conv (``out`` = the ring slot it writes) plus the first conv of a fused launch:
+# ``head`` (conv_head_fused: the entry pair on planar input) or ``pre`` (conv_pair_fused); at most one of the two is set.
+Launch = namedtuple("Launch", ["sp", "x", "halo_prev", "halo_next", "extra", "extra_pstride", "extra_cstride", "x_planar", "y_planar",
+                               "out", "head", "pre"])
 
 
 class _Recorder:
@@ -83,46 +92,36 @@ class _Recorder:
         self.count.clear()
         self.rec = []
 
+    def _slot(self, key, T):
+        """the next slot of ring ``key``, cut to T frames (the last chunk of a clip may be shorter)"""
+        ring = self.eng.rings[key]
+        n = self.count.get(key, 0)
+        self.count[key] = n + 1
+        o = ring[n % len(ring)]
+        return o if T == o.shape[0] else o[:T]
+
     def conv(self, sp, x, halo_prev=None, halo_next=None, extra=None, extra_pstride=0, extra_cstride=1,
              x_planar=False, y_planar=None, out=None):
-        ring = self.eng.rings[sp.key]
-        n = self.count.get(sp.key, 0)
-        self.count[sp.key] = n + 1
-        o = ring[n % len(ring)]
-        T = x.shape[0]
-        if T != o.shape[0]:
-            o = o[:T]                 # the last chunk of a clip may be shorter
-        self.rec.append((sp, x, halo_prev, halo_next, extra, extra_pstride, extra_cstride, x_planar, y_planar, o, None, None))
+        o = self._slot(sp.key, x.shape[0])
+        self.rec.append(Launch(sp, x, halo_prev, halo_next, extra, extra_pstride, extra_cstride, x_planar, y_planar, o, None, None))
         return o
 
     def fuse_head(self, S):
-        fn = getattr(self.eng.ex, "fuse_head", None)
-        return bool(fn and fn(S))
+        return _fused_head(self.eng.ex, S)
 
     def fuse_pair(self, S, na, nb):
-        fn = getattr(self.eng.ex, "fuse_pair", None)
-        return bool(fn and fn(S, na, nb))
+        return _fused_pair(self.eng.ex, S, na, nb)
 
     def conv_pair_fused(self, spa, spb, x, extra=None, extra_pstride=0, extra_cstride=1, y_planar=None, out=None):
         """a fused pair of plain convs as ONE recorded launch writing spb's ring (spa's ring does not exist)"""
-        ring = self.eng.rings[spb.key]
-        n = self.count.get(spb.key, 0)
-        self.count[spb.key] = n + 1
-        o = ring[n % len(ring)]
-        if x.shape[0] != o.shape[0]:
-            o = o[:x.shape[0]]
-        self.rec.append((spb, x, None, None, extra, extra_pstride, extra_cstride, False, y_planar, o, None, spa))
+        o = self._slot(spb.key, x.shape[0])
+        self.rec.append(Launch(spb, x, None, None, extra, extra_pstride, extra_cstride, False, y_planar, o, None, spa))
         return o
 
     def conv_head_fused(self, sp0, sp3, x, out=None):
         """the fused entry pair as ONE recorded launch writing inc3's ring (inc0's ring stays unused)"""
-        ring = self.eng.rings[sp3.key]
-        n = self.count.get(sp3.key, 0)
-        self.count[sp3.key] = n + 1
-        o = ring[n % len(ring)]
-        if x.shape[0] != o.shape[0]:
-            o = o[:x.shape[0]]
-        self.rec.append((sp3, x, None, None, None, 0, 1, True, None, o, sp0, None))
+        o = self._slot(sp3.key, x.shape[0])
+        self.rec.append(Launch(sp3, x, None, None, None, 0, 1, True, None, o, sp0, None))
         return o
 
     def take(self):
@@ -131,9 +130,9 @@ class _Recorder:
 
 
 def _signature(rec):
-    return tuple((r[0].key, r[1].shape[0], r[1].data_ptr(), r[2].t.data_ptr() if r[2] is not None else 0,
-                  r[3].t.data_ptr() if r[3] is not None else 0, r[4].data_ptr() if r[4] is not None else 0,
-                  r[9].data_ptr()) for r in rec)
+    return tuple((r.sp.key, r.x.shape[0], r.x.data_ptr(), r.halo_prev.t.data_ptr() if r.halo_prev is not None else 0,
+                  r.halo_next.t.data_ptr() if r.halo_next is not None else 0, r.extra.data_ptr() if r.extra is not None else 0,
+                  r.out.data_ptr()) for r in rec)
 
 
 class _Plan:
@@ -173,30 +172,14 @@ class StreamEngine:
         # the caller's frames are copied (and converted to fp32) into this ring: inc0 reads them in place, the residual
         # of DenBlock 1 reads them again 8 steps later (MemSkip skip1, bsvd_arch.py:378,394)
         ring("input", (n, in_ch, H, W), 10)
-        exit_key = net.temp2["out3"].key
-        fuse = getattr(ex, "fuse_head", None)
-        fused_away = {net.temp1["inc0"].key} if (fuse and fuse(net.temp1)) else set()     # their outputs never exist (engine.head_fusable / pair_fusable)
-        fusep = getattr(ex, "fuse_pair", None)
-        if fusep:
-            for blk in (net.temp1, net.temp2):
-                for na, nb in (("inc0", "inc3"), ("out0", "out3")):
-                    if fusep(blk, na, nb):
-                        fused_away.add(blk[na].key)
+        fused_away = {net.temp1["inc0"].key} if _fused_head(ex, net.temp1) else set()     # their outputs never exist (engine.head_fusable / pair_fusable)
         for blk in (net.temp1, net.temp2):
-            h, w = H, W
-            for name, sp in blk.items():
-                ho, wo = (h - 1) // sp.stride + 1, (w - 1) // sp.stride + 1
-                if sp.epilogue == 1:            # EPI_PS_ADD
-                    shape = (n, 2 * ho, 2 * wo, sp.cout_pad // 4)
-                    h, w = 2 * ho, 2 * wo
-                else:
-                    shape = (n, ho, wo, sp.cout_pad)
-                    h, w = ho, wo
-                if sp.key == exit_key:          # planar [n, out_ch, H, W]: what the caller gets a copy of
-                    shape = (n, sp.cout, ho, wo)
-                if sp.key in fused_away:
-                    continue
-                ring(sp.key, shape, ring_depth(name, blk is net.temp1 and name == "out3", sp.key == exit_key), out_v(sp) if out_v else 0)
+            for na, nb in (("inc0", "inc3"), ("out0", "out3")):
+                if _fused_pair(ex, blk, na, nb):
+                    fused_away.add(blk[na].key)
+        for name, sp, shape, depth in _ring_layout(net, H, W, n):
+            if sp.key not in fused_away:
+                ring(sp.key, shape, depth, out_v(sp) if out_v else 0)
         self.t1 = _DenBlockStream(net.temp1)
         self.t2 = _DenBlockStream(net.temp2)
         self.r1 = _Recorder(self)
@@ -265,8 +248,7 @@ class StreamEngine:
         y = blk.feed(recorder, x, x_planar=x_planar, y_planar=y_planar)
         rec = recorder.take()
         sig = _signature(rec)
-        pk = getattr(self.ex, "packed", None)
-        shared_chip = bool(shared_chip and self.hip and pk is not None and getattr(pk, "wino", None) and any(v in (2, 6) for v in pk.wino_layer_abi.values()))
+        shared_chip = bool(shared_chip and self.hip and any(v in (2, 6) for v in self.ex.packed.wino_layer_abi.values()))
         if shared_chip:             # (only an engine whose launches pick their own tile keeps two sets of plans)
             sig = ("shared", sig)
         plan = self.plans.get(sig)
@@ -275,7 +257,8 @@ class StreamEngine:
             if self.hip:
                 plan.args = (self.ex.lib_args_type() * max(plan.n, 1))()
                 for i, r in enumerate(rec):
-                    plan.args[i], _ = self.ex.build_args(*r[:9], out=r[9], head=r[10], shared_chip=shared_chip, pre=r[11])
+                    plan.args[i], _ = self.ex.build_args(r.sp, r.x, r.halo_prev, r.halo_next, r.extra, r.extra_pstride, r.extra_cstride,
+                                                         r.x_planar, r.y_planar, out=r.out, head=r.head, shared_chip=shared_chip, pre=r.pre)
             self.plans[sig] = plan
         return y, sig, plan
 
@@ -283,15 +266,14 @@ class StreamEngine:
     def _issue_generic(self, plan):
         """plain executor (CPU tests): layer by layer, in order"""
         for r in plan.rec:
-            sp, x, hp, hn, extra, eps, ecs, xpl, ypl, o = r[:10]
-            if r[10] is not None:
-                self.ex.conv_head_fused(r[10], sp, x, out=o)
-                continue
-            if r[11] is not None:
-                self.ex.conv_pair_fused(r[11], sp, x, extra=extra, extra_pstride=eps, extra_cstride=ecs, y_planar=ypl, out=o)
-                continue
-            self.ex.conv(sp, x, halo_prev=hp, halo_next=hn, extra=extra, extra_pstride=eps, extra_cstride=ecs,
-                         x_planar=xpl, y_planar=ypl, out=o)
+            if r.head is not None:
+                self.ex.conv_head_fused(r.head, r.sp, r.x, out=r.out)
+            elif r.pre is not None:
+                self.ex.conv_pair_fused(r.pre, r.sp, r.x, extra=r.extra, extra_pstride=r.extra_pstride, extra_cstride=r.extra_cstride,
+                                        y_planar=r.y_planar, out=r.out)
+            else:
+                self.ex.conv(r.sp, r.x, halo_prev=r.halo_prev, halo_next=r.halo_next, extra=r.extra, extra_pstride=r.extra_pstride,
+                             extra_cstride=r.extra_cstride, x_planar=r.x_planar, y_planar=r.y_planar, out=r.out)
 
     def _streams(self):
         if self._cap is None:

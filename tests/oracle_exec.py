@@ -9,7 +9,7 @@ comparator for the GPU parity tests.  Never imported by bsvd_amd.
 import torch
 import torch.nn.functional as F
 
-from bsvd_amd.netspec import EPI_PS_ADD, EPI_RESID
+from bsvd_amd.netspec import EPI_PS_ADD, EPI_RESID, out_hwc
 
 
 def _slice_from_halo(halo, hw, n):
@@ -55,10 +55,7 @@ class OracleExecutor:
 
     def out_shape(self, sp, x):
         T, H, W, _ = x.shape
-        Ho, Wo = (H - 1) // sp.stride + 1, (W - 1) // sp.stride + 1
-        if sp.epilogue == EPI_PS_ADD:
-            return (T, 2 * Ho, 2 * Wo, sp.cout_pad // 4)
-        return (T, Ho, Wo, sp.cout_pad)
+        return (T,) + out_hwc(sp, H, W)
 
     def halo_pack(self, frame, c0, n):
         return frame[..., c0:c0 + n].contiguous()

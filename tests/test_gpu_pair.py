@@ -130,6 +130,53 @@ def test_whole_network_with_fused_pairs_is_bit_identical_in_every_schedule(blind
     models[True].release_stream_buffers()
 
 
+def test_every_launch_passes_through_exactly_one_public_launch_method():
+    """A profiler wraps conv / conv_head_fused / conv_pair_fused on the executor INSTANCE and sets record_variants around each call (bench.py's
+    LaunchTimer): every launch of the clip schedule and of the layer-by-layer stream schedule must pass through exactly one of the three
+    -- none of them may end in another -- and leave the kernel's name behind."""
+    import bsvd_amd
+    from bsvd_amd.stream_plan import StreamEngine
+    dev = torch.device("cuda", 0)
+    m = bsvd_amd.BSVD(chns=[64, 128, 256], mid_ch=64, in_ch=4, out_ch=3, norm="none", act="relu6", interm_ch=64, pretrain_ckpt=None,
+                      precision="f16x3", fuse_pairs=True, engine_mode="clip")
+    m.load_state_dict({k: torch.as_tensor(v) for k, v in seeded_state(bsvd_keys([64, 128, 256], 64, 4, 3, 64), 9).items()})
+    m = m.to(dev).eval()
+    x = torch.from_numpy(np.random.RandomState(4).rand(1, 3, 4, 16, 24).astype(np.float32)).to(dev)
+    ex = m._executor(dev)
+    calls = {}
+
+    def wrap(name):
+        orig = getattr(ex, name)
+
+        def counted(*a, **k):
+            ex.record_variants, ex.last_variant = True, None
+            y = orig(*a, **k)
+            assert ex.last_variant, name
+            calls[name] = calls.get(name, 0) + 1
+            return y
+        setattr(ex, name, counted)
+
+    for name in ("conv", "conv_head_fused", "conv_pair_fused"):
+        wrap(name)
+    n0 = ex.launches
+    y = m(x)
+    assert ex.launches - n0 == sum(calls.values()) == 28         # 32 layers: the entry pair and three fused pairs are one launch each
+    assert calls == {"conv": 24, "conv_head_fused": 1, "conv_pair_fused": 3}
+    eng = StreamEngine(m.net, ex, 16, 24, 4)
+    eng.layerwise = True
+    calls.clear()
+    n0 = ex.launches
+    outs = []
+    for f in list(x[0].split(1)) + [None] * m.shift_num:
+        o = eng.feed(f, (3, None))               # a view of the exit ring: copy before the next step
+        if o is not None:
+            outs.append(o.clone())
+    assert eng.feed(None, (3, None)) is None
+    assert ex.launches - n0 == sum(calls.values()) == 3 * 28 and set(calls) == {"conv", "conv_head_fused", "conv_pair_fused"}
+    assert torch.equal(torch.cat(outs), y[0])
+    eng.release()
+
+
 def test_fused_pair_refuses_what_it_cannot_run():
     from bsvd_amd import _lib
     a, b, st, fused, plain = _setup(64, 64, 64, "relu6", "relu6", 0)

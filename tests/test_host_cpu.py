@@ -7,6 +7,7 @@ import torch
 
 from helpers import bsvd_keys, load_golden, maxabs, state_for
 from oracle_exec import OracleExecutor
+from seeded import seeded_state
 
 
 def _model(**kw):
@@ -88,3 +89,17 @@ def test_both_schedules_with_fused_pairs_equal_the_unfused_ones(T):
     assert eng.feed(None, (3, None)) is None
     got = torch.cat([o for o in outs if o is not None])
     assert got.shape == y0.shape and maxabs(got.numpy(), y0.numpy()) < 1e-4 and not bool(torch.isnan(got).any())      # (CPU conv2d: batch-dependent last bits)
+
+
+@pytest.mark.parametrize("name,H,W,want", [("down0", 7, 9, (4, 5, 32)), ("down0", 1, 1, (1, 1, 32)),      # stride 2 at odd sizes
+                                           ("up2", 3, 5, (6, 10, 32)),                                  # PixelShuffle
+                                           ("out0", 4, 6, (4, 6, 16))])                                 # plain
+def test_out_hwc_is_the_shape_the_oracle_conv_returns(name, H, W, want):
+    """netspec.out_hwc is the one statement of a layer's output shape (executors, ring layout): it must say what a conv produces"""
+    from bsvd_amd.netspec import make_netspec, out_hwc
+    sp = make_netspec([16, 32, 64], 16, 4, 3, "relu6", 16).temp1[name]
+    ex = OracleExecutor(seeded_state([(sp.key + ".weight", (sp.cout, sp.cin, 3, 3)), (sp.key + ".bias", (sp.cout,))], 1))
+    x = torch.zeros((2, H, W, sp.cin_pad))
+    y = ex.conv(sp, x)
+    assert out_hwc(sp, H, W) == want
+    assert tuple(y.shape) == (2,) + want == ex.out_shape(sp, x)

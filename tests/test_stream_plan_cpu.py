@@ -10,7 +10,7 @@ from oracle_exec import OracleExecutor
 from seeded import seeded_state, seeded_clip
 from bsvd_amd.netspec import make_netspec
 from bsvd_amd.schedule import StreamPipeline
-from bsvd_amd.stream_plan import StreamEngine, ring_depth, RING_PERIOD
+from bsvd_amd.stream_plan import Launch, StreamEngine, ring_depth, RING_PERIOD
 
 
 def _engine(net, st, H, W, C, chunk=1):
@@ -120,6 +120,30 @@ def test_steady_state_signature_has_the_ring_period():
     for t in range(20):
         eng.feed(x2[t:t + 1], (3, None))
     assert len(eng.plans) == before
+
+
+def test_recorded_launches_name_their_fused_pair_and_planar_entry():
+    """A plan's steps are Launch records read by field: a fused pair carries its first conv in ``pre`` (never ``head``), the network
+    entry is the only launch on planar input.  (That steps one ring period apart have equal signatures is pinned by the test above:
+    the plan table stops growing.)"""
+    net = make_netspec([32, 64, 128], 32, 4, 3, "relu6", 32)
+    st = seeded_state(bsvd_keys([32, 64, 128], 32, 4, 3, 32), 5)
+    eng = StreamEngine(net, OracleExecutor(st, fuse_pairs=True), 8, 12, 4, alloc=lambda shape: torch.zeros(shape, dtype=torch.float32),
+                       poison=True)
+    x = torch.zeros((1, 4, 8, 12))
+    for _ in range(net.shift_num + 1):
+        y = eng.feed(x, (3, None))
+    assert y is not None                      # the pipeline is full: every layer of both DenBlocks has been recorded
+    recs = [r for p in eng.plans.values() for r in p.rec]
+    assert recs and all(isinstance(r, Launch) for r in recs)
+    pairs = [r for r in recs if r.pre is not None]
+    assert {(r.pre.key, r.sp.key) for r in pairs} == {(net.temp1["out0"].key, net.temp1["out3"].key), (net.temp2["inc0"].key, net.temp2["inc3"].key),
+                                                      (net.temp2["out0"].key, net.temp2["out3"].key)}
+    assert all(r.head is None and not r.x_planar and r.halo_prev is None and r.halo_next is None for r in pairs)
+    assert all(r.y_planar == (3, None) for r in pairs if r.sp.key == net.temp2["out3"].key)
+    entry = [r for r in recs if r.x_planar]
+    assert entry and all(r.sp.key == net.temp1["inc0"].key and r.head is None and r.pre is None for r in entry)
+    assert all(r.out.shape[0] == r.x.shape[0] == 1 for r in recs)
 
 
 @pytest.mark.parametrize("chunk", [2, 3, 8])
