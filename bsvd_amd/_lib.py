@@ -20,7 +20,11 @@ EXPORTS = ("bsvd_abi_version", "bsvd_conv_args_size", "bsvd_build_info", "bsvd_l
            "bsvd_nchw_to_nhwc", "bsvd_nhwc_to_nchw", "bsvd_halo_pack", "bsvd_halo_unpack", "bsvd_workspace_bytes",
            "bsvd_u8_to_planar", "bsvd_planar_to_u8", "bsvd_conv3x3_batch", "bsvd_graph_begin", "bsvd_graph_fork",
            "bsvd_graph_join", "bsvd_graph_end", "bsvd_graph_abort", "bsvd_graph_launch", "bsvd_graph_destroy",
-           "bsvd_v_frame_elems", "bsvd_v_groups", "bsvd_to_v")
+           "bsvd_v_frame_elems", "bsvd_v_groups", "bsvd_to_v",
+           "bsvd_yuv420_frame_bytes", "bsvd_yuv420_to_planar", "bsvd_planar_to_yuv420")
+PIX_FMT = {"nv12": 0, "p010": 1}
+MATRIX = {"bt601": 0, "bt709": 1, "bt2020": 2}
+CHROMA = {"nearest": 0, "linear": 1}
 
 
 class BsvdConvArgs(ctypes.Structure):
@@ -62,6 +66,12 @@ class BsvdConvArgs(ctypes.Structure):
         ("x_v", ctypes.c_int32), ("y_v", ctypes.c_int32),
         ("out_scale", ctypes.c_float), ("head_out_scale", ctypes.c_float), ("pre_out_scale", ctypes.c_float),
     ]
+
+
+class BsvdYuvDesc(ctypes.Structure):
+    """Mirror of ``struct BsvdYuvDesc`` (include/bsvd_hip.h)."""
+    _fields_ = [("pix_fmt", ctypes.c_int32), ("matrix", ctypes.c_int32), ("full_range", ctypes.c_int32), ("chroma", ctypes.c_int32),
+                ("row_pitch", ctypes.c_int32), ("reserved", ctypes.c_int32), ("frame_stride", ctypes.c_int64)]
 
 
 class BsvdLibraryError(RuntimeError):
@@ -134,6 +144,12 @@ def load():
     lib.bsvd_v_groups.argtypes = [i32, i32]
     lib.bsvd_to_v.restype = ctypes.c_int
     lib.bsvd_to_v.argtypes = [vp, i64, i32, vp, i64, i32, i32, i32, i32, i32, vp]
+    lib.bsvd_yuv420_frame_bytes.restype = i64
+    lib.bsvd_yuv420_frame_bytes.argtypes = [i32, i32, i32, i32]
+    lib.bsvd_yuv420_to_planar.restype = ctypes.c_int
+    lib.bsvd_yuv420_to_planar.argtypes = [vp, vp, i32, i32, i32, ctypes.POINTER(BsvdYuvDesc), i32, f32, vp]
+    lib.bsvd_planar_to_yuv420.restype = ctypes.c_int
+    lib.bsvd_planar_to_yuv420.argtypes = [vp, vp, i32, i32, i32, ctypes.POINTER(BsvdYuvDesc), vp]
     lib.bsvd_workspace_bytes.restype = i64
     lib.bsvd_workspace_bytes.argtypes = [ctypes.POINTER(BsvdConvArgs)]
     if lib.bsvd_abi_version() != ABI_VERSION:

@@ -336,14 +336,6 @@ __global__ void to_v_kernel(const float *__restrict__ x, int64_t x_fs, int x_f32
     }
 }
 
-static inline unsigned grid_for(int64_t n, int block)
-{
-    int64_t g = (n + block - 1) / block;
-    if (g > 256 * 16) g = 256 * 16;
-    if (g < 1) g = 1;
-    return (unsigned)g;
-}
-
 }  // namespace bsvd
 
 using namespace bsvd;

@@ -74,6 +74,15 @@ __host__ __device__ constexpr int v_block_floats(int m) { return ((m + 2) * 4 * 
 
 void set_error(const char *fmt, ...);
 
+// grid of the bandwidth-bound helper kernels (grid-stride loops over n items): enough workgroups to fill the chip, capped at 16 per CU
+static inline unsigned grid_for(int64_t n, int block)
+{
+    int64_t g = (n + block - 1) / block;
+    if (g > 256 * 16) g = 256 * 16;
+    if (g < 1) g = 1;
+    return (unsigned)g;
+}
+
 // fp16 range of the split mode.  Every value is carried as hi = fp16(v), lo = fp16(v - hi); a conversion that overflows to +-inf turns
 // the pair into (inf, NaN) and every product it meets into NaN.  The stores of the direct kernel clamp to +-65504 first (v_med3_f32),
 // but the Winograd kernel converts TRANSFORMED values -- sums of up to 2x (F(2,3)), 3x (F(4,3)), 4.7x (F(6,3)) the activation range --

@@ -11,9 +11,9 @@ OUT="${BSVD_OUT:-$ROOT/bsvd_amd/libbsvd_hip.so}"
 # objects live outside the package: build/obj (product), build/obj_ab<i> (tools/build_ab.sh variants)
 OBJ="$ROOT/build/obj${BSVD_OBJ_SUFFIX:-}"
 mkdir -p "$OBJ"
-# the product library: four translation units.  A measurement build (EXTRA_HIPCC_FLAGS contains -DBSVD_MEASURE, tools/build_measure.sh)
+# the product library: five translation units.  A measurement build (EXTRA_HIPCC_FLAGS contains -DBSVD_MEASURE, tools/build_measure.sh)
 # adds conv3x3_wino.hip (the rejected all-positions-per-wave Winograd kernel) and the variant instantiations of conv3x3_winox.hip
-SRCS="conv3x3_mfma conv3x3_winox conv3x3_edge_f32 bsvd_abi"
+SRCS="conv3x3_mfma conv3x3_winox conv3x3_edge_f32 bsvd_abi frame_yuv"
 case " ${EXTRA_HIPCC_FLAGS} " in *" -DBSVD_MEASURE"*) SRCS="$SRCS conv3x3_wino";; esac
 pids=()
 for src in $SRCS; do

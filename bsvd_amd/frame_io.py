@@ -1,7 +1,11 @@
 """uint8 frame I/O on the device: upload frames as uint8 (4x less PCIe traffic than fp32), build the
 network input (RGB/255 + constant sigma map, the tensor ``temp_denoise`` hands to the model,
 /root/reference/Experimental_root/models/validation_seq_infer.py:15-24) and turn the result into uint8 with the
-reference's clamp + round (``tensor2img``, /root/reference/BasicSR/basicsr/utils/img_util.py:66,87-90) -- both on the GPU."""
+reference's clamp + round (``tensor2img``, /root/reference/BasicSR/basicsr/utils/img_util.py:66,87-90) -- both on the GPU.
+
+The same two steps for YUV 4:2:0 surfaces (NV12, P010), the formats decoders, capture cards and encoders speak:
+``yuv420_to_input`` / ``output_to_yuv420`` (include/bsvd_hip.h, bsvd_yuv420_to_planar / bsvd_planar_to_yuv420; 1.5 or 3 bytes per
+pixel over PCIe instead of RGB24's 3, and no colour conversion on the host)."""
 import ctypes
 
 import torch
@@ -41,4 +45,76 @@ def output_to_frames(y, hwc=True, rgb2bgr=False):
     with torch.cuda.device(y.device):
         _lib.check(lib.bsvd_planar_to_u8(y.data_ptr(), out.data_ptr(), T, C, H, W, 1 if hwc else 0, 1 if rgb2bgr else 0,
                                          _stream()), "bsvd_planar_to_u8")
+    return out
+
+
+def _yuv_desc(H, W, pix_fmt, matrix, full_range, chroma, row_pitch):
+    """-> (BsvdYuvDesc, frame_bytes); ValueError for a name or a size the library would refuse"""
+    for what, name, table in (("pix_fmt", pix_fmt, _lib.PIX_FMT), ("matrix", matrix, _lib.MATRIX), ("chroma", chroma, _lib.CHROMA)):
+        if name not in table:
+            raise ValueError("%s %r: one of %s" % (what, name, ", ".join(sorted(table))))
+    desc = _lib.BsvdYuvDesc(pix_fmt=_lib.PIX_FMT[pix_fmt], matrix=_lib.MATRIX[matrix], full_range=1 if full_range else 0,
+                            chroma=_lib.CHROMA[chroma], row_pitch=int(row_pitch or 0))
+    nbytes = _lib.load().bsvd_yuv420_frame_bytes(int(H), int(W), desc.pix_fmt, desc.row_pitch)
+    if nbytes < 0:
+        raise ValueError("yuv420 %s frame %d x %d with row_pitch %s: H and W must be positive multiples of 4 and row_pitch (bytes%s) at least "
+                         "W samples" % (pix_fmt, H, W, row_pitch, ", even" if pix_fmt == "p010" else ""))
+    return desc, nbytes
+
+
+def yuv420_frame_bytes(H, W, pix_fmt, row_pitch=None):
+    """Bytes of one NV12 / P010 frame: ``row_pitch * H * 3 / 2`` (Y plane, then the interleaved CbCr plane of H/2 rows);
+    ``row_pitch`` in bytes, None = tight (W samples)."""
+    return _yuv_desc(H, W, pix_fmt, "bt709", False, "linear", row_pitch)[1]
+
+
+def _yuv_buffer(buf, T, nbytes, pix_fmt, what):
+    """a surface buffer [T, >= frame_bytes] -> its frame stride in bytes"""
+    if buf.dtype != torch.uint8 or not buf.is_cuda or buf.dim() != 2 or not buf.is_contiguous():
+        raise ValueError("%s: expected a contiguous uint8 device tensor [T, frame_bytes] (P010 callers view their uint16 as bytes)" % what)
+    if (T is not None and buf.shape[0] != T) or buf.shape[0] < 1 or buf.shape[1] < nbytes:
+        raise ValueError("%s: shape %s, expected [%s, %d] (or longer rows: frames row-length bytes apart)"
+                         % (what, tuple(buf.shape), "T" if T is None else T, nbytes))
+    if pix_fmt == "p010" and buf.shape[1] % 2:
+        raise ValueError("%s: p010 frames must be an even number of bytes apart, got %d" % (what, buf.shape[1]))
+    return buf.shape[1]
+
+
+def yuv420_to_input(buf, H, W, pix_fmt="nv12", matrix="bt709", full_range=False, chroma="linear", sigma=None, row_pitch=None):
+    """buf: uint8 device tensor [T, frame_bytes] of NV12 / P010 frames (``yuv420_frame_bytes``; rows longer than one frame are
+    frames that far apart) -> fp32 [T,3(+1),H,W] RGB, the tensor ``frames_to_input`` builds; with ``sigma`` the constant noise-map
+    channel is appended.  matrix 'bt601' | 'bt709' | 'bt2020', limited or full range, chroma upsampling 'nearest' | 'linear'
+    (MPEG-2 / H.264 / HEVC default siting).  The result is NOT clamped to [0,1]: the out-of-gamut values of a noisy source are
+    information for a denoiser."""
+    desc, nbytes = _yuv_desc(H, W, pix_fmt, matrix, full_range, chroma, row_pitch)
+    lib = require_hip()
+    desc.frame_stride = _yuv_buffer(buf, None, nbytes, pix_fmt, "yuv420_to_input")
+    T = buf.shape[0]
+    extra = 0 if sigma is None else 1
+    y = torch.empty((T, 3 + extra, H, W), dtype=torch.float32, device=buf.device)
+    with torch.cuda.device(buf.device):
+        _lib.check(lib.bsvd_yuv420_to_planar(buf.data_ptr(), y.data_ptr(), T, H, W, ctypes.byref(desc), extra, float(sigma or 0.0),
+                                             _stream()), "bsvd_yuv420_to_planar")
+    return y
+
+
+def output_to_yuv420(y, pix_fmt="nv12", matrix="bt709", full_range=False, chroma="linear", row_pitch=None, out=None):
+    """y: fp32 device tensor [T,3,H,W] RGB -> uint8 [T, frame_bytes] NV12 / P010 frames: clamp [0,1], matrix, chroma downsampling
+    ('nearest': mean of the 2x2 block; 'linear': rows averaged, [1 2 1]/4 over columns), scale, clamp to the legal codes, round half
+    to even.  ``out``: the caller's buffer [T, >= frame_bytes] to write into -- pitch padding and the bytes between frames are left
+    as they were; without it the result's padding is zero."""
+    if y.dtype != torch.float32 or not y.is_cuda or y.dim() != 4 or y.shape[1] != 3:
+        raise ValueError("expected a float32 device tensor [T,3,H,W]")
+    T, _, H, W = y.shape
+    desc, nbytes = _yuv_desc(H, W, pix_fmt, matrix, full_range, chroma, row_pitch)
+    lib = require_hip()
+    y = y.contiguous()
+    if out is None:
+        out = (torch.zeros if row_pitch else torch.empty)((T, nbytes), dtype=torch.uint8, device=y.device)
+    elif out.device != y.device:
+        raise ValueError("output_to_yuv420: out is on %s, y on %s" % (out.device, y.device))
+    desc.frame_stride = _yuv_buffer(out, T, nbytes, pix_fmt, "output_to_yuv420(out=)")
+    with torch.cuda.device(y.device):
+        _lib.check(lib.bsvd_planar_to_yuv420(y.data_ptr(), out.data_ptr(), T, H, W, ctypes.byref(desc), _stream()),
+                   "bsvd_planar_to_yuv420")
     return out

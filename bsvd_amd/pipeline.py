@@ -11,13 +11,98 @@ flows through three HIP streams so PCIe never idles the matrix cores:
 
 ``depth`` slots of pinned staging memory form a ring; slot k is reused once its download has completed.  Results are
 yielded in submission order.
+
+``pix_fmt`` selects what crosses PCIe: 'rgb24' (the default, packed RGB uint8 [H,W,3]) or the YUV 4:2:0 surfaces video sources and
+sinks speak, 'nv12' (uint8) and 'p010' (uint16, 10-bit code in the high bits), as arrays [H*3/2, pitch] -- the Y plane's H rows,
+then the H/2 rows of interleaved CbCr; 1.5 (NV12) or 3 (P010) bytes per pixel each way instead of 3, converted by
+``bsvd_yuv420_to_planar`` / ``bsvd_planar_to_yuv420`` where the uint8 kernels run for 'rgb24'.
 """
 import collections
 
 import numpy as np
 import torch
 
-from .frame_io import frames_to_input, output_to_frames
+from .frame_io import _yuv_desc, frames_to_input, output_to_frames, output_to_yuv420, yuv420_frame_bytes, yuv420_to_input
+
+Colour = collections.namedtuple("Colour", "matrix full_range chroma row_pitch width", defaults=("bt709", False, "linear", None, None))
+Colour.__doc__ = """How a YUV surface is to be read and written: matrix 'bt601' | 'bt709' | 'bt2020', full_range (False = limited / "TV"
+range), chroma 'nearest' | 'linear' (frame_io.yuv420_to_input), row_pitch in bytes (None = tight; otherwise it must be the arrays' row
+length) and, for a pitch wider than the picture, its width W in samples (None = the arrays' row length)."""
+
+
+_Geometry = collections.namedtuple("_Geometry", "h w staging row_pitch")      # of one submitted array: picture size, shape of its bytes
+                                                                                # in the staging buffers, YUV row pitch (None = tight)
+
+
+class _Rgb24:
+    """packed RGB uint8 [H,W,3]: staged as it comes, converted by bsvd_u8_to_planar / bsvd_planar_to_u8"""
+    dtype = np.dtype(np.uint8)
+
+    def geometry(self, a, clip):
+        if a.dtype != np.uint8 or a.ndim != (4 if clip else 3) or a.shape[-1] != 3:
+            raise ValueError("expected uint8 frames [T,H,W,3]" if clip else "expected one uint8 frame [H,W,3]")
+        if a.shape[-3] % 4 or a.shape[-2] % 4:
+            raise ValueError("H and W must be multiples of 4 (pad first: denoise.pad_to_multiple_of_4)")
+        return _Geometry(a.shape[-3], a.shape[-2], tuple(a.shape), None)
+
+    def to_input(self, dev_in, geom, sigma):
+        return frames_to_input(dev_in, sigma)
+
+    def to_output(self, y, geom):
+        return output_to_frames(y)
+
+
+class _Yuv420:
+    """NV12 (uint8) / P010 (uint16) arrays [H*3/2, pitch]: staged as the bytes of the surface, converted by bsvd_yuv420_to_planar /
+    bsvd_planar_to_yuv420"""
+
+    def __init__(self, pix_fmt, colour):
+        if colour is None:
+            colour = Colour()
+        elif isinstance(colour, dict):
+            unknown = set(colour) - set(Colour._fields)
+            if unknown:
+                raise ValueError("colour: unknown key(s) %s (known: %s)" % (sorted(unknown), ", ".join(Colour._fields)))
+            colour = Colour(**colour)
+        else:
+            colour = Colour(*colour)
+        self.pix_fmt, self.colour = pix_fmt, colour
+        self.dtype = np.dtype(np.uint8 if pix_fmt == "nv12" else np.uint16)
+        self.kw = dict(pix_fmt=pix_fmt, matrix=colour.matrix, full_range=bool(colour.full_range), chroma=colour.chroma)
+        _yuv_desc(4, 4, row_pitch=None, **self.kw)               # a wrong name fails here, not at the first frame
+
+    def geometry(self, a, clip):
+        what = "%s %s [%sH*3/2,pitch]" % (self.pix_fmt, self.dtype.name, "T," if clip else "")
+        if a.dtype != self.dtype or a.ndim != (3 if clip else 2):
+            raise ValueError("expected %s, got %s %s" % (what, a.dtype, a.shape))
+        rows, pitch = a.shape[-2], a.shape[-1]
+        w = pitch if self.colour.width is None else int(self.colour.width)
+        if rows <= 0 or rows % 6 or w <= 0 or w % 4:
+            raise ValueError("expected %s with H and W multiples of 4 (pad first: denoise.pad_to_multiple_of_4), got %s" % (what, a.shape))
+        if w > pitch:
+            raise ValueError("%s: rows of %d samples are shorter than colour.width = %d" % (what, pitch, w))
+        row_bytes = pitch * self.dtype.itemsize
+        if self.colour.row_pitch is not None and self.colour.row_pitch != row_bytes:
+            raise ValueError("%s: rows of %d bytes, colour.row_pitch says %d" % (what, row_bytes, self.colour.row_pitch))
+        h = rows // 3 * 2
+        nbytes = yuv420_frame_bytes(h, w, self.pix_fmt, row_bytes)
+        return _Geometry(h, w, (a.shape[0], nbytes) if clip else (nbytes,), None if w == pitch else row_bytes)
+
+    def to_input(self, dev_in, geom, sigma):
+        return yuv420_to_input(dev_in, geom.h, geom.w, sigma=sigma, row_pitch=geom.row_pitch, **self.kw)
+
+    def to_output(self, y, geom):
+        return output_to_yuv420(y, row_pitch=geom.row_pitch, **self.kw)
+
+
+def _pixel_format(pix_fmt, colour):
+    if pix_fmt == "rgb24":
+        if colour is not None:
+            raise ValueError("colour describes a YUV surface; pix_fmt 'rgb24' takes none")
+        return _Rgb24()
+    if pix_fmt in ("nv12", "p010"):
+        return _Yuv420(pix_fmt, colour)
+    raise ValueError("pix_fmt %r: one of 'rgb24', 'nv12', 'p010'" % (pix_fmt,))
 
 
 class _Slot:
@@ -34,13 +119,13 @@ class _Slot:
 class _Ticket:
     """One submitted clip: owns its slot until the download has been copied out of the pinned buffer."""
 
-    def __init__(self, slot):
-        self.slot, self.result = slot, None
+    def __init__(self, slot, dtype):
+        self.slot, self.dtype, self.result = slot, dtype, None
 
     def finish(self):
         if self.slot is not None:
             self.slot.downloaded.synchronize()
-            self.result = self.slot.pin_out.numpy().copy()
+            self.result = self.slot.pin_out.numpy().copy().view(self.dtype).reshape(self.slot.shape)
             self.slot.ticket = None
             self.slot = None
         return self.result
@@ -48,11 +133,13 @@ class _Ticket:
 
 class ClipPipeline:
     """model: a bsvd_amd.BSVD on a HIP device.  sigma: noise std in [0,1] units for the constant noise map (None for a
-    blind model).  depth >= 2 overlaps the transfers of one clip with the forward of another."""
+    blind model).  depth >= 2 overlaps the transfers of one clip with the forward of another.  pix_fmt 'rgb24' | 'nv12' | 'p010' and
+    colour (a ``Colour`` or a dict of its fields; YUV only): what ``submit`` takes and the results are, see the module docstring."""
 
-    def __init__(self, model, sigma=None, depth=2):
+    def __init__(self, model, sigma=None, depth=2, pix_fmt="rgb24", colour=None):
         if depth < 1:
             raise ValueError("depth must be >= 1")
+        self.fmt = _pixel_format(pix_fmt, colour)
         self.model, self.sigma = model, sigma
         self.device = model._device()
         if self.device.type != "cuda":
@@ -65,13 +152,10 @@ class ClipPipeline:
 
     # ------------------------------------------------------------------------------------------------
     def submit(self, frames_u8):
-        """frames_u8: numpy uint8 [T,H,W,3] (RGB).  Enqueues upload + forward + download; returns immediately unless
-        the ring is full (then it first drains the oldest clip into its result)."""
+        """frames_u8: numpy uint8 [T,H,W,3] (RGB); with pix_fmt 'nv12' / 'p010' uint8 / uint16 [T,H*3/2,pitch].  Enqueues upload +
+        forward + download; returns immediately unless the ring is full (then it first drains the oldest clip into its result)."""
         frames_u8 = np.ascontiguousarray(frames_u8)
-        if frames_u8.dtype != np.uint8 or frames_u8.ndim != 4 or frames_u8.shape[-1] != 3:
-            raise ValueError("expected uint8 frames [T,H,W,3]")
-        if frames_u8.shape[1] % 4 or frames_u8.shape[2] % 4:
-            raise ValueError("H and W must be multiples of 4 (pad first: denoise.pad_to_multiple_of_4)")
+        geom = self.fmt.geometry(frames_u8, clip=True)
         slot = self.slots[self.count % len(self.slots)]
         self.count += 1
         if slot.ticket is not None:
@@ -79,28 +163,28 @@ class ClipPipeline:
         with torch.cuda.device(self.device):
             if slot.shape != frames_u8.shape:
                 slot.shape = frames_u8.shape
-                slot.pin_in = torch.empty(frames_u8.shape, dtype=torch.uint8).pin_memory()
-                slot.pin_out = torch.empty(frames_u8.shape, dtype=torch.uint8).pin_memory()
-                slot.dev_in = torch.empty(frames_u8.shape, dtype=torch.uint8, device=self.device)
-            slot.pin_in.numpy()[...] = frames_u8
+                slot.pin_in = torch.empty(geom.staging, dtype=torch.uint8).pin_memory()
+                slot.pin_out = torch.empty(geom.staging, dtype=torch.uint8).pin_memory()
+                slot.dev_in = torch.empty(geom.staging, dtype=torch.uint8, device=self.device)
+            slot.pin_in.numpy()[...] = frames_u8.view(np.uint8).reshape(geom.staging)
             with torch.cuda.stream(self.up):
                 slot.dev_in.copy_(slot.pin_in, non_blocking=True)
                 slot.uploaded.record()
             with torch.cuda.stream(self.comp):
                 self.comp.wait_event(slot.uploaded)
-                x = frames_to_input(slot.dev_in, self.sigma)
+                x = self.fmt.to_input(slot.dev_in, geom, self.sigma)
                 T, _, H, W = x.shape
                 if self.model._pick_mode(T, H, W) == "clip":
                     y = self.model.clip_forward(x)
                 else:
                     y = self.model.streaming_forward(x)
-                slot.dev_out = output_to_frames(y.float())          # held by the slot until its download completed
+                slot.dev_out = self.fmt.to_output(y.float(), geom)  # held by the slot until its download completed
                 slot.computed.record()
             with torch.cuda.stream(self.down):
                 self.down.wait_event(slot.computed)
                 slot.pin_out.copy_(slot.dev_out, non_blocking=True)
                 slot.downloaded.record()
-        slot.ticket = _Ticket(slot)
+        slot.ticket = _Ticket(slot, self.fmt.dtype)
         self.pending.append(slot.ticket)
         return slot.ticket
 
@@ -110,8 +194,8 @@ class ClipPipeline:
             yield self.pending.popleft().finish()
 
     def run(self, clips):
-        """clips: iterable of uint8 [T,H,W,3] arrays -> generator of denoised uint8 [T,H,W,3] arrays, in order, with up
-        to ``depth`` clips in flight."""
+        """clips: iterable of uint8 [T,H,W,3] arrays (or of the pix_fmt's surfaces) -> generator of the denoised arrays of the same
+        shape and dtype, in order, with up to ``depth`` clips in flight."""
         for clip in clips:
             if len(self.pending) == len(self.slots):
                 yield self.pending.popleft().finish()
@@ -136,13 +220,17 @@ class LiveStream:
     DenBlock 2 run one step behind DenBlock 1 as a parallel graph branch (``BSVD.feed_overlapped``): one more feed of latency
     (``shift_num + depth`` in total), the single-frame launches of two independent chains share the chip.  Results keep
     submission order and are byte-identical in every mode.  Not re-entrant (one stream per instance, like the reference's
-    module state)."""
+    module state).
 
-    def __init__(self, model, sigma=None, depth=2, overlap_blocks=None, frame_shape=None):
+    pix_fmt 'nv12' / 'p010' (with ``colour``, a ``Colour`` or a dict of its fields): feed takes and returns uint8 / uint16 surfaces
+    [H*3/2,pitch] instead, converted by ``bsvd_yuv420_to_planar`` / ``bsvd_planar_to_yuv420``; everything else is the same."""
+
+    def __init__(self, model, sigma=None, depth=2, overlap_blocks=None, frame_shape=None, pix_fmt="rgb24", colour=None):
         """frame_shape: optional (H, W) of the frames to come -- the overlap decision (and with it ``latency``) is then final at
         construction instead of at the first feed."""
         if depth < 1:
             raise ValueError("depth must be >= 1")
+        self.fmt = _pixel_format(pix_fmt, colour)
         self.model, self.sigma, self.depth = model, sigma, depth
         self._overlap_wanted = (depth >= 2) if overlap_blocks is None else bool(overlap_blocks)
         self._overlap_explicit = overlap_blocks is not None
@@ -153,7 +241,7 @@ class LiveStream:
             raise RuntimeError("LiveStream needs the model on a HIP device (model.cuda())")
         with torch.cuda.device(self.device):
             self.up, self.comp, self.down = (torch.cuda.Stream(), torch.cuda.Stream(), torch.cuda.Stream())
-        self.slots, self.shape = None, None
+        self.slots, self.shape, self.geom = None, None, None
         self.inflight = collections.deque()          # (slot, has_output) in submission order
         self.count = 0
         model.reset()
@@ -190,30 +278,30 @@ class LiveStream:
         self.overlap = self._overlap_wanted
         self._overlap_decided = not self._overlap_wanted
 
-    def _alloc(self, shape):
-        self.shape = shape
+    def _alloc(self, shape, geom):
+        self.shape, self.geom = shape, geom
         self.slots = []
         for _ in range(self.depth):                   # step k reuses the slot of step k - depth, which has been handed out
             s = _Slot()
-            s.pin_in = torch.empty(shape, dtype=torch.uint8).pin_memory()
-            s.pin_out = torch.empty(shape, dtype=torch.uint8).pin_memory()
-            s.dev_in = torch.empty((1,) + shape, dtype=torch.uint8, device=self.device)
+            s.pin_in = torch.empty(geom.staging, dtype=torch.uint8).pin_memory()
+            s.pin_out = torch.empty(geom.staging, dtype=torch.uint8).pin_memory()
+            s.dev_in = torch.empty((1,) + geom.staging, dtype=torch.uint8, device=self.device)
             self.slots.append(s)
 
     def _pop(self):
         """oldest in-flight step -> its uint8 frame, or None if that step emitted nothing (pipeline fill)"""
         slot, has_out = self.inflight.popleft()
         slot.downloaded.synchronize()
-        return slot.pin_out.numpy().copy() if has_out else None
+        return slot.pin_out.numpy().copy().view(self.fmt.dtype).reshape(self.shape) if has_out else None
 
     def _step(self, frame_u8, last=False):
         if frame_u8 is not None:
-            self._decide_overlap(frame_u8.shape[0], frame_u8.shape[1])
+            self._decide_overlap(self.geom.h, self.geom.w)
         slot = self.slots[self.count % len(self.slots)]
         self.count += 1
         with torch.cuda.device(self.device):
             if frame_u8 is not None:
-                slot.pin_in.numpy()[...] = frame_u8
+                slot.pin_in.numpy()[...] = frame_u8.view(np.uint8).reshape(self.geom.staging)
                 with torch.cuda.stream(self.up):
                     slot.dev_in[0].copy_(slot.pin_in, non_blocking=True)
                     slot.uploaded.record()
@@ -221,10 +309,10 @@ class LiveStream:
                 x = None
                 if frame_u8 is not None:
                     self.comp.wait_event(slot.uploaded)
-                    x = frames_to_input(slot.dev_in, self.sigma)
+                    x = self.fmt.to_input(slot.dev_in, self.geom, self.sigma)
                 y = self.model.feed_overlapped(x, last=last) if self.overlap else self.model.feedin_one_element(x)
                 if y is not None:
-                    slot.dev_out = output_to_frames(y.float())      # held by the slot until its download completed
+                    slot.dev_out = self.fmt.to_output(y.float(), self.geom)   # held by the slot until its download completed
                 slot.computed.record()
             with torch.cuda.stream(self.down):
                 self.down.wait_event(slot.computed)
@@ -241,15 +329,12 @@ class LiveStream:
 
     def feed(self, frame_u8):
         frame_u8 = np.ascontiguousarray(frame_u8)
-        if frame_u8.dtype != np.uint8 or frame_u8.ndim != 3 or frame_u8.shape[-1] != 3:
-            raise ValueError("expected one uint8 frame [H,W,3]")
-        if frame_u8.shape[0] % 4 or frame_u8.shape[1] % 4:
-            raise ValueError("H and W must be multiples of 4 (pad first: denoise.pad_to_multiple_of_4)")
+        geom = self.fmt.geometry(frame_u8, clip=False)
         if self.shape != frame_u8.shape:
             if self.inflight:
                 raise ValueError("frame size changed mid-stream; flush() first")
             self._reopen_overlap()                    # the rings of another frame size may or may not fit
-            self._alloc(frame_u8.shape)
+            self._alloc(frame_u8.shape, geom)
         self._step(frame_u8)                          # step k is in flight ...
         outs = []
         self._drain(self.depth - 1, outs)             # ... while step k - (depth-1) is waited for and handed out

@@ -294,6 +294,49 @@ int bsvd_planar_to_u8(const float *src, uint8_t *dst, int32_t frames, int32_t C,
                       int32_t reverse_channels, void *stream);
 
 /*
+ * YUV 4:2:0 frame I/O on device: NV12 (8 bit) and P010 (10 bit) surfaces, as decoders, capture cards and encoders hand them over, in place
+ * of the packed RGB above.  The reference has no YUV path: it builds the network input from RGB frames (validation_seq_infer.py:15-24,
+ * what yuv420_to_planar stands in for together with the colour conversion a caller would do on the host) and makes the output image with
+ * tensor2img (img_util.py:66,87-90, what planar_to_yuv420 stands in for).  Added without a new BSVD_ABI_VERSION: discover the three
+ * entry points by symbol (dlsym); a version-12 library without them has no YUV path.
+ *
+ * Surface, per frame: a Y plane of H rows directly followed by an interleaved CbCr plane of H/2 rows, both with row_pitch BYTES per row;
+ * frames frame_stride bytes apart.  NV12: one byte per sample.  P010: one little-endian 16-bit word per sample, the 10-bit code in the
+ * high bits (code = word >> 6 in, word = code << 6 out; the low 6 bits are ignored in, zero out).  H and W are multiples of 4; bytes of a
+ * row beyond W samples are never read and never written.  With b = 8 | 10 bits and s = 2^(b-8):
+ *   matrix      (Kr, Kb) = BT.601 (0.299, 0.114) | BT.709 (0.2126, 0.0722) | BT.2020 non-constant-luminance (0.2627, 0.0593), Kg = 1 - Kr - Kb
+ *   range       limited: y = (Y - 16s) / 219s, c = (C - 128s) / 224s;  full: y = Y / (2^b - 1), c = (C - 2^(b-1)) / (2^b - 1)
+ *   chroma      NEAREST: a 2x2 luma block shares its chroma sample (in) / takes the mean of the block (out).  LINEAR: chroma sample (i, j)
+ *               sits at luma (2i, 2j + 0.5), the MPEG-2 / H.264 / HEVC default siting.  In: rows 2j, 2j+1 take c[j-1]/4 + 3c[j]/4,
+ *               3c[j]/4 + c[j+1]/4, then even columns c[i], odd columns (c[i] + c[i+1])/2, indices clamped at the frame edges.  Out: the
+ *               mean of the two rows, then [1 2 1]/4 over columns 2i-1, 2i, 2i+1, edge-clamped.
+ * yuv420_to_planar: dst planar fp32 [frames][3 + const_channels][H][W] (the tensor of bsvd_u8_to_planar, trailing channels = const_value):
+ *   R = y + 2(1-Kr) cr, B = y + 2(1-Kb) cb, G = y - (2Kr(1-Kr)/Kg) cr - (2Kb(1-Kb)/Kg) cb.  NOT clamped: the out-of-gamut values of a
+ *   noisy source are information for a denoiser.
+ * planar_to_yuv420: src planar fp32 [frames][3][H][W]: R, G, B clamped to [0,1], Y' = Kr R + Kg G + Kb B, Cb = (B - Y') / 2(1-Kb),
+ *   Cr = (R - Y') / 2(1-Kr), chroma filter, scale to codes, clamp to the legal range (limited: luma [16s, 235s], chroma [16s, 240s]; full:
+ *   [0, 2^b - 1]), round half to even.
+ * Both return -3, naming the argument in bsvd_last_error(), for: a NULL pointer; frames <= 0; H or W <= 0 or not a multiple of 4; an unknown
+ * enum value; reserved != 0; row_pitch below W samples; with P010 a row_pitch / frame_stride that is not a multiple of 2 or a surface
+ * pointer that is not 2-byte aligned; frame_stride below one frame; a planar pointer that is not 16-byte aligned; const_channels < 0.
+ * bsvd_yuv420_frame_bytes: row_pitch * H * 3 / 2 (row_pitch 0 = tight), -1 on bad arguments.
+ */
+enum { BSVD_PIX_NV12 = 0, BSVD_PIX_P010 = 1 };
+enum { BSVD_MATRIX_BT601 = 0, BSVD_MATRIX_BT709 = 1, BSVD_MATRIX_BT2020 = 2 };
+enum { BSVD_CHROMA_NEAREST = 0, BSVD_CHROMA_LINEAR = 1 };
+typedef struct BsvdYuvDesc {
+    int32_t pix_fmt, matrix, full_range, chroma;
+    int32_t row_pitch;      /* bytes; 0 = tight (W samples) */
+    int32_t reserved;       /* must be 0 */
+    int64_t frame_stride;   /* bytes; 0 = tight (row_pitch * H * 3 / 2) */
+} BsvdYuvDesc;
+int64_t bsvd_yuv420_frame_bytes(int32_t H, int32_t W, int32_t pix_fmt, int32_t row_pitch);
+int bsvd_yuv420_to_planar(const void *src, float *dst, int32_t frames, int32_t H, int32_t W, const BsvdYuvDesc *desc,
+                          int32_t const_channels, float const_value, void *stream);
+int bsvd_planar_to_yuv420(const float *src, void *dst, int32_t frames, int32_t H, int32_t W, const BsvdYuvDesc *desc,
+                          void *stream);
+
+/*
  * Frame-window sharding: gathers the channel slice [c0, c0+n) of one NHWC frame into
  * a compact [H*W][n] buffer -- the message a rank sends to its temporal neighbour
  * (first frame, c0 = 0 -> the left neighbour's halo_next; last frame, c0 = fold -> the right

@@ -1,0 +1,86 @@
+#!/usr/bin/env python3
+"""Denoises a raw YUV 4:2:0 stream -- NV12 or P010 frames as any `-f rawvideo` producer pipes them -- through
+bsvd_amd.pipeline.LiveStream(pix_fmt=...): surfaces over PCIe, colour conversion on the device, one graph-replayed pipeline step per
+frame.  Prints one JSON line: frames, frames_per_s (whole run, host to host, file I/O and pipeline fill included), ms_per_feed p50 / p99 and
+steady_frames_per_s (wall clock, reads and writes included) over the steady state, the second half of the feeds.
+
+    python tools/yuv_denoise.py IN OUT --size 1920x1080 --pix-fmt nv12 --sigma 30 [--matrix bt709] [--full-range] [--chroma linear]
+                                [--depth 2] [--ckpt model.pth]                IN / OUT: a file, or - for stdin / stdout
+
+The width and height must be multiples of 4.  Without --ckpt the weights are seeded random ones (rates, not pictures), like
+tools/live_stream.py."""
+import argparse, json, os, sys, time
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+
+
+def read_frames(f, nbytes):
+    while True:
+        raw = f.read(nbytes)
+        if len(raw) < nbytes:                      # end of the stream (a trailing partial frame is dropped)
+            return
+        yield raw
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("input")
+    ap.add_argument("output")
+    ap.add_argument("--size", required=True, help="WxH of the pictures, e.g. 1920x1080")
+    ap.add_argument("--pix-fmt", required=True, choices=["nv12", "p010"])
+    ap.add_argument("--sigma", type=float, required=True, help="noise std in 8-bit code units (e.g. 30)")
+    ap.add_argument("--matrix", default="bt709", choices=["bt601", "bt709", "bt2020"])
+    ap.add_argument("--full-range", action="store_true")
+    ap.add_argument("--chroma", default="linear", choices=["nearest", "linear"])
+    ap.add_argument("--depth", type=int, default=2)
+    ap.add_argument("--ckpt", default=None)
+    ap.add_argument("--precision", default="f16x3")
+    a = ap.parse_args(argv)
+    W, H = map(int, a.size.lower().split("x"))
+    if W <= 0 or H <= 0 or W % 4 or H % 4:
+        ap.error("--size %s: width and height must be positive multiples of 4" % a.size)
+    dtype = np.dtype(np.uint8 if a.pix_fmt == "nv12" else "<u2")
+    nbytes = W * H * 3 // 2 * dtype.itemsize
+
+    import torch
+    import bsvd_amd
+    from bsvd_amd.pipeline import LiveStream
+    torch.manual_seed(1234)
+    m = bsvd_amd.BSVD(chns=[64, 128, 256], mid_ch=64, norm="none", act="relu6", interm_ch=64, pretrain_ckpt=a.ckpt,
+                      precision=a.precision).to(torch.device("cuda", 0)).eval()
+    live = LiveStream(m, sigma=a.sigma / 255.0, depth=a.depth, frame_shape=(H, W), pix_fmt=a.pix_fmt,
+                      colour={"matrix": a.matrix, "full_range": a.full_range, "chroma": a.chroma})
+    fin = sys.stdin.buffer if a.input == "-" else open(a.input, "rb")
+    fout = sys.stdout.buffer if a.output == "-" else open(a.output, "wb")
+    n_in = n_out = 0
+    ms, done = [], []                              # per feed: time inside feed(), clock when its iteration (read, feed, write) ended
+    t0 = time.perf_counter()
+    for raw in read_frames(fin, nbytes):
+        frame = np.frombuffer(raw, dtype).reshape(H * 3 // 2, W)
+        t1 = time.perf_counter()
+        r = live.feed(frame)
+        ms.append((time.perf_counter() - t1) * 1e3)
+        n_in += 1
+        if r is not None:
+            fout.write(r.tobytes())
+            n_out += 1
+        done.append(time.perf_counter())
+    for r in live.flush():
+        fout.write(r.tobytes())
+        n_out += 1
+    fout.flush()
+    total = time.perf_counter() - t0
+    assert n_out == n_in, (n_in, n_out)
+    # steady state: the second half of the feeds, behind the pipeline fill and the first ring cycles' graph captures
+    k = max(live.latency + 1, n_in // 2)
+    steady = np.array(ms[k:] or ms or [0.0])
+    res = {"frames": n_out, "frames_per_s": n_out / total if total > 0 else 0.0,
+           "ms_per_feed": {"p50": float(np.percentile(steady, 50)), "p99": float(np.percentile(steady, 99))},
+           "steady_frames_per_s": (n_in - k) / (done[-1] - done[k - 1]) if n_in > k >= 1 else 0.0,       # wall clock, reads and writes included
+           "size": "%dx%d" % (W, H), "pix_fmt": a.pix_fmt, "depth": a.depth, "frame_latency_feeds": live.latency}
+    print(json.dumps(res), file=sys.stderr if a.output == "-" else sys.stdout, flush=True)
+    return res
+
+
+if __name__ == "__main__":
+    main()
