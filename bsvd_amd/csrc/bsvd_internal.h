@@ -71,8 +71,18 @@ static_assert(offsetof(ConvParams, wino_m) == 272 && offsetof(ConvParams, pre_ou
 // 128-byte EDGE LINE [side 0 | 1][4 quarters] x 16 B: position 0 of the tile's first group resp. position m + 1 of its last group, which need a pixel of
 // the neighbouring tile -- readers take these two values from the edge line (written by the patch pass behind the producer), never from the planes.
 __host__ __device__ constexpr int v_block_floats(int m) { return ((m + 2) * 4 * 8 + 8) * 4; }
+// groups per image row (ceil(W / m) rounded up to 8); floats of a frame's blocks; floats of the producer's edge record behind them
+static inline int v_groups(int W, int m) { return (((W + m - 1) / m) + 7) / 8 * 8; }
+static inline int64_t v_plane_elems(int H, int W, int C, int m) { return (int64_t)H * (v_groups(W, m) / 8) * (C / 16) * v_block_floats(m); }
+static inline int64_t v_edge_elems(int H, int W, int C, int m) { return (int64_t)H * ((W + 8 * m - 1) / (8 * m)) * 4 * C; }
 
 void set_error(const char *fmt, ...);
+
+// the host checks' three recurring questions: a pointer fit for 16-byte vector access; a byte count a kernel may address with 32-bit
+// offsets; a Winograd form F(m, 3) that has a transformed-domain layout and a weight pack
+static inline bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
+static inline bool fits_2gib(int64_t bytes) { return bytes < 0x7fffffffLL; }
+static inline bool wino_m_ok(int m) { return m == 2 || m == 4 || m == 6; }
 
 // grid of the bandwidth-bound helper kernels (grid-stride loops over n items): enough workgroups to fill the chip, capped at 16 per CU
 static inline unsigned grid_for(int64_t n, int block)
@@ -81,6 +91,14 @@ static inline unsigned grid_for(int64_t n, int block)
     if (g > 256 * 16) g = 256 * 16;
     if (g < 1) g = 1;
     return (unsigned)g;
+}
+
+// launch of such a kernel on the caller's stream: a grid-stride sweep over n items, 256 lanes per workgroup
+template <typename K, typename... A>
+static inline int launch_sweep(K kernel, int64_t n, void *stream, A... a)
+{
+    hipLaunchKernelGGL(kernel, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream, a...);
+    return (int)hipGetLastError();
 }
 
 // fp16 range of the split mode.  Every value is carried as hi = fp16(v), lo = fp16(v - hi); a conversion that overflows to +-inf turns

@@ -11,17 +11,14 @@ OUT="${BSVD_OUT:-$ROOT/bsvd_amd/libbsvd_hip.so}"
 # objects live outside the package: build/obj (product), build/obj_ab<i> (tools/build_ab.sh variants)
 OBJ="$ROOT/build/obj${BSVD_OBJ_SUFFIX:-}"
 mkdir -p "$OBJ"
-# the product library: five translation units.  A measurement build (EXTRA_HIPCC_FLAGS contains -DBSVD_MEASURE, tools/build_measure.sh)
-# adds conv3x3_wino.hip (the rejected all-positions-per-wave Winograd kernel) and the variant instantiations of conv3x3_winox.hip
-SRCS="conv3x3_mfma conv3x3_winox conv3x3_edge_f32 bsvd_abi frame_yuv"
-case " ${EXTRA_HIPCC_FLAGS} " in *" -DBSVD_MEASURE"*) SRCS="$SRCS conv3x3_wino";; esac
+. "$HERE/sources.sh"      # BSVD_SRCS, bsvd_src_flags
+SRCS="$BSVD_SRCS"
 pids=()
 for src in $SRCS; do
   if [ ! -f "$OBJ/$src.o" ] || [ "$HERE/$src.hip" -nt "$OBJ/$src.o" ] || \
      [ "$HERE/bsvd_internal.h" -nt "$OBJ/$src.o" ] || [ "$HERE/wino_forms.h" -nt "$OBJ/$src.o" ] || [ "$ROOT/include/bsvd_hip.h" -nt "$OBJ/$src.o" ] || \
      [ "$(cat "$OBJ/$src.flags" 2>/dev/null)" != "$FLAGS" ]; then
-    # conv3x3_winox: no SLP vectorizer (it turns the transform's fma_mix forms into convert + packed-fp32 math, see dec_pair)
-    XF=""; [ "$src" = conv3x3_winox ] && XF="-fno-slp-vectorize"
+    XF="$(bsvd_src_flags $src)"
     ( $HIPCC $FLAGS $XF -c "$HERE/$src.hip" -o "$OBJ/$src.o" && echo "$FLAGS" > "$OBJ/$src.flags" ) &
     pids+=($!)
   fi

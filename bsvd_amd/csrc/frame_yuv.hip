@@ -1,6 +1,6 @@
 // frame_yuv.hip -- YUV 4:2:0 frame I/O on the device (include/bsvd_hip.h, bsvd_yuv420_to_planar / bsvd_planar_to_yuv420): NV12 and P010
 // surfaces, as decoders, capture cards and encoders hand them over, <-> the planar fp32 tensors of the network.  The YUV counterpart of
-// u8_to_planar_kernel / planar_to_u8_kernel (bsvd_abi.hip): helper kernels on the caller's stream, outside the captured graphs.
+// u8_to_planar_kernel / planar_to_u8_kernel (tensor_layout.hip): helper kernels on the caller's stream, outside the captured graphs.
 //
 // Both kernels are bandwidth-bound and the fp32 side carries 8 to 16 times the bytes of the YUV side, so the fp32 side decides the layout
 // of work over lanes: one ITEM is 4 columns x 2 rows of one frame, consecutive lanes take consecutive items of a row pair -- a lane moves one
@@ -219,18 +219,6 @@ static int yuv_check(const char *fn, const void *yuv, const char *yuv_name, cons
     return 0;
 }
 
-template <int PIX, int LINEAR, typename... A>
-static void launch_decode(const YuvGeom &g, hipStream_t st, A... a)
-{
-    hipLaunchKernelGGL((yuv420_to_planar_kernel<PIX, LINEAR>), dim3(grid_for(g.items, 256)), dim3(256), 0, st, a...);
-}
-
-template <int PIX, int LINEAR, typename... A>
-static void launch_encode(const YuvGeom &g, hipStream_t st, A... a)
-{
-    hipLaunchKernelGGL((planar_to_yuv420_kernel<PIX, LINEAR>), dim3(grid_for(g.items, 256)), dim3(256), 0, st, a...);
-}
-
 }  // namespace bsvd
 
 using namespace bsvd;
@@ -265,14 +253,10 @@ int bsvd_yuv420_to_planar(const void *src, float *dst, int32_t frames, int32_t H
     k.g_cr = (float)(2 * kr * (1 - kr) / kg);
     k.g_cb = (float)(2 * kb * (1 - kb) / kg);
     k.b_cb = (float)(2 * (1 - kb));
-    const uint8_t *s8 = (const uint8_t *)src;
-    hipStream_t st = (hipStream_t)stream;
     const int sel = desc->pix_fmt * 2 + desc->chroma;
-    if (sel == 0) launch_decode<BSVD_PIX_NV12, 0>(g, st, s8, dst, H, W, g.pitch, g.fstride, const_channels, const_value, k, g.items);
-    else if (sel == 1) launch_decode<BSVD_PIX_NV12, 1>(g, st, s8, dst, H, W, g.pitch, g.fstride, const_channels, const_value, k, g.items);
-    else if (sel == 2) launch_decode<BSVD_PIX_P010, 0>(g, st, s8, dst, H, W, g.pitch, g.fstride, const_channels, const_value, k, g.items);
-    else launch_decode<BSVD_PIX_P010, 1>(g, st, s8, dst, H, W, g.pitch, g.fstride, const_channels, const_value, k, g.items);
-    return (int)hipGetLastError();
+    static decltype(&yuv420_to_planar_kernel<BSVD_PIX_NV12, 0>) const kernels[4] = {yuv420_to_planar_kernel<BSVD_PIX_NV12, 0>, yuv420_to_planar_kernel<BSVD_PIX_NV12, 1>,
+        yuv420_to_planar_kernel<BSVD_PIX_P010, 0>, yuv420_to_planar_kernel<BSVD_PIX_P010, 1>};
+    return launch_sweep(kernels[sel], g.items, stream, (const uint8_t *)src, dst, H, W, g.pitch, g.fstride, const_channels, const_value, k, g.items);
 }
 
 int bsvd_planar_to_yuv420(const float *src, void *dst, int32_t frames, int32_t H, int32_t W, const BsvdYuvDesc *desc, void *stream)
@@ -294,14 +278,10 @@ int bsvd_planar_to_yuv420(const float *src, void *dst, int32_t frames, int32_t H
     k.y_lo = k.c_lo = desc->full_range ? 0.f : (float)(16 * s);
     k.y_hi = desc->full_range ? (float)top : (float)(235 * s);
     k.c_hi = desc->full_range ? (float)top : (float)(240 * s);
-    uint8_t *d8 = (uint8_t *)dst;
-    hipStream_t st = (hipStream_t)stream;
     const int sel = desc->pix_fmt * 2 + desc->chroma;
-    if (sel == 0) launch_encode<BSVD_PIX_NV12, 0>(g, st, src, d8, H, W, g.pitch, g.fstride, k, g.items);
-    else if (sel == 1) launch_encode<BSVD_PIX_NV12, 1>(g, st, src, d8, H, W, g.pitch, g.fstride, k, g.items);
-    else if (sel == 2) launch_encode<BSVD_PIX_P010, 0>(g, st, src, d8, H, W, g.pitch, g.fstride, k, g.items);
-    else launch_encode<BSVD_PIX_P010, 1>(g, st, src, d8, H, W, g.pitch, g.fstride, k, g.items);
-    return (int)hipGetLastError();
+    static decltype(&planar_to_yuv420_kernel<BSVD_PIX_NV12, 0>) const kernels[4] = {planar_to_yuv420_kernel<BSVD_PIX_NV12, 0>, planar_to_yuv420_kernel<BSVD_PIX_NV12, 1>,
+        planar_to_yuv420_kernel<BSVD_PIX_P010, 0>, planar_to_yuv420_kernel<BSVD_PIX_P010, 1>};
+    return launch_sweep(kernels[sel], g.items, stream, src, (uint8_t *)dst, H, W, g.pitch, g.fstride, k, g.items);
 }
 
 }  // extern "C"

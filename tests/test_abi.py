@@ -155,3 +155,69 @@ def test_workspace_bytes_is_zero_and_validates():
     assert lib.bsvd_workspace_bytes(None) == -1
     assert lib.bsvd_halo_unpack(None, None, 4, 16, 0, 8, 0, None) == -3
     assert lib.bsvd_halo_unpack(16, 16, 4, 16, 12, 8, 0, None) == -3        # c0 + n > C
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# validation replay: tests/golden/abi_replay.json holds what the conv entry answered when the fixture was recorded (tools/abi_replay_gen.py)
+
+REPLAY = os.path.join(ROOT, "tests", "golden", "abi_replay.json")
+# every negative code the conv path can answer through bsvd_conv3x3_variant, read off the source the fixture was recorded from: -1 .. -13
+# and -15 .. -23 of bsvd_abi.hip, with -17 and -19 coming out of the launchers as well (-14 is the fp32 head's launch, never a dry run)
+REPLAY_CODES = set(range(-23, 0)) - {-14}
+
+
+def _replay_args(fx, template, overrides):
+    from bsvd_amd import _lib
+    if overrides.get("_null"):
+        return None
+    a = _lib.BsvdConvArgs()
+    for k, v in dict(fx["base"], **dict(fx["templates"][template], **overrides)).items():
+        if not k.startswith("_"):
+            setattr(a, k, float(v) if isinstance(v, str) else v)       # floats travel as text (inf and nan are no JSON)
+    return a
+
+
+def test_validation_replay():
+    """Return code, bsvd_last_error() text and dry-run name of every recorded BsvdConvArgs: byte for byte what the fixture holds."""
+    import json
+    from bsvd_amd import _lib
+    lib = _lib.load()
+    fx = json.load(open(REPLAY))
+    assert len(fx["cases"]) >= 2000
+    buf = ctypes.create_string_buffer(96)
+    codes, wrong = set(), []
+    for template, overrides, oi in fx["cases"]:
+        rc_exp, err_exp, name_exp = fx["outcomes"][oi]
+        a = _replay_args(fx, template, overrides)
+        name_len = overrides.get("_name_len", 96)
+        buf.value = b"?"
+        rc = lib.bsvd_conv3x3_variant(ctypes.byref(a) if a is not None else None, buf, name_len)
+        got = [rc, lib.bsvd_last_error().decode() if rc < 0 else "", buf.value.decode() if name_len >= 8 else ""]
+        if got != [rc_exp, err_exp, name_exp]:
+            wrong.append((template, overrides, got, fx["outcomes"][oi]))
+        codes.add(rc_exp)
+    assert not wrong, "%d of %d cases differ, first: %r" % (len(wrong), len(fx["cases"]), wrong[:3])
+    assert {c for c in codes if c < 0} == REPLAY_CODES and 0 in codes
+    launcher = {(o[0], o[1].split(":")[1].strip()[:12]) for o in fx["outcomes"] if o[0] in (-17, -19)}
+    assert (-17, "BSVD_F16X3 n") in launcher and (-19, "y_v is not a") in launcher      # ... and the launchers' own refusals are among them
+
+
+@pytest.mark.gpu
+def test_batch_replay_names_the_failing_layer():
+    """bsvd_conv3x3_batch with a bad second element: the first one is launched (on real tensors), the message names layer 1 of 2."""
+    import json
+    import torch
+    from bsvd_amd import _lib
+    lib = _lib.load()
+    fx = json.load(open(REPLAY))
+    rec = fx["batch"]
+    x, w, y = (torch.zeros(n, device="cuda") for n in (8 * 8 * 16, 16 * 9 * 16, 8 * 8 * 16))
+    arr = (_lib.BsvdConvArgs * 2)()
+    for a, ov in zip(arr, rec["args"]):
+        for k, v in dict(fx["base"], **ov).items():
+            setattr(a, k, v)
+        a.x, a.w_packed, a.y = x.data_ptr(), w.data_ptr(), y.data_ptr()
+    rc = lib.bsvd_conv3x3_batch(arr, 2, None)
+    torch.cuda.synchronize()
+    assert (rc, lib.bsvd_last_error().decode()) == (rec["rc"], rec["error"])
+    assert rec["rc"] < 0 and rec["error"].startswith("bsvd_conv3x3_batch: layer 1 of 2: bsvd_conv3x3: ")

@@ -8,11 +8,11 @@
 # reorders the kernels of a translation unit (the whole-file digest still sees the order).
 ROOT="$(cd "$(dirname "$0")/.." && pwd)"
 OUT=$(mktemp -d)
-SRCS="conv3x3_mfma conv3x3_winox conv3x3_edge_f32 bsvd_abi"
-case " ${EXTRA_HIPCC_FLAGS} " in *" -DBSVD_MEASURE"*) SRCS="$SRCS conv3x3_wino";; esac      # measurement builds only (bsvd_amd/csrc/build.sh)
+. "$ROOT/bsvd_amd/csrc/sources.sh"      # BSVD_SRCS, bsvd_src_flags: the list bsvd_amd/csrc/build.sh builds
+SRCS="$BSVD_SRCS"
 [ $# -gt 0 ] && SRCS="$*"
 for src in $SRCS; do
-  XF=""; [ "$src" = conv3x3_winox ] && XF="-fno-slp-vectorize"
+  XF="$(bsvd_src_flags $src)"
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -I$ROOT/include -I$ROOT/bsvd_amd/csrc -Wno-unused-function \
      $XF ${EXTRA_HIPCC_FLAGS} --cuda-device-only -S $ROOT/bsvd_amd/csrc/$src.hip -o $OUT/$src.s 2> $OUT/$src.log &
 done

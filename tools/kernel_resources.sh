@@ -3,10 +3,10 @@
 # usage: [EXTRA_HIPCC_FLAGS=...] tools/kernel_resources.sh   -> builds into a scratch object dir, prints one line per kernel
 ROOT="$(cd "$(dirname "$0")/.." && pwd)"
 OUT=$(mktemp -d)
-SRCS="conv3x3_mfma conv3x3_winox conv3x3_edge_f32 bsvd_abi"
-case " ${EXTRA_HIPCC_FLAGS} " in *" -DBSVD_MEASURE"*) SRCS="$SRCS conv3x3_wino";; esac      # measurement builds only (bsvd_amd/csrc/build.sh)
+. "$ROOT/bsvd_amd/csrc/sources.sh"      # BSVD_SRCS, bsvd_src_flags: the list bsvd_amd/csrc/build.sh builds
+SRCS="$BSVD_SRCS"
 for src in $SRCS; do
-  XF=""; [ "$src" = conv3x3_winox ] && XF="-fno-slp-vectorize"
+  XF="$(bsvd_src_flags $src)"
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -I$ROOT/include -I$ROOT/bsvd_amd/csrc -Wno-unused-function \
      $XF ${EXTRA_HIPCC_FLAGS} -Rpass-analysis=kernel-resource-usage -c $ROOT/bsvd_amd/csrc/$src.hip -o $OUT/$src.o 2> $OUT/$src.log &
 done
