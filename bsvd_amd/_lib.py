@@ -21,7 +21,9 @@ EXPORTS = ("bsvd_abi_version", "bsvd_conv_args_size", "bsvd_build_info", "bsvd_l
            "bsvd_u8_to_planar", "bsvd_planar_to_u8", "bsvd_conv3x3_batch", "bsvd_graph_begin", "bsvd_graph_fork",
            "bsvd_graph_join", "bsvd_graph_end", "bsvd_graph_abort", "bsvd_graph_launch", "bsvd_graph_destroy",
            "bsvd_v_frame_elems", "bsvd_v_groups", "bsvd_to_v",
-           "bsvd_yuv420_frame_bytes", "bsvd_yuv420_to_planar", "bsvd_planar_to_yuv420")
+           "bsvd_yuv420_frame_bytes", "bsvd_yuv420_to_planar", "bsvd_planar_to_yuv420",
+           "bsvd_u8_to_planar_pad", "bsvd_planar_to_u8_crop", "bsvd_yuv420_picture_bytes", "bsvd_yuv420_to_planar_pad",
+           "bsvd_planar_to_yuv420_crop")
 PIX_FMT = {"nv12": 0, "p010": 1}
 MATRIX = {"bt601": 0, "bt709": 1, "bt2020": 2}
 CHROMA = {"nearest": 0, "linear": 1}
@@ -150,6 +152,16 @@ def load():
     lib.bsvd_yuv420_to_planar.argtypes = [vp, vp, i32, i32, i32, ctypes.POINTER(BsvdYuvDesc), i32, f32, vp]
     lib.bsvd_planar_to_yuv420.restype = ctypes.c_int
     lib.bsvd_planar_to_yuv420.argtypes = [vp, vp, i32, i32, i32, ctypes.POINTER(BsvdYuvDesc), vp]
+    lib.bsvd_u8_to_planar_pad.restype = ctypes.c_int
+    lib.bsvd_u8_to_planar_pad.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, f32, vp]
+    lib.bsvd_planar_to_u8_crop.restype = ctypes.c_int
+    lib.bsvd_planar_to_u8_crop.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]
+    lib.bsvd_yuv420_picture_bytes.restype = i64
+    lib.bsvd_yuv420_picture_bytes.argtypes = [i32, i32, i32, i32]
+    lib.bsvd_yuv420_to_planar_pad.restype = ctypes.c_int
+    lib.bsvd_yuv420_to_planar_pad.argtypes = [vp, vp, i32, i32, i32, i32, i32, ctypes.POINTER(BsvdYuvDesc), i32, f32, vp]
+    lib.bsvd_planar_to_yuv420_crop.restype = ctypes.c_int
+    lib.bsvd_planar_to_yuv420_crop.argtypes = [vp, vp, i32, i32, i32, i32, i32, ctypes.POINTER(BsvdYuvDesc), vp]
     lib.bsvd_workspace_bytes.restype = i64
     lib.bsvd_workspace_bytes.argtypes = [ctypes.POINTER(BsvdConvArgs)]
     if lib.bsvd_abi_version() != ABI_VERSION:

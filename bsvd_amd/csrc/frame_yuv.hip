@@ -8,33 +8,9 @@
 // the YUV side an item is one group of 4 Y samples per row and the 2 CbCr pairs under them (4 + 4 + 4 bytes with NV12, 8 + 8 + 8 with
 // P010), each read or written once, as a whole, by this lane alone.
 #include "bsvd_internal.h"
+#include "frame_items.h"      // Pix, load_codes / store_codes, YuvDecode / YuvEncode; the item bodies of the pad / crop kernels
 
 namespace bsvd {
-
-template <int PIX> struct Pix;
-template <> struct Pix<BSVD_PIX_NV12> { using S = uint8_t;  static constexpr int SHIFT = 0; };
-template <> struct Pix<BSVD_PIX_P010> { using S = uint16_t; static constexpr int SHIFT = 6; };   // 10-bit code in the high bits of the word
-
-// N consecutive samples of a surface row.  A surface promises no more than its sample's own alignment (pitch and base are the caller's),
-// hence the memcpy: one load / store of the group's width, legal at any sample-aligned address.
-template <int PIX, int N>
-__device__ __forceinline__ void load_codes(const uint8_t *p, float *out)
-{
-    typename Pix<PIX>::S v[N];
-    __builtin_memcpy(v, __builtin_assume_aligned(p, sizeof(v[0])), sizeof(v));
-#pragma unroll
-    for (int k = 0; k < N; ++k) out[k] = (float)(v[k] >> Pix<PIX>::SHIFT);
-}
-
-// scaled values -> legal codes (clamp, round half to even like planar_to_u8_kernel) -> 4 samples in one store
-template <int PIX>
-__device__ __forceinline__ void store_codes(uint8_t *p, const float *val, float lo, float hi)
-{
-    typename Pix<PIX>::S v[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) v[k] = (typename Pix<PIX>::S)((unsigned)rintf(fminf(fmaxf(val[k], lo), hi)) << Pix<PIX>::SHIFT);
-    __builtin_memcpy(__builtin_assume_aligned(p, sizeof(v[0])), v, sizeof(v));
-}
 
 // item index -> frame, chroma row j (luma rows 2j, 2j + 1), first column x0.  Items of one frame fit 32 bits (checked by the host).
 struct Item { int64_t f; int j, x0; };
@@ -49,9 +25,6 @@ __device__ __forceinline__ Item item_of(int64_t i, int64_t per_frame, int wq)
 }
 
 // ---------------------------------------------------------------------------------------------
-// decode: codes -> (Y - y_off) * y_mul, (C - c_off) * c_mul -> R = y + r_cr cr, G = y - g_cr cr - g_cb cb, B = y + b_cb cb.  NOT clamped.
-struct YuvDecode { float y_off, y_mul, c_off, c_mul, r_cr, g_cr, g_cb, b_cb; };
-
 template <int PIX, int LINEAR>
 __global__ __launch_bounds__(256) void yuv420_to_planar_kernel(const uint8_t *__restrict__ src, float *__restrict__ dst, int H, int W, int64_t pitch,
                                                                int64_t fstride, int cc, float const_val, YuvDecode k, int64_t items)
@@ -117,12 +90,7 @@ __global__ __launch_bounds__(256) void yuv420_to_planar_kernel(const uint8_t *__
 }
 
 // ---------------------------------------------------------------------------------------------
-// encode: clamp RGB to [0,1] -> Y' = kr R + kg G + kb B, B - Y', R - Y' -> chroma filter on the differences (it is linear; cb_mul / cr_mul
-// carry the 1 / (2 (1 - K)) of Cb / Cr with the code scale) -> scale + offset -> clamp to the legal codes -> rintf
-struct YuvEncode { float kr, kg, kb, y_mul, y_off, cb_mul, cr_mul, c_off, y_lo, y_hi, c_lo, c_hi; };
-
-__device__ __forceinline__ float clamp01(float v) { return fminf(fmaxf(v, 0.f), 1.f); }
-
+// encode (YuvEncode, frame_items.h)
 template <int PIX, int LINEAR>
 __global__ __launch_bounds__(256) void planar_to_yuv420_kernel(const float *__restrict__ src, uint8_t *__restrict__ dst, int H, int W, int64_t pitch,
                                                                int64_t fstride, YuvEncode k, int64_t items)
@@ -179,6 +147,23 @@ __global__ __launch_bounds__(256) void planar_to_yuv420_kernel(const float *__re
 }
 
 // ---------------------------------------------------------------------------------------------
+// pad / crop (bsvd_yuv420_to_planar_pad / bsvd_planar_to_yuv420_crop): the same work shape over the PICTURE's items; the bodies, with the
+// half item of W % 4 == 2 and the mirror images of the pad region, are in frame_items.h
+template <int PIX, int LINEAR>
+__global__ __launch_bounds__(256) void yuv420_to_planar_pad_kernel(const uint8_t *__restrict__ src, float *__restrict__ dst, YuvPadGeom g, YuvDecode k, int64_t items)
+{
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < items; i += (int64_t)gridDim.x * blockDim.x)
+        yuv420_to_planar_pad_item<PIX, LINEAR>(src, dst, g, k, i);
+}
+
+template <int PIX, int LINEAR>
+__global__ __launch_bounds__(256) void planar_to_yuv420_crop_kernel(const float *__restrict__ src, uint8_t *__restrict__ dst, YuvPadGeom g, YuvEncode k, int64_t items)
+{
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < items; i += (int64_t)gridDim.x * blockDim.x)
+        planar_to_yuv420_crop_item<PIX, LINEAR>(src, dst, g, k, i);
+}
+
+// ---------------------------------------------------------------------------------------------
 // host side: validation (no device needed), constants in double, dispatch
 static const double kMatrix[3][2] = {{0.299, 0.114}, {0.2126, 0.0722}, {0.2627, 0.0593}};   // (Kr, Kb): BT.601, BT.709, BT.2020 ncl
 
@@ -186,15 +171,28 @@ struct YuvGeom { int64_t pitch, fstride, items; };
 
 static inline int sample_bytes(int pix_fmt) { return pix_fmt == BSVD_PIX_P010 ? 2 : 1; }
 
+// H x W is the surface's picture.  pad == 0: the plain entry points, H and W multiples of 4.  pad != 0: the pad / crop entry points, H and W
+// even, the planar tensor Hp x Wp.
 static int yuv_check(const char *fn, const void *yuv, const char *yuv_name, const float *planar, const char *planar_name, int32_t frames, int32_t H,
-                     int32_t W, const BsvdYuvDesc *d, YuvGeom *g)
+                     int32_t W, const BsvdYuvDesc *d, YuvGeom *g, int pad = 0, int32_t Hp = 0, int32_t Wp = 0)
 {
     if (!yuv) { set_error("%s: %s is NULL", fn, yuv_name); return -3; }
     if (!planar) { set_error("%s: %s is NULL", fn, planar_name); return -3; }
     if (!d) { set_error("%s: desc is NULL", fn); return -3; }
     if (frames <= 0) { set_error("%s: frames = %d must be positive", fn, frames); return -3; }
-    if (H <= 0 || (H & 3)) { set_error("%s: H = %d must be a positive multiple of 4", fn, H); return -3; }
-    if (W <= 0 || (W & 3)) { set_error("%s: W = %d must be a positive multiple of 4", fn, W); return -3; }
+    if (!pad) {
+        if (H <= 0 || (H & 3)) { set_error("%s: H = %d must be a positive multiple of 4", fn, H); return -3; }
+        if (W <= 0 || (W & 3)) { set_error("%s: W = %d must be a positive multiple of 4", fn, W); return -3; }
+    } else {
+        if (H <= 0 || (H & 1)) { set_error("%s: H = %d must be positive and even (4:2:0)", fn, H); return -3; }
+        if (W <= 0 || (W & 1)) { set_error("%s: W = %d must be positive and even (4:2:0)", fn, W); return -3; }
+        if (Hp < H) { set_error("%s: Hp = %d is below H = %d", fn, Hp, H); return -3; }
+        if (Wp < W) { set_error("%s: Wp = %d is below W = %d", fn, Wp, W); return -3; }
+        if (Hp - H >= H) { set_error("%s: Hp = %d pads H = %d by a whole dimension or more (reflect is defined up to 2 H - 1)", fn, Hp, H); return -3; }
+        if (Wp - W >= W) { set_error("%s: Wp = %d pads W = %d by a whole dimension or more (reflect is defined up to 2 W - 1)", fn, Wp, W); return -3; }
+        if (Hp & 1) { set_error("%s: Hp = %d must be even", fn, Hp); return -3; }
+        if (Wp & 3) { set_error("%s: Wp = %d must be a multiple of 4 (rows move as float4)", fn, Wp); return -3; }
+    }
     if (d->pix_fmt != BSVD_PIX_NV12 && d->pix_fmt != BSVD_PIX_P010) { set_error("%s: desc->pix_fmt = %d (BSVD_PIX_NV12, BSVD_PIX_P010)", fn, d->pix_fmt); return -3; }
     if (d->matrix < BSVD_MATRIX_BT601 || d->matrix > BSVD_MATRIX_BT2020) { set_error("%s: desc->matrix = %d (BSVD_MATRIX_BT601 .. BT2020)", fn, d->matrix); return -3; }
     if (d->full_range != 0 && d->full_range != 1) { set_error("%s: desc->full_range = %d (0 or 1)", fn, d->full_range); return -3; }
@@ -213,34 +211,14 @@ static int yuv_check(const char *fn, const void *yuv, const char *yuv_name, cons
         if ((uintptr_t)yuv & 1) { set_error("%s: %s must be 2-byte aligned with BSVD_PIX_P010", fn, yuv_name); return -3; }
     }
     if ((uintptr_t)planar & 15) { set_error("%s: %s must be 16-byte aligned (rows move as float4)", fn, planar_name); return -3; }
-    const int64_t per_frame = (int64_t)(H / 2) * (W / 4);
+    const int64_t per_frame = (int64_t)(H / 2) * (pad ? items_per_row(W) : W / 4);
     if (per_frame > 0x7fffffff) { set_error("%s: H x W = %d x %d: more than 2^31 items per frame", fn, H, W); return -3; }
     g->items = per_frame * frames;
     return 0;
 }
 
-}  // namespace bsvd
-
-using namespace bsvd;
-
-extern "C" {
-
-int64_t bsvd_yuv420_frame_bytes(int32_t H, int32_t W, int32_t pix_fmt, int32_t row_pitch)
+static YuvDecode decode_constants(const BsvdYuvDesc *desc)
 {
-    if (H <= 0 || W <= 0 || (H & 3) || (W & 3) || (pix_fmt != BSVD_PIX_NV12 && pix_fmt != BSVD_PIX_P010) || row_pitch < 0) return -1;
-    const int sb = sample_bytes(pix_fmt);
-    const int64_t pitch = row_pitch ? row_pitch : (int64_t)W * sb;
-    if (pitch < (int64_t)W * sb || (pitch & (sb - 1))) return -1;
-    return pitch * H / 2 * 3;
-}
-
-int bsvd_yuv420_to_planar(const void *src, float *dst, int32_t frames, int32_t H, int32_t W, const BsvdYuvDesc *desc, int32_t const_channels,
-                          float const_value, void *stream)
-{
-    YuvGeom g;
-    const int rc = yuv_check("bsvd_yuv420_to_planar", src, "src", dst, "dst", frames, H, W, desc, &g);
-    if (rc) return rc;
-    if (const_channels < 0) { set_error("bsvd_yuv420_to_planar: const_channels = %d must not be negative", const_channels); return -3; }
     const int bits = desc->pix_fmt == BSVD_PIX_P010 ? 10 : 8;
     const double s = (double)(1 << (bits - 8)), top = (double)((1 << bits) - 1);
     const double kr = kMatrix[desc->matrix][0], kb = kMatrix[desc->matrix][1], kg = 1.0 - kr - kb;
@@ -253,17 +231,11 @@ int bsvd_yuv420_to_planar(const void *src, float *dst, int32_t frames, int32_t H
     k.g_cr = (float)(2 * kr * (1 - kr) / kg);
     k.g_cb = (float)(2 * kb * (1 - kb) / kg);
     k.b_cb = (float)(2 * (1 - kb));
-    const int sel = desc->pix_fmt * 2 + desc->chroma;
-    static decltype(&yuv420_to_planar_kernel<BSVD_PIX_NV12, 0>) const kernels[4] = {yuv420_to_planar_kernel<BSVD_PIX_NV12, 0>, yuv420_to_planar_kernel<BSVD_PIX_NV12, 1>,
-        yuv420_to_planar_kernel<BSVD_PIX_P010, 0>, yuv420_to_planar_kernel<BSVD_PIX_P010, 1>};
-    return launch_sweep(kernels[sel], g.items, stream, (const uint8_t *)src, dst, H, W, g.pitch, g.fstride, const_channels, const_value, k, g.items);
+    return k;
 }
 
-int bsvd_planar_to_yuv420(const float *src, void *dst, int32_t frames, int32_t H, int32_t W, const BsvdYuvDesc *desc, void *stream)
+static YuvEncode encode_constants(const BsvdYuvDesc *desc)
 {
-    YuvGeom g;
-    const int rc = yuv_check("bsvd_planar_to_yuv420", dst, "dst", src, "src", frames, H, W, desc, &g);
-    if (rc) return rc;
     const int bits = desc->pix_fmt == BSVD_PIX_P010 ? 10 : 8;
     const double s = (double)(1 << (bits - 8)), top = (double)((1 << bits) - 1);
     const double kr = kMatrix[desc->matrix][0], kb = kMatrix[desc->matrix][1], kg = 1.0 - kr - kb;
@@ -278,10 +250,78 @@ int bsvd_planar_to_yuv420(const float *src, void *dst, int32_t frames, int32_t H
     k.y_lo = k.c_lo = desc->full_range ? 0.f : (float)(16 * s);
     k.y_hi = desc->full_range ? (float)top : (float)(235 * s);
     k.c_hi = desc->full_range ? (float)top : (float)(240 * s);
+    return k;
+}
+
+static int64_t yuv_bytes(int32_t H, int32_t W, int32_t pix_fmt, int32_t row_pitch, int mask)
+{
+    if (H <= 0 || W <= 0 || (H & mask) || (W & mask) || (pix_fmt != BSVD_PIX_NV12 && pix_fmt != BSVD_PIX_P010) || row_pitch < 0) return -1;
+    const int sb = sample_bytes(pix_fmt);
+    const int64_t pitch = row_pitch ? row_pitch : (int64_t)W * sb;
+    if (pitch < (int64_t)W * sb || (pitch & (sb - 1))) return -1;
+    return pitch * H / 2 * 3;
+}
+
+}  // namespace bsvd
+
+using namespace bsvd;
+
+extern "C" {
+
+int64_t bsvd_yuv420_frame_bytes(int32_t H, int32_t W, int32_t pix_fmt, int32_t row_pitch) { return yuv_bytes(H, W, pix_fmt, row_pitch, 3); }
+int64_t bsvd_yuv420_picture_bytes(int32_t H, int32_t W, int32_t pix_fmt, int32_t row_pitch) { return yuv_bytes(H, W, pix_fmt, row_pitch, 1); }
+
+int bsvd_yuv420_to_planar(const void *src, float *dst, int32_t frames, int32_t H, int32_t W, const BsvdYuvDesc *desc, int32_t const_channels,
+                          float const_value, void *stream)
+{
+    YuvGeom g;
+    const int rc = yuv_check("bsvd_yuv420_to_planar", src, "src", dst, "dst", frames, H, W, desc, &g);
+    if (rc) return rc;
+    if (const_channels < 0) { set_error("bsvd_yuv420_to_planar: const_channels = %d must not be negative", const_channels); return -3; }
+    const YuvDecode k = decode_constants(desc);
+    const int sel = desc->pix_fmt * 2 + desc->chroma;
+    static decltype(&yuv420_to_planar_kernel<BSVD_PIX_NV12, 0>) const kernels[4] = {yuv420_to_planar_kernel<BSVD_PIX_NV12, 0>, yuv420_to_planar_kernel<BSVD_PIX_NV12, 1>,
+        yuv420_to_planar_kernel<BSVD_PIX_P010, 0>, yuv420_to_planar_kernel<BSVD_PIX_P010, 1>};
+    return launch_sweep(kernels[sel], g.items, stream, (const uint8_t *)src, dst, H, W, g.pitch, g.fstride, const_channels, const_value, k, g.items);
+}
+
+int bsvd_planar_to_yuv420(const float *src, void *dst, int32_t frames, int32_t H, int32_t W, const BsvdYuvDesc *desc, void *stream)
+{
+    YuvGeom g;
+    const int rc = yuv_check("bsvd_planar_to_yuv420", dst, "dst", src, "src", frames, H, W, desc, &g);
+    if (rc) return rc;
+    const YuvEncode k = encode_constants(desc);
     const int sel = desc->pix_fmt * 2 + desc->chroma;
     static decltype(&planar_to_yuv420_kernel<BSVD_PIX_NV12, 0>) const kernels[4] = {planar_to_yuv420_kernel<BSVD_PIX_NV12, 0>, planar_to_yuv420_kernel<BSVD_PIX_NV12, 1>,
         planar_to_yuv420_kernel<BSVD_PIX_P010, 0>, planar_to_yuv420_kernel<BSVD_PIX_P010, 1>};
     return launch_sweep(kernels[sel], g.items, stream, src, (uint8_t *)dst, H, W, g.pitch, g.fstride, k, g.items);
+}
+
+int bsvd_yuv420_to_planar_pad(const void *src, float *dst, int32_t frames, int32_t H, int32_t W, int32_t Hp, int32_t Wp, const BsvdYuvDesc *desc,
+                              int32_t const_channels, float const_value, void *stream)
+{
+    YuvGeom g;
+    const int rc = yuv_check("bsvd_yuv420_to_planar_pad", src, "src", dst, "dst", frames, H, W, desc, &g, 1, Hp, Wp);
+    if (rc) return rc;
+    if (const_channels < 0) { set_error("bsvd_yuv420_to_planar_pad: const_channels = %d must not be negative", const_channels); return -3; }
+    const YuvPadGeom pg = {H, W, Hp, Wp, const_channels, g.pitch, g.fstride, const_value};
+    const int sel = desc->pix_fmt * 2 + desc->chroma;
+    static decltype(&yuv420_to_planar_pad_kernel<BSVD_PIX_NV12, 0>) const kernels[4] = {yuv420_to_planar_pad_kernel<BSVD_PIX_NV12, 0>, yuv420_to_planar_pad_kernel<BSVD_PIX_NV12, 1>,
+        yuv420_to_planar_pad_kernel<BSVD_PIX_P010, 0>, yuv420_to_planar_pad_kernel<BSVD_PIX_P010, 1>};
+    return launch_sweep(kernels[sel], g.items, stream, (const uint8_t *)src, dst, pg, decode_constants(desc), g.items);
+}
+
+int bsvd_planar_to_yuv420_crop(const float *src, void *dst, int32_t frames, int32_t Hp, int32_t Wp, int32_t H, int32_t W, const BsvdYuvDesc *desc,
+                               void *stream)
+{
+    YuvGeom g;
+    const int rc = yuv_check("bsvd_planar_to_yuv420_crop", dst, "dst", src, "src", frames, H, W, desc, &g, 1, Hp, Wp);
+    if (rc) return rc;
+    const YuvPadGeom pg = {H, W, Hp, Wp, 0, g.pitch, g.fstride, 0.f};
+    const int sel = desc->pix_fmt * 2 + desc->chroma;
+    static decltype(&planar_to_yuv420_crop_kernel<BSVD_PIX_NV12, 0>) const kernels[4] = {planar_to_yuv420_crop_kernel<BSVD_PIX_NV12, 0>, planar_to_yuv420_crop_kernel<BSVD_PIX_NV12, 1>,
+        planar_to_yuv420_crop_kernel<BSVD_PIX_P010, 0>, planar_to_yuv420_crop_kernel<BSVD_PIX_P010, 1>};
+    return launch_sweep(kernels[sel], g.items, stream, src, (uint8_t *)dst, pg, encode_constants(desc), g.items);
 }
 
 }  // extern "C"

@@ -2,6 +2,7 @@
 // frame I/O, halo slices for frame-window sharding, and the transformed-domain tensors of the Winograd form (bsvd_to_v and its sizes).
 #include <math.h>
 #include "bsvd_internal.h"
+#include "frame_items.h"      // the item bodies of the pad / crop uint8 kernels
 #include "wino_forms.h"
 
 namespace bsvd {
@@ -86,7 +87,6 @@ __global__ void planar_to_u8_kernel(const float *__restrict__ src, uint8_t *__re
     }
 }
 
-
 // bsvd_to_v: one thread per (frame, row, group, 8-channel block): the A = M + 2 pixels of the group (zero outside the image), BT per channel in
 // fp32 (the kernels' WinoForm<M>::input), every transformed value split into an fp16 pair with the kernels' saturating conversions
 template <int M>
@@ -152,6 +152,18 @@ __global__ void to_v_kernel(const float *__restrict__ x, int64_t x_fs, int x_f32
     }
 }
 
+// u8_to_planar_kernel / planar_to_u8_kernel with reflect pad / crop (bsvd_u8_to_planar_pad / bsvd_planar_to_u8_crop) in the YUV kernels' shape: an item is 4 columns of a
+// picture row, one float4 per plane on the fp32 side, one group of bytes on the uint8 side (frame_items.h)
+__global__ __launch_bounds__(256) void u8_to_planar_pad_kernel(const uint8_t *__restrict__ src, float *__restrict__ dst, U8Geom g, int64_t items)
+{
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < items; i += (int64_t)gridDim.x * blockDim.x) u8_to_planar_pad_item(src, dst, g, i);
+}
+
+__global__ __launch_bounds__(256) void planar_to_u8_crop_kernel(const float *__restrict__ src, uint8_t *__restrict__ dst, U8Geom g, int64_t items)
+{
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < items; i += (int64_t)gridDim.x * blockDim.x) planar_to_u8_crop_item(src, dst, g, i);
+}
+
 // bsvd_halo_pack / bsvd_halo_unpack: one check, one copy in either direction
 static int halo_copy(const void *frame, const void *slice, int32_t HW, int32_t C, int32_t c0, int32_t n, int32_t dtype, int unpack, void *stream)
 {
@@ -163,6 +175,24 @@ static int halo_copy(const void *frame, const void *slice, int32_t HW, int32_t C
     // half-chunk slice of a split16 frame (whole chunks are plain float ranges: use BSVD_F32)
     if (n != 8 || (c0 & 7) || (C & 15)) { set_error("bsvd_halo_%s: BSVD_F16X3 %ss one 8-channel half chunk (n == 8, c0 %% 8 == 0)", verb, verb); return -3; }
     return launch_sweep(halo_pack_split8_kernel, 2 * (int64_t)HW, stream, (const float *)f, s, (int64_t)HW, C, c0, unpack);
+}
+
+// the checks of bsvd_u8_to_planar_pad / bsvd_planar_to_u8_crop: picture H x W, tensor Hp x Wp -> items (negative: refused)
+static int64_t u8_pad_check(const char *fn, const void *src, const void *dst, int32_t frames, int32_t C, int32_t H, int32_t W, int32_t Hp, int32_t Wp)
+{
+    if (!src) { set_error("%s: src is NULL", fn); return -3; }
+    if (!dst) { set_error("%s: dst is NULL", fn); return -3; }
+    if (frames <= 0) { set_error("%s: frames = %d must be positive", fn, frames); return -3; }
+    if (C <= 0) { set_error("%s: C = %d must be positive", fn, C); return -3; }
+    if (H <= 0) { set_error("%s: H = %d must be positive", fn, H); return -3; }
+    if (W <= 0) { set_error("%s: W = %d must be positive", fn, W); return -3; }
+    if (Hp < H) { set_error("%s: Hp = %d is below H = %d", fn, Hp, H); return -3; }
+    if (Wp < W) { set_error("%s: Wp = %d is below W = %d", fn, Wp, W); return -3; }
+    if (Hp - H >= H) { set_error("%s: Hp = %d pads H = %d by a whole dimension or more (reflect is defined up to 2 H - 1)", fn, Hp, H); return -3; }
+    if (Wp - W >= W) { set_error("%s: Wp = %d pads W = %d by a whole dimension or more (reflect is defined up to 2 W - 1)", fn, Wp, W); return -3; }
+    const int64_t per_frame = (int64_t)H * items_per_row(W);
+    if (per_frame > 0x7fffffff) { set_error("%s: H x W = %d x %d: more than 2^31 items per frame", fn, H, W); return -3; }
+    return per_frame * frames;
 }
 
 }  // namespace bsvd
@@ -199,6 +229,25 @@ int bsvd_planar_to_u8(const float *src, uint8_t *dst, int32_t frames, int32_t C,
     if (!src || !dst || frames <= 0 || C <= 0 || H <= 0 || W <= 0) { set_error("bsvd_planar_to_u8: bad arguments"); return -3; }
     const int64_t total = (int64_t)frames * C * H * W;
     return launch_sweep(planar_to_u8_kernel, total, stream, src, dst, C, H * W, dst_hwc ? 1 : 0, reverse_channels ? 1 : 0, total);
+}
+
+int bsvd_u8_to_planar_pad(const uint8_t *src, float *dst, int32_t frames, int32_t C, int32_t H, int32_t W, int32_t Hp, int32_t Wp, int32_t src_hwc,
+                          int32_t const_channels, float const_val, void *stream)
+{
+    const int64_t items = u8_pad_check("bsvd_u8_to_planar_pad", src, dst, frames, C, H, W, Hp, Wp);
+    if (items < 0) return (int)items;
+    if (const_channels < 0) { set_error("bsvd_u8_to_planar_pad: const_channels = %d must not be negative", const_channels); return -3; }
+    const U8Geom g = {C, const_channels, H, W, Hp, Wp, src_hwc ? 1 : 0, 0, (Wp & 3) == 0 && aligned16(dst), const_val};
+    return launch_sweep(u8_to_planar_pad_kernel, items, stream, src, dst, g, items);
+}
+
+int bsvd_planar_to_u8_crop(const float *src, uint8_t *dst, int32_t frames, int32_t C, int32_t Hp, int32_t Wp, int32_t H, int32_t W, int32_t dst_hwc,
+                           int32_t reverse_channels, void *stream)
+{
+    const int64_t items = u8_pad_check("bsvd_planar_to_u8_crop", src, dst, frames, C, H, W, Hp, Wp);
+    if (items < 0) return (int)items;
+    const U8Geom g = {C, 0, H, W, Hp, Wp, dst_hwc ? 1 : 0, reverse_channels ? 1 : 0, (Wp & 3) == 0 && aligned16(src), 0.f};
+    return launch_sweep(planar_to_u8_crop_kernel, items, stream, src, dst, g, items);
 }
 
 int bsvd_halo_pack(const void *frame, void *dst, int32_t HW, int32_t C, int32_t c0, int32_t n, int32_t dtype, void *stream) { return halo_copy(frame, dst, HW, C, c0, n, dtype, 0, stream); }

@@ -5,7 +5,12 @@ reference's clamp + round (``tensor2img``, /root/reference/BasicSR/basicsr/utils
 
 The same two steps for YUV 4:2:0 surfaces (NV12, P010), the formats decoders, capture cards and encoders speak:
 ``yuv420_to_input`` / ``output_to_yuv420`` (include/bsvd_hip.h, bsvd_yuv420_to_planar / bsvd_planar_to_yuv420; 1.5 or 3 bytes per
-pixel over PCIe instead of RGB24's 3, and no colour conversion on the host)."""
+pixel over PCIe instead of RGB24's 3, and no colour conversion on the host).
+
+Any picture size: the network needs H and W to be multiples of 4, and the reference's callers reflect-pad the fp32 tensor on the right and
+bottom and crop the result (``denoise.pad_to_multiple_of_4`` / ``crop_padding`` here).  ``pad_to=(Hp, Wp)`` on the way in and
+``crop_to=(H, W)`` on the way out do both inside the conversion kernels (bsvd_*_pad / bsvd_*_crop): the frames stay picture-sized uint8 /
+YUV on the host and over PCIe.  ``network_size(H, W)`` is the (Hp, Wp) the pipelines use.  Without them every function is what it was."""
 import ctypes
 
 import torch
@@ -18,15 +23,36 @@ def _stream():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
-def frames_to_input(frames_u8, sigma=None, hwc=True):
+def network_size(H, W):
+    """-> (Hp, Wp): H and W rounded up to the next multiples of 4, the size the network runs a H x W picture at"""
+    return (int(H) + 3) // 4 * 4, (int(W) + 3) // 4 * 4
+
+
+def _pair(v, what):
+    try:
+        a, b = v
+        return int(a), int(b)
+    except (TypeError, ValueError):
+        raise ValueError("%s: expected a pair of ints, got %r" % (what, v)) from None
+
+
+def frames_to_input(frames_u8, sigma=None, hwc=True, pad_to=None):
     """frames_u8: uint8 device tensor [T,H,W,3] (hwc) or [T,3,H,W] -> fp32 [T,3(+1),H,W] in [0,1]; with ``sigma`` (noise
-    std in [0,1] units, e.g. 30/255) a constant noise-map channel is appended."""
+    std in [0,1] units, e.g. 30/255) a constant noise-map channel is appended.  ``pad_to=(Hp, Wp)``: the result is [T,3(+1),Hp,Wp],
+    reflect-padded on the right and bottom (F.pad(..., mode='reflect') of the unpadded result, bit for bit)."""
     lib = require_hip()
     if frames_u8.dtype != torch.uint8 or not frames_u8.is_cuda or frames_u8.dim() != 4:
         raise ValueError("expected a uint8 device tensor [T,H,W,C] or [T,C,H,W]")
     x = frames_u8.contiguous()
     T, H, W, C = x.shape if hwc else (x.shape[0], x.shape[2], x.shape[3], x.shape[1])
     extra = 0 if sigma is None else 1
+    if pad_to is not None:
+        Hp, Wp = _pair(pad_to, "pad_to")
+        y = torch.empty((T, C + extra, max(Hp, 0), max(Wp, 0)), dtype=torch.float32, device=x.device)
+        with torch.cuda.device(x.device):
+            _lib.check(lib.bsvd_u8_to_planar_pad(x.data_ptr(), y.data_ptr(), T, C, H, W, Hp, Wp, 1 if hwc else 0, extra,
+                                                 float(sigma or 0.0), _stream()), "bsvd_u8_to_planar_pad")
+        return y
     y = torch.empty((T, C + extra, H, W), dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device):
         _lib.check(lib.bsvd_u8_to_planar(x.data_ptr(), y.data_ptr(), T, C, H, W, 1 if hwc else 0, extra,
@@ -34,13 +60,21 @@ def frames_to_input(frames_u8, sigma=None, hwc=True):
     return y
 
 
-def output_to_frames(y, hwc=True, rgb2bgr=False):
-    """y: fp32 device tensor [T,C,H,W] -> uint8 [T,H,W,C] (or [T,C,H,W]): clamp [0,1], x255, round half to even."""
+def output_to_frames(y, hwc=True, rgb2bgr=False, crop_to=None):
+    """y: fp32 device tensor [T,C,H,W] -> uint8 [T,H,W,C] (or [T,C,H,W]): clamp [0,1], x255, round half to even.  ``crop_to=(H, W)``:
+    the frames of ``y[..., :H, :W]``; the rows and columns beyond are not read."""
     lib = require_hip()
     if y.dtype != torch.float32 or not y.is_cuda or y.dim() != 4:
         raise ValueError("expected a float32 device tensor [T,C,H,W]")
     y = y.contiguous()
     T, C, H, W = y.shape
+    if crop_to is not None:
+        Hc, Wc = _pair(crop_to, "crop_to")
+        out = torch.empty((T, max(Hc, 0), max(Wc, 0), C) if hwc else (T, C, max(Hc, 0), max(Wc, 0)), dtype=torch.uint8, device=y.device)
+        with torch.cuda.device(y.device):
+            _lib.check(lib.bsvd_planar_to_u8_crop(y.data_ptr(), out.data_ptr(), T, C, H, W, Hc, Wc, 1 if hwc else 0, 1 if rgb2bgr else 0,
+                                                  _stream()), "bsvd_planar_to_u8_crop")
+        return out
     out = torch.empty((T, H, W, C) if hwc else (T, C, H, W), dtype=torch.uint8, device=y.device)
     with torch.cuda.device(y.device):
         _lib.check(lib.bsvd_planar_to_u8(y.data_ptr(), out.data_ptr(), T, C, H, W, 1 if hwc else 0, 1 if rgb2bgr else 0,
@@ -48,17 +82,19 @@ def output_to_frames(y, hwc=True, rgb2bgr=False):
     return out
 
 
-def _yuv_desc(H, W, pix_fmt, matrix, full_range, chroma, row_pitch):
-    """-> (BsvdYuvDesc, frame_bytes); ValueError for a name or a size the library would refuse"""
+def _yuv_desc(H, W, pix_fmt, matrix, full_range, chroma, row_pitch, picture=False):
+    """-> (BsvdYuvDesc, frame_bytes); ValueError for a name or a size the library would refuse.  picture: a surface for the pad / crop
+    entry points, whose H and W only need to be even"""
     for what, name, table in (("pix_fmt", pix_fmt, _lib.PIX_FMT), ("matrix", matrix, _lib.MATRIX), ("chroma", chroma, _lib.CHROMA)):
         if name not in table:
             raise ValueError("%s %r: one of %s" % (what, name, ", ".join(sorted(table))))
     desc = _lib.BsvdYuvDesc(pix_fmt=_lib.PIX_FMT[pix_fmt], matrix=_lib.MATRIX[matrix], full_range=1 if full_range else 0,
                             chroma=_lib.CHROMA[chroma], row_pitch=int(row_pitch or 0))
-    nbytes = _lib.load().bsvd_yuv420_frame_bytes(int(H), int(W), desc.pix_fmt, desc.row_pitch)
+    lib = _lib.load()
+    nbytes = (lib.bsvd_yuv420_picture_bytes if picture else lib.bsvd_yuv420_frame_bytes)(int(H), int(W), desc.pix_fmt, desc.row_pitch)
     if nbytes < 0:
-        raise ValueError("yuv420 %s frame %d x %d with row_pitch %s: H and W must be positive multiples of 4 and row_pitch (bytes%s) at least "
-                         "W samples" % (pix_fmt, H, W, row_pitch, ", even" if pix_fmt == "p010" else ""))
+        raise ValueError("yuv420 %s frame %d x %d with row_pitch %s: H and W must be positive %s and row_pitch (bytes%s) at least "
+                         "W samples" % (pix_fmt, H, W, row_pitch, "and even" if picture else "multiples of 4", ", even" if pix_fmt == "p010" else ""))
     return desc, nbytes
 
 
@@ -66,6 +102,11 @@ def yuv420_frame_bytes(H, W, pix_fmt, row_pitch=None):
     """Bytes of one NV12 / P010 frame: ``row_pitch * H * 3 / 2`` (Y plane, then the interleaved CbCr plane of H/2 rows);
     ``row_pitch`` in bytes, None = tight (W samples)."""
     return _yuv_desc(H, W, pix_fmt, "bt709", False, "linear", row_pitch)[1]
+
+
+def yuv420_picture_bytes(H, W, pix_fmt, row_pitch=None):
+    """``yuv420_frame_bytes`` for the surfaces ``pad_to`` / ``crop_to`` take: H and W only need to be even."""
+    return _yuv_desc(H, W, pix_fmt, "bt709", False, "linear", row_pitch, picture=True)[1]
 
 
 def _yuv_buffer(buf, T, nbytes, pix_fmt, what):
@@ -80,17 +121,26 @@ def _yuv_buffer(buf, T, nbytes, pix_fmt, what):
     return buf.shape[1]
 
 
-def yuv420_to_input(buf, H, W, pix_fmt="nv12", matrix="bt709", full_range=False, chroma="linear", sigma=None, row_pitch=None):
+def yuv420_to_input(buf, H, W, pix_fmt="nv12", matrix="bt709", full_range=False, chroma="linear", sigma=None, row_pitch=None, pad_to=None):
     """buf: uint8 device tensor [T, frame_bytes] of NV12 / P010 frames (``yuv420_frame_bytes``; rows longer than one frame are
     frames that far apart) -> fp32 [T,3(+1),H,W] RGB, the tensor ``frames_to_input`` builds; with ``sigma`` the constant noise-map
     channel is appended.  matrix 'bt601' | 'bt709' | 'bt2020', limited or full range, chroma upsampling 'nearest' | 'linear'
     (MPEG-2 / H.264 / HEVC default siting).  The result is NOT clamped to [0,1]: the out-of-gamut values of a noisy source are
-    information for a denoiser."""
-    desc, nbytes = _yuv_desc(H, W, pix_fmt, matrix, full_range, chroma, row_pitch)
+    information for a denoiser.  ``pad_to=(Hp, Wp)`` (Hp even, Wp a multiple of 4): H and W only need to be even (``yuv420_picture_bytes``)
+    and the result is [T,3(+1),Hp,Wp]: the picture converted with its chroma clamped at the picture's own edges, then reflect-padded on
+    the right and bottom."""
+    desc, nbytes = _yuv_desc(H, W, pix_fmt, matrix, full_range, chroma, row_pitch, picture=pad_to is not None)
     lib = require_hip()
     desc.frame_stride = _yuv_buffer(buf, None, nbytes, pix_fmt, "yuv420_to_input")
     T = buf.shape[0]
     extra = 0 if sigma is None else 1
+    if pad_to is not None:
+        Hp, Wp = _pair(pad_to, "pad_to")
+        y = torch.empty((T, 3 + extra, max(Hp, 0), max(Wp, 0)), dtype=torch.float32, device=buf.device)
+        with torch.cuda.device(buf.device):
+            _lib.check(lib.bsvd_yuv420_to_planar_pad(buf.data_ptr(), y.data_ptr(), T, H, W, Hp, Wp, ctypes.byref(desc), extra,
+                                                     float(sigma or 0.0), _stream()), "bsvd_yuv420_to_planar_pad")
+        return y
     y = torch.empty((T, 3 + extra, H, W), dtype=torch.float32, device=buf.device)
     with torch.cuda.device(buf.device):
         _lib.check(lib.bsvd_yuv420_to_planar(buf.data_ptr(), y.data_ptr(), T, H, W, ctypes.byref(desc), extra, float(sigma or 0.0),
@@ -98,15 +148,19 @@ def yuv420_to_input(buf, H, W, pix_fmt="nv12", matrix="bt709", full_range=False,
     return y
 
 
-def output_to_yuv420(y, pix_fmt="nv12", matrix="bt709", full_range=False, chroma="linear", row_pitch=None, out=None):
+def output_to_yuv420(y, pix_fmt="nv12", matrix="bt709", full_range=False, chroma="linear", row_pitch=None, out=None, crop_to=None):
     """y: fp32 device tensor [T,3,H,W] RGB -> uint8 [T, frame_bytes] NV12 / P010 frames: clamp [0,1], matrix, chroma downsampling
     ('nearest': mean of the 2x2 block; 'linear': rows averaged, [1 2 1]/4 over columns), scale, clamp to the legal codes, round half
     to even.  ``out``: the caller's buffer [T, >= frame_bytes] to write into -- pitch padding and the bytes between frames are left
-    as they were; without it the result's padding is zero."""
+    as they were; without it the result's padding is zero.  ``crop_to=(H, W)`` (even): the surfaces, H x W, of ``y[..., :H, :W]``; the
+    rows and columns of ``y`` beyond reach no sample."""
     if y.dtype != torch.float32 or not y.is_cuda or y.dim() != 4 or y.shape[1] != 3:
         raise ValueError("expected a float32 device tensor [T,3,H,W]")
     T, _, H, W = y.shape
-    desc, nbytes = _yuv_desc(H, W, pix_fmt, matrix, full_range, chroma, row_pitch)
+    Hp, Wp = H, W
+    if crop_to is not None:
+        H, W = _pair(crop_to, "crop_to")
+    desc, nbytes = _yuv_desc(H, W, pix_fmt, matrix, full_range, chroma, row_pitch, picture=crop_to is not None)
     lib = require_hip()
     y = y.contiguous()
     if out is None:
@@ -115,6 +169,10 @@ def output_to_yuv420(y, pix_fmt="nv12", matrix="bt709", full_range=False, chroma
         raise ValueError("output_to_yuv420: out is on %s, y on %s" % (out.device, y.device))
     desc.frame_stride = _yuv_buffer(out, T, nbytes, pix_fmt, "output_to_yuv420(out=)")
     with torch.cuda.device(y.device):
-        _lib.check(lib.bsvd_planar_to_yuv420(y.data_ptr(), out.data_ptr(), T, H, W, ctypes.byref(desc), _stream()),
-                   "bsvd_planar_to_yuv420")
+        if crop_to is not None:
+            _lib.check(lib.bsvd_planar_to_yuv420_crop(y.data_ptr(), out.data_ptr(), T, Hp, Wp, H, W, ctypes.byref(desc), _stream()),
+                       "bsvd_planar_to_yuv420_crop")
+        else:
+            _lib.check(lib.bsvd_planar_to_yuv420(y.data_ptr(), out.data_ptr(), T, H, W, ctypes.byref(desc), _stream()),
+                       "bsvd_planar_to_yuv420")
     return out

@@ -16,13 +16,20 @@ yielded in submission order.
 sinks speak, 'nv12' (uint8) and 'p010' (uint16, 10-bit code in the high bits), as arrays [H*3/2, pitch] -- the Y plane's H rows,
 then the H/2 rows of interleaved CbCr; 1.5 (NV12) or 3 (P010) bytes per pixel each way instead of 3, converted by
 ``bsvd_yuv420_to_planar`` / ``bsvd_planar_to_yuv420`` where the uint8 kernels run for 'rgb24'.
+
+``pad`` selects what happens to a picture whose H or W is no multiple of 4 (the network has two 2x scales): None (the default) refuses
+it; 'reflect' takes any size -- even H and W for the 4:2:0 surfaces -- and does what the reference's callers do around the model
+(denoising_model.py, padding_input / crop_output): reflect-pad on the right and bottom up to the next multiples of 4, run the network at that
+size, crop the result.  Pad and crop happen inside the conversion kernels (``frame_io``'s ``pad_to`` / ``crop_to``), so the staging buffers
+and the PCIe transfers stay picture-sized and the results have the shape and dtype of what was fed.
 """
 import collections
 
 import numpy as np
 import torch
 
-from .frame_io import _yuv_desc, frames_to_input, output_to_frames, output_to_yuv420, yuv420_frame_bytes, yuv420_to_input
+from .frame_io import (_yuv_desc, frames_to_input, network_size, output_to_frames, output_to_yuv420, yuv420_frame_bytes,
+                       yuv420_picture_bytes, yuv420_to_input)
 
 Colour = collections.namedtuple("Colour", "matrix full_range chroma row_pitch width", defaults=("bt709", False, "linear", None, None))
 Colour.__doc__ = """How a YUV surface is to be read and written: matrix 'bt601' | 'bt709' | 'bt2020', full_range (False = limited / "TV"
@@ -30,33 +37,59 @@ range), chroma 'nearest' | 'linear' (frame_io.yuv420_to_input), row_pitch in byt
 length) and, for a pitch wider than the picture, its width W in samples (None = the arrays' row length)."""
 
 
-_Geometry = collections.namedtuple("_Geometry", "h w staging row_pitch")      # of one submitted array: picture size, shape of its bytes
-                                                                                # in the staging buffers, YUV row pitch (None = tight)
+# of one submitted array: picture size, shape of its bytes in the staging buffers, YUV row pitch (None = tight), and the size the network
+# runs at: the picture's, or with pad='reflect' the next multiples of 4
+_Geometry = collections.namedtuple("_Geometry", "h w staging row_pitch net_h net_w")
+
+PADS = (None, "reflect")
+
+
+def _check_pad(pad):
+    if pad not in PADS:
+        raise ValueError("pad %r: None (H and W must be multiples of 4) or 'reflect'" % (pad,))
+    return pad
+
+
+def _padded_size(h, w, what):
+    """the network size of a picture under pad='reflect'; reflect needs a pad below the dimension, which rules out 1 and 2"""
+    hp, wp = network_size(h, w)
+    if hp - h >= h or wp - w >= w:
+        raise ValueError("%s: a %d x %d picture cannot be reflect-padded to %d x %d (the pad must stay below the dimension)" % (what, h, w, hp, wp))
+    return hp, wp
 
 
 class _Rgb24:
     """packed RGB uint8 [H,W,3]: staged as it comes, converted by bsvd_u8_to_planar / bsvd_planar_to_u8"""
     dtype = np.dtype(np.uint8)
 
+    def __init__(self, pad=None):
+        self.pad = _check_pad(pad)
+
     def geometry(self, a, clip):
         if a.dtype != np.uint8 or a.ndim != (4 if clip else 3) or a.shape[-1] != 3:
             raise ValueError("expected uint8 frames [T,H,W,3]" if clip else "expected one uint8 frame [H,W,3]")
-        if a.shape[-3] % 4 or a.shape[-2] % 4:
-            raise ValueError("H and W must be multiples of 4 (pad first: denoise.pad_to_multiple_of_4)")
-        return _Geometry(a.shape[-3], a.shape[-2], tuple(a.shape), None)
+        h, w = a.shape[-3], a.shape[-2]
+        if self.pad:
+            if h < 2 or w < 2:
+                raise ValueError("expected frames of at least 2 x 2, got %d x %d" % (h, w))
+            return _Geometry(h, w, tuple(a.shape), None, *_padded_size(h, w, "rgb24"))
+        if h % 4 or w % 4:
+            raise ValueError("H and W must be multiples of 4 (pad first: denoise.pad_to_multiple_of_4; or pad='reflect')")
+        return _Geometry(h, w, tuple(a.shape), None, h, w)
 
     def to_input(self, dev_in, geom, sigma):
-        return frames_to_input(dev_in, sigma)
+        return frames_to_input(dev_in, sigma, pad_to=(geom.net_h, geom.net_w) if self.pad else None)
 
     def to_output(self, y, geom):
-        return output_to_frames(y)
+        return output_to_frames(y, crop_to=(geom.h, geom.w) if self.pad else None)
 
 
 class _Yuv420:
     """NV12 (uint8) / P010 (uint16) arrays [H*3/2, pitch]: staged as the bytes of the surface, converted by bsvd_yuv420_to_planar /
     bsvd_planar_to_yuv420"""
 
-    def __init__(self, pix_fmt, colour):
+    def __init__(self, pix_fmt, colour, pad=None):
+        self.pad = _check_pad(pad)
         if colour is None:
             colour = Colour()
         elif isinstance(colour, dict):
@@ -77,31 +110,37 @@ class _Yuv420:
             raise ValueError("expected %s, got %s %s" % (what, a.dtype, a.shape))
         rows, pitch = a.shape[-2], a.shape[-1]
         w = pitch if self.colour.width is None else int(self.colour.width)
-        if rows <= 0 or rows % 6 or w <= 0 or w % 4:
-            raise ValueError("expected %s with H and W multiples of 4 (pad first: denoise.pad_to_multiple_of_4), got %s" % (what, a.shape))
+        if self.pad:
+            if rows <= 0 or rows % 3 or w <= 0 or w % 2:
+                raise ValueError("expected %s with H and W even, got %s" % (what, a.shape))
+        elif rows <= 0 or rows % 6 or w <= 0 or w % 4:
+            raise ValueError("expected %s with H and W multiples of 4 (pad first: denoise.pad_to_multiple_of_4; or pad='reflect'), got %s" % (what, a.shape))
         if w > pitch:
             raise ValueError("%s: rows of %d samples are shorter than colour.width = %d" % (what, pitch, w))
         row_bytes = pitch * self.dtype.itemsize
         if self.colour.row_pitch is not None and self.colour.row_pitch != row_bytes:
             raise ValueError("%s: rows of %d bytes, colour.row_pitch says %d" % (what, row_bytes, self.colour.row_pitch))
         h = rows // 3 * 2
-        nbytes = yuv420_frame_bytes(h, w, self.pix_fmt, row_bytes)
-        return _Geometry(h, w, (a.shape[0], nbytes) if clip else (nbytes,), None if w == pitch else row_bytes)
+        net = _padded_size(h, w, what) if self.pad else (h, w)
+        nbytes = (yuv420_picture_bytes if self.pad else yuv420_frame_bytes)(h, w, self.pix_fmt, row_bytes)
+        return _Geometry(h, w, (a.shape[0], nbytes) if clip else (nbytes,), None if w == pitch else row_bytes, *net)
 
     def to_input(self, dev_in, geom, sigma):
-        return yuv420_to_input(dev_in, geom.h, geom.w, sigma=sigma, row_pitch=geom.row_pitch, **self.kw)
+        return yuv420_to_input(dev_in, geom.h, geom.w, sigma=sigma, row_pitch=geom.row_pitch,
+                               pad_to=(geom.net_h, geom.net_w) if self.pad else None, **self.kw)
 
     def to_output(self, y, geom):
-        return output_to_yuv420(y, row_pitch=geom.row_pitch, **self.kw)
+        return output_to_yuv420(y, row_pitch=geom.row_pitch, crop_to=(geom.h, geom.w) if self.pad else None, **self.kw)
 
 
-def _pixel_format(pix_fmt, colour):
+def _pixel_format(pix_fmt, colour, pad=None):
+    _check_pad(pad)
     if pix_fmt == "rgb24":
         if colour is not None:
             raise ValueError("colour describes a YUV surface; pix_fmt 'rgb24' takes none")
-        return _Rgb24()
+        return _Rgb24(pad)
     if pix_fmt in ("nv12", "p010"):
-        return _Yuv420(pix_fmt, colour)
+        return _Yuv420(pix_fmt, colour, pad)
     raise ValueError("pix_fmt %r: one of 'rgb24', 'nv12', 'p010'" % (pix_fmt,))
 
 
@@ -134,12 +173,13 @@ class _Ticket:
 class ClipPipeline:
     """model: a bsvd_amd.BSVD on a HIP device.  sigma: noise std in [0,1] units for the constant noise map (None for a
     blind model).  depth >= 2 overlaps the transfers of one clip with the forward of another.  pix_fmt 'rgb24' | 'nv12' | 'p010' and
-    colour (a ``Colour`` or a dict of its fields; YUV only): what ``submit`` takes and the results are, see the module docstring."""
+    colour (a ``Colour`` or a dict of its fields; YUV only): what ``submit`` takes and the results are, see the module docstring.
+    pad None | 'reflect': 'reflect' takes pictures of any size (even H and W for YUV), padded and cropped on the device."""
 
-    def __init__(self, model, sigma=None, depth=2, pix_fmt="rgb24", colour=None):
+    def __init__(self, model, sigma=None, depth=2, pix_fmt="rgb24", colour=None, pad=None):
         if depth < 1:
             raise ValueError("depth must be >= 1")
-        self.fmt = _pixel_format(pix_fmt, colour)
+        self.fmt = _pixel_format(pix_fmt, colour, pad)
         self.model, self.sigma = model, sigma
         self.device = model._device()
         if self.device.type != "cuda":
@@ -223,14 +263,17 @@ class LiveStream:
     module state).
 
     pix_fmt 'nv12' / 'p010' (with ``colour``, a ``Colour`` or a dict of its fields): feed takes and returns uint8 / uint16 surfaces
-    [H*3/2,pitch] instead, converted by ``bsvd_yuv420_to_planar`` / ``bsvd_planar_to_yuv420``; everything else is the same."""
+    [H*3/2,pitch] instead, converted by ``bsvd_yuv420_to_planar`` / ``bsvd_planar_to_yuv420``; everything else is the same.
 
-    def __init__(self, model, sigma=None, depth=2, overlap_blocks=None, frame_shape=None, pix_fmt="rgb24", colour=None):
-        """frame_shape: optional (H, W) of the frames to come -- the overlap decision (and with it ``latency``) is then final at
-        construction instead of at the first feed."""
+    pad None | 'reflect': 'reflect' takes frames of any size (even H and W for YUV): reflect-padded to the next multiples of 4 and cropped
+    again on the device, same latency, frames back in the fed shape."""
+
+    def __init__(self, model, sigma=None, depth=2, overlap_blocks=None, frame_shape=None, pix_fmt="rgb24", colour=None, pad=None):
+        """frame_shape: optional (H, W) of the frames to come (the picture, also with ``pad``) -- the overlap decision (and with it
+        ``latency``) is then final at construction instead of at the first feed."""
         if depth < 1:
             raise ValueError("depth must be >= 1")
-        self.fmt = _pixel_format(pix_fmt, colour)
+        self.fmt = _pixel_format(pix_fmt, colour, pad)
         self.model, self.sigma, self.depth = model, sigma, depth
         self._overlap_wanted = (depth >= 2) if overlap_blocks is None else bool(overlap_blocks)
         self._overlap_explicit = overlap_blocks is not None
@@ -246,7 +289,8 @@ class LiveStream:
         self.count = 0
         model.reset()
         if frame_shape is not None:
-            self._decide_overlap(int(frame_shape[0]), int(frame_shape[1]))
+            h, w = int(frame_shape[0]), int(frame_shape[1])
+            self._decide_overlap(*(_padded_size(h, w, "frame_shape") if pad else (h, w)))
 
     @property
     def latency(self):
@@ -296,7 +340,7 @@ class LiveStream:
 
     def _step(self, frame_u8, last=False):
         if frame_u8 is not None:
-            self._decide_overlap(self.geom.h, self.geom.w)
+            self._decide_overlap(self.geom.net_h, self.geom.net_w)
         slot = self.slots[self.count % len(self.slots)]
         self.count += 1
         with torch.cuda.device(self.device):

@@ -337,6 +337,40 @@ int bsvd_planar_to_yuv420(const float *src, void *dst, int32_t frames, int32_t H
                           void *stream);
 
 /*
+ * Frame I/O for any picture size: the four entry points above with a reflect pad on the way in and a crop on the way out, in the kernel.
+ * The network needs H and W to be multiples of 4; the reference's callers pad the fp32 tensor on the right and bottom and crop the result
+ * (denoising_model.py, padding_input / crop_output -- F.pad(x, (0, pw, 0, ph), mode='reflect') and y[..., :H, :W]).  These entry points
+ * stand in for those two lines where the frames are uint8 or YUV 4:2:0 and never exist as fp32 on the host.  Added without a new
+ * BSVD_ABI_VERSION: discover them by symbol (dlsym), like the YUV entry points.
+ *
+ * Picture size H x W: what the caller's frames / surfaces have.  Network size Hp x Wp: what the planar fp32 tensor has, Hp >= H, Wp >= W.
+ *   in  (_pad):  dst [frames][C + const_channels][Hp][Wp]: element (r, c) = the converted picture element (refl_H(r), refl_W(c)),
+ *                refl_N(i) = i for i < N, else 2 (N - 1) - i (the edge sample is not repeated: torch's 'reflect').  I.e. exactly
+ *                "convert at picture size, then reflect-pad".  The constant channels are constant over the whole Hp x Wp plane.  With YUV
+ *                the chroma upsampling clamps at the PICTURE's edges as in bsvd_yuv420_to_planar; the mirror acts on the RGB values.
+ *   out (_crop): src [frames][C][Hp][Wp]: exactly "take src[..., :H, :W], then convert at picture size".  Pad rows and columns of src
+ *                influence no sample; with YUV the chroma filter sees picture columns only.
+ * Conversions, rounding and every other argument: as documented at the entry point of the same name without suffix.  The uint8 frames /
+ * the surface are picture-sized (BsvdYuvDesc.row_pitch and frame_stride describe the picture-sized surface); no byte outside their
+ * samples is read or written, and every destination element is written exactly once.  Hp == H and Wp == W is allowed (no pad).
+ * All four return -3, naming the argument in bsvd_last_error(), for: a NULL pointer; frames, C, H or W <= 0; const_channels < 0; Hp < H or
+ * Wp < W; a pad of a whole dimension or more (Hp - H >= H or Wp - W >= W: reflect is undefined there).  The YUV pair in addition for: H or
+ * W odd; Hp odd; Wp not a multiple of 4 (the fp32 rows move as float4); and every desc / pitch / stride / alignment condition of
+ * bsvd_yuv420_to_planar.  The uint8 pair takes any Hp, Wp and any alignment (float4 on the fp32 side when Wp % 4 == 0 and the tensor is
+ * 16-byte aligned, scalars otherwise).
+ * bsvd_yuv420_picture_bytes: as bsvd_yuv420_frame_bytes (row_pitch * H * 3 / 2), but H and W only need to be even.
+ */
+int bsvd_u8_to_planar_pad(const uint8_t *src, float *dst, int32_t frames, int32_t C, int32_t H, int32_t W, int32_t Hp, int32_t Wp,
+                          int32_t src_hwc, int32_t const_channels, float const_val, void *stream);
+int bsvd_planar_to_u8_crop(const float *src, uint8_t *dst, int32_t frames, int32_t C, int32_t Hp, int32_t Wp, int32_t H, int32_t W,
+                           int32_t dst_hwc, int32_t reverse_channels, void *stream);
+int64_t bsvd_yuv420_picture_bytes(int32_t H, int32_t W, int32_t pix_fmt, int32_t row_pitch);
+int bsvd_yuv420_to_planar_pad(const void *src, float *dst, int32_t frames, int32_t H, int32_t W, int32_t Hp, int32_t Wp,
+                              const BsvdYuvDesc *desc, int32_t const_channels, float const_value, void *stream);
+int bsvd_planar_to_yuv420_crop(const float *src, void *dst, int32_t frames, int32_t Hp, int32_t Wp, int32_t H, int32_t W,
+                               const BsvdYuvDesc *desc, void *stream);
+
+/*
  * Frame-window sharding: gathers the channel slice [c0, c0+n) of one NHWC frame into
  * a compact [H*W][n] buffer -- the message a rank sends to its temporal neighbour
  * (first frame, c0 = 0 -> the left neighbour's halo_next; last frame, c0 = fold -> the right

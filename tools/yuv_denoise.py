@@ -7,7 +7,8 @@ steady_frames_per_s (wall clock, reads and writes included) over the steady stat
     python tools/yuv_denoise.py IN OUT --size 1920x1080 --pix-fmt nv12 --sigma 30 [--matrix bt709] [--full-range] [--chroma linear]
                                 [--depth 2] [--ckpt model.pth]                IN / OUT: a file, or - for stdin / stdout
 
-The width and height must be multiples of 4.  Without --ckpt the weights are seeded random ones (rates, not pictures), like
+The width and height must be even; a size that is no multiple of 4 (854x480) is reflect-padded to the next one and cropped again on the
+device (LiveStream(pad='reflect')), the files hold pictures of the size given.  Without --ckpt the weights are seeded random ones (rates, not pictures), like
 tools/live_stream.py."""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -37,8 +38,9 @@ def main(argv=None):
     ap.add_argument("--precision", default="f16x3")
     a = ap.parse_args(argv)
     W, H = map(int, a.size.lower().split("x"))
-    if W <= 0 or H <= 0 or W % 4 or H % 4:
-        ap.error("--size %s: width and height must be positive multiples of 4" % a.size)
+    if W <= 2 or H <= 2 or W % 2 or H % 2:
+        ap.error("--size %s: width and height must be even (4:2:0) and at least 4" % a.size)
+    pad = "reflect" if W % 4 or H % 4 else None
     dtype = np.dtype(np.uint8 if a.pix_fmt == "nv12" else "<u2")
     nbytes = W * H * 3 // 2 * dtype.itemsize
 
@@ -49,7 +51,7 @@ def main(argv=None):
     m = bsvd_amd.BSVD(chns=[64, 128, 256], mid_ch=64, norm="none", act="relu6", interm_ch=64, pretrain_ckpt=a.ckpt,
                       precision=a.precision).to(torch.device("cuda", 0)).eval()
     live = LiveStream(m, sigma=a.sigma / 255.0, depth=a.depth, frame_shape=(H, W), pix_fmt=a.pix_fmt,
-                      colour={"matrix": a.matrix, "full_range": a.full_range, "chroma": a.chroma})
+                      colour={"matrix": a.matrix, "full_range": a.full_range, "chroma": a.chroma}, pad=pad)
     fin = sys.stdin.buffer if a.input == "-" else open(a.input, "rb")
     fout = sys.stdout.buffer if a.output == "-" else open(a.output, "wb")
     n_in = n_out = 0
@@ -77,7 +79,7 @@ def main(argv=None):
     res = {"frames": n_out, "frames_per_s": n_out / total if total > 0 else 0.0,
            "ms_per_feed": {"p50": float(np.percentile(steady, 50)), "p99": float(np.percentile(steady, 99))},
            "steady_frames_per_s": (n_in - k) / (done[-1] - done[k - 1]) if n_in > k >= 1 else 0.0,       # wall clock, reads and writes included
-           "size": "%dx%d" % (W, H), "pix_fmt": a.pix_fmt, "depth": a.depth, "frame_latency_feeds": live.latency}
+           "size": "%dx%d" % (W, H), "pix_fmt": a.pix_fmt, "depth": a.depth, "frame_latency_feeds": live.latency, "pad": pad}
     print(json.dumps(res), file=sys.stderr if a.output == "-" else sys.stdout, flush=True)
     return res
 
