@@ -420,9 +420,10 @@ __global__ __launch_bounds__(256, (PREF ? 2 : occ_of<C, PREC>())) void conv3x3_k
                     c.rs = rs_next; c.ps4 = s.next_ps * 4u;
                     c.rs2 = rs_prev; c.ps4_2 = s.prev_ps * 4u;
                     // fp32: channel c of a source sits at float offset co + (c - first channel of the slice); split16: the
-                    // pieces of a full frame keep their place inside chunk 0 (the channel offset co is not a byte offset)
-                    c.soff = PREC == 1 ? 0u : (unsigned)s.next_co * 4u;
-                    c.soff2 = PREC == 1 ? 0u : (unsigned)s.prev_co * 4u;
+                    // pieces of a full frame keep their place inside their chunk -- co names the chunk (co & ~15: chunk 0 of a neighbour
+                    // frame, a later one where the frame sits inside a wider holding tensor), its low bits are not a byte offset
+                    c.soff = PREC == 1 ? (unsigned)(s.next_co & ~15) * 4u : (unsigned)s.next_co * 4u;
+                    c.soff2 = PREC == 1 ? (unsigned)(s.prev_co & ~15) * 4u : (unsigned)s.prev_co * 4u;
                     return c;
                 }
             }
@@ -1407,7 +1408,9 @@ static int launch_cfg(const ConvParams &pin, hipStream_t stream, char *name = nu
     if (nblk <= 0 || nblk > 0x7fffffff) { set_error("bsvd_conv3x3: grid of %lld workgroups", (long long)nblk); return -1; }
     static std::atomic<int> granted[MAX_DEVICES];
     // + the raw input patch of the fused entry / the first conv's staged input chunk of a fused pair (20 rows x 1280 B)
-    constexpr int LDS = C::LDS_BYTES + (HEADF ? (C::TH + 4) * (C::TW + 4) * 16 : 0) +
+    // (the GENERIC K loop alternates between two patch buffers whatever the tile: the single-buffer stride-2 tile needs the second one here)
+    constexpr int PATCH = FAST || C::DBUF ? C::LDS_BYTES : (C::LDS_BYTES > 2 * C::PATCH_FLOATS * 4 ? C::LDS_BYTES : 2 * C::PATCH_FLOATS * 4);
+    constexpr int LDS = PATCH + (HEADF ? (C::TH + 4) * (C::TW + 4) * 16 : 0) +
                         (PREF ? (C::TH + 4) * (((C::TW + 4) * 64 + 255) / 256 * 256) : 0);
     hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void *>(&conv3x3_kernel<C, FAST, PREC, MIXF, HEADF, PREF>), LDS, granted);
     if (e != hipSuccess) return (int)e;
@@ -1515,7 +1518,19 @@ int launch_conv3x3(const ConvParams &p, int stride, hipStream_t stream, char *na
             if (fat_wide >= fat_min) return launch_cfg<ConvCfg<4, 2, 2, 2, 1>, true, 1>(p, stream, name, name_len);
             return launch_cfg<ConvCfg<2, 2, 2, 2, 1>, true, 1>(p, stream, name, name_len);
         }
-        if (p.fold == 8) return launch_cfg<ConvCfg<2, 2, 4, 1, 1>, true, 1, true>(p, stream, name, name_len);   // c32-sized nets
+        if (p.fold == 8) {                                                                                      // c32-sized nets
+            // a half chunk of fp16 pairs has two shapes: the compact [hi x8 | lo x8] slice (pstride 8) and its place inside a split16 frame --
+            // whole 16-channel chunks per pixel, the slice in the second half of a chunk for halo_prev, the first for halo_next; coff names the
+            // CHUNK (coff & ~15), its low bits do not move the slice inside it.  A chunk that is not whole or not inside the pixel is refused.
+            auto half_ok = [](const float *h, int ps, int co) { return !h || ps == 8 || ((ps & 15) == 0 && co >= 0 && (co & ~15) + 16 <= ps); };
+            if (!half_ok(p.halo_prev, p.halo_prev_ps, p.halo_prev_co) || !half_ok(p.halo_next, p.halo_next_ps, p.halo_next_co)) {
+                set_error("bsvd_conv3x3: BSVD_F16X3 fold 8: a halo is the compact slice (pstride 8) or sits in a split16 frame (pstride %% 16 == 0, the "
+                          "chunk coff names inside the pixel); got prev (%d, %d), next (%d, %d)",
+                          p.halo_prev_ps, p.halo_prev_co, p.halo_next_ps, p.halo_next_co);
+                return -17;
+            }
+            return launch_cfg<ConvCfg<2, 2, 4, 1, 1>, true, 1, true>(p, stream, name, name_len);
+        }
         // the 64-channel layers: 128-px x 32-ch wave tiles (<4,1,2,2,1>, 2 waves per SIMD) instead of 64 px x 64 ch at 3 waves per SIMD: half the weight
         // bytes per MFMA (the 64 x 64 tile pulled 4 KB of weights per wave and tap through the L1: ~42 B/clk/CU of its 64), twice the pixel-fragment
         // reads -- a loss with the padded LDS layout (r01), a 7 % gain with the conflict-free quad-planar one (r03: 6.42 -> 5.94 ms per clip).

@@ -268,7 +268,8 @@ int bsvd_to_v(const void *x, int64_t x_fs, int32_t x_f32, void *v, int64_t v_fs,
     if (!aligned16(x) || !aligned16(v) || (v_fs & 3)) { set_error("bsvd_to_v: 16-byte aligned tensors"); return -3; }
     if (v_fs < bsvd_v_frame_elems(H, W, C, m)) { set_error("bsvd_to_v: v_frame_stride < bsvd_v_frame_elems"); return -3; }
     const int wg = v_groups(W, m);
-    hipError_t e = hipMemsetAsync(v, 0, (size_t)frames * v_fs * 4, (hipStream_t)stream);        // pad groups and the edge record: zeros
+    // pad groups and the edge record: zeros -- of the frames themselves, never of what the caller keeps between them (v_fs > the frame)
+    hipError_t e = hipMemset2DAsync(v, (size_t)v_fs * 4, 0, (size_t)bsvd_v_frame_elems(H, W, C, m) * 4, (size_t)frames, (hipStream_t)stream);
     if (e != hipSuccess) return (int)e;
     return launch_sweep(m == 2 ? to_v_kernel<2> : m == 4 ? to_v_kernel<4> : to_v_kernel<6>, (int64_t)frames * H * wg * (C >> 3), stream,
                         (const float *)x, x_fs, x_f32, (float *)v, v_fs, frames, H, W, C, wg);

@@ -17,6 +17,13 @@
  *   - Activations are NHWC ("channels last"): element (f, y, x, c) of a clip lives at
  *         base + f*frame_stride + (y*W + x)*C + c        (strides in ELEMENTS)
  *     with C already padded by the caller to a multiple of 16 (padded channels hold zeros).
+ *   - Every stride is the caller's (tests/test_gpu_strides.py): a frame stride is >= the tight frame.  x_frame_stride takes any such value in
+ *     BSVD_F32 (an unaligned x or stride runs the [generic] kernel); the NHWC x of BSVD_F16X3 and of the Winograd form, like its halos, needs
+ *     16-byte aligned pointers and strides that are multiples of 4 elements, and anything else is refused (-17 / -19 / -20, naming the
+ *     alignment) before a launch.  y and extra are the caller's to keep 16-byte aligned with strides that are multiples of 4 elements; the
+ *     library does not check them.  No element outside [frames][H][W][C] of a tensor -- between its frames, in the other channels of a
+ *     holding tensor -- influences a result; no byte outside y's logical elements is written; every logical element of y is written, padded
+ *     channels included.
  *   - dtype: BSVD_F32 is the exact-fp32 mode (v_mfma_f32_32x32x2_f32, bitwise an fmaf chain); BSVD_F16X3 the
  *     split-fp16 3-pass mode (see the enum).  In BSVD_F16X3 the edge layers convert: planar fp32 in -> split16,
  *     split16 -> planar fp32 out; the packed weights of MFMA layers are split16 too (bsvd_pack_weights dtype).
@@ -70,6 +77,11 @@ enum {
  * (compact [H][W][fold] slice: pstride = fold, coff = 0; a full NHWC frame: pstride = Cin,
  *  coff = fold resp. 0.)  This is what a neighbouring frame-window shard sends over RCCL, and in
  *  streaming mode it is BiBufferConv's left_fold_2fold / input_right.
+ * BSVD_F16X3 with fold 8 (half a 16-channel chunk of fp16 pairs per source) knows two halo shapes: the compact slice of bsvd_halo_pack
+ * (pstride 8: [hi x8 | lo x8]) and the slice in its place inside a split16 frame (pstride % 16 == 0).  There coff names the CHUNK -- coff -
+ * coff % 16 is the first channel of the frame's chunk 0 inside a (possibly wider) holding tensor -- and the slice's place inside the chunk is
+ * fixed: its second half for halo_prev, its first for halo_next; coff % 16 is ignored (a neighbour frame is passed with coff = fold resp. 0).
+ * A pstride that is neither, or a chunk that does not lie inside the pixel (coff - coff % 16 + 16 > pstride), returns -17.
  */
 typedef struct BsvdConvArgs {
     const void *x;              /* [frames][H][W][Cin]                                              */
@@ -220,7 +232,7 @@ const char *bsvd_last_error(void);
 /* Transformed-domain tensors (BsvdConvArgs.x_v / y_v): floats per frame (V planes + edge record), groups per row, and a stand-alone
  * transform of an NHWC tensor (x_f32 != 0: plain fp32 channels, else fp16 pairs) into that layout -- what a y_v producer writes, computed
  * directly (no edge record needed; the E block is zero-filled).  Test / measurement aid and the fallback for a producer that cannot
- * write the layout itself.  m = 2, 4 or 6; C % 16 == 0. */
+ * write the layout itself.  m = 2, 4 or 6; C % 16 == 0.  Writes the bsvd_v_frame_elems floats of every frame, nothing between frames. */
 int64_t bsvd_v_frame_elems(int32_t H, int32_t W, int32_t C, int32_t m);
 int32_t bsvd_v_groups(int32_t W, int32_t m);
 int bsvd_to_v(const void *x, int64_t x_frame_stride, int32_t x_f32, void *v, int64_t v_frame_stride, int32_t frames, int32_t H, int32_t W,
