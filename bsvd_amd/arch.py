@@ -364,7 +364,7 @@ class BSVD(_HipNet):
                     frame-by-frame pipeline).  feedin_one_element always runs one frame per step.
       precision   : 'f16x3' (split-fp16 3-pass MFMA with fp32 accumulation: fp32-class accuracy -- 2-6e-5 max-abs on
                     bsvd_c64, budget 1e-3 -- at ~3x the throughput; needs 64-channel or 128k-channel temporal-fusion layers:
-                    fold 8 or fold % 16 == 0), 'fp32' (exact fp32 MFMA, bitwise an fmaf chain) or 'auto' (default: 'f16x3'
+                    fold 8 or fold % 16 == 0), 'fp32' (exact fp32 MFMA, bitwise the fmaf chain include/bsvd_hip.h spells out -- tests/test_gpu_fp32_chain.py) or 'auto' (default: 'f16x3'
                     when the network admits it, else 'fp32'; ``self.precision`` holds the choice).
       norm        : 'none' or 'bn' (the reference default; eval mode only: the BatchNorm layers hold their parameters
                     under the reference's names and are folded into the packed conv weights).

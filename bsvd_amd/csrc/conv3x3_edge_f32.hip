@@ -14,7 +14,9 @@
 //
 // Both read the SAME packed weight layout as the MFMA kernel ([Cin_pad/16][9][4][Cout_pad][4]); weights are
 // wave-uniform and travel through the scalar cache into SGPR operands of v_fma_f32.  Accumulation order is a plain
-// fp32 fmaf chain over (chunk, tap, channel) -- exact fp32 like the MFMA path.
+// fp32 fmaf chain over (chunk, tap, channel) -- exact fp32 like the MFMA path.  The tail starts it at +0 and adds the bias
+// behind it (one rounding, like the MFMA epilogue); the head starts it AT the bias.  include/bsvd_hip.h ("Arithmetic of
+// BSVD_F32") states both, tests/test_gpu_fp32_chain.py holds the kernels to those bits (profiles/fp32_chain_bits.txt).
 #include "bsvd_internal.h"
 
 namespace bsvd {

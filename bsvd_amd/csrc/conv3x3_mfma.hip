@@ -27,6 +27,10 @@
 // spreads consecutive pixels over the banks).  K-order trick: lane l of a 32x32x2 MFMA supplies k = l>>5;
 // a 16-byte read gives a lane 4 consecutive channels and MFMA j (0..3) uses k = 8g + 4(l>>5) + j on both
 // operands -- any K permutation is legal as long as A and B agree, so every operand read is 16 bytes wide.
+// The permutation IS the exact-fp32 mode's summation order: per output, from +0, one fmaf per (chunk, tap, g, j, k = 0 then 1), the
+// bias added behind the chain in one rounding.  Measured bit for bit on the MI355X against that chain on the CPU in every f32
+// instantiation, FAST and [generic] (include/bsvd_hip.h "Arithmetic of BSVD_F32", tests/test_gpu_fp32_chain.py,
+// profiles/fp32_chain_bits.txt): the instruction accumulates k = 0 before k = 1, each as a fused multiply-add.
 //
 // PREC = 1 (BSVD_F16X3, "split16"): the same data movement with every fp32 value carried as an fp16 pair
 // v = hi + lo (hi = fp16(v), lo = fp16(v - hi)).  A 16-channel chunk of a pixel is stored as [hi x16 | lo x16] in

@@ -28,6 +28,21 @@
  *     split-fp16 3-pass mode (see the enum).  In BSVD_F16X3 the edge layers convert: planar fp32 in -> split16,
  *     split16 -> planar fp32 out; the packed weights of MFMA layers are split16 too (bsvd_pack_weights dtype).
  */
+// Arithmetic of BSVD_F32, bit for bit ("bitwise an fmaf chain" above, spelled out; the CPU model oracle/chain_ref.c restates it,
+// tests/test_gpu_fp32_chain.py compares the bits on the MI355X, profiles/fp32_chain_bits.txt is the record).  Per output value, with x the
+// gathered input of the frame -- zero outside the image and in its padded channels -- and every operation below ONE fp32 operation, round to
+// nearest even:
+//   chain     acc = fmaf(x, w, acc) once per term, in the kernel's order.  A term with a zero operand changes nothing but the sign of a zero
+//             accumulator and may be skipped: results are the chain's up to the sign of zero.
+//     MFMA layers -- everything but the two planar edge layers; FAST, [generic] and [fold8] alike, every tile, both tile_order values:
+//             acc starts at +0; for each 16-channel chunk c, for each tap t = 3 ky + kx, for g in 0..1, for j in 0..3:
+//             channel 16c + 8g + j, then channel 16c + 8g + 4 + j (the two k of one v_mfma_f32_32x32x2_f32, k = 0 first).
+//     planar exit  (y_planar_ch > 0): acc starts at +0; for each chunk c, each tap t, channel 16c + 0 .. 16c + 15.
+//     planar entry (x_planar_ch > 0): acc starts at the BIAS (+0 without one); for each tap t, channel 0 .. x_planar_ch - 1.
+//   bias      v = acc + bias, one rounding (== fmaf(acc, 1.0f, bias)); the planar entry has it at the chain's start instead.
+//   act       BSVD_ACT_RELU max(v, 0); BSVD_ACT_RELU6 min(max(v, 0), 6).
+//   epilogue  PS_ADD v + skip; RESID extra - v on the first resid_ch channels; then, with y_clamp, min(max(v, y_lo), y_hi).
+// A schedule, shard or halo form changes which launch computes a value, never its chain: clip, stream and sharded runs give the same bits.
 #ifndef BSVD_HIP_H
 #define BSVD_HIP_H
 
