@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("BSVD_HIP_LIB") or os.path.join(_HERE, "libbsvd_hip.so")   # env override: A/B tuning builds
 
 ABI_VERSION = 12
-BSVD_F32, BSVD_F16, BSVD_F16X3 = 0, 1, 2
+BSVD_F32, BSVD_F16X3, BSVD_F16 = 0, 2, 3       # (1 is retired: the library refuses it)
 ACT = {"none": 0, "relu": 1, "relu6": 2}
 EPI_PLAIN, EPI_PS_ADD, EPI_RESID = 0, 1, 2
 BUILD_MEASURE = 1            # bsvd_build_info(): a -DBSVD_MEASURE build (tools/build_measure.sh), never the in-tree product library

@@ -71,6 +71,9 @@ F16X3_WEIGHT_LIMIT = 6.0e4      # |folded weight| beyond this cannot be carried 
 # existing result, stay what they were) packs w itself.  Exact-fp32 mode: accepted, does nothing.
 WEIGHT_SCALE = ("off", "auto")
 WEIGHT_SCALE_DEFAULT = "off"
+# precision: 'f16x3' and 'f16' are the SPLIT modes (fp16-pair tensors and packs; three MFMA passes / one); 'auto' never resolves to 'f16'
+PRECISIONS = ("auto", "fp32", "f16x3", "f16")
+from .engine import SPLIT_PRECISIONS  # noqa: E402  (one definition: engine.py)
 
 
 class _Slots(nn.Module):
@@ -131,8 +134,8 @@ class _HipNet(nn.Module):
 
     def _init_engine(self, net, precision, clamp, norm='none', wide_conv='auto', fuse_pairs='auto', f32_handover='auto', v_handover='auto',
                      weight_scale=WEIGHT_SCALE_DEFAULT):
-        if precision not in ("auto", "fp32", "f16x3"):
-            raise ValueError("precision must be 'auto', 'fp32' or 'f16x3'")
+        if precision not in PRECISIONS:
+            raise ValueError("precision must be one of %s" % (PRECISIONS,))
         self.weight_scale = weight_scale       # (property: validates, see below)
         if wide_conv == "auto":
             wide_conv = WIDE_CONV_DEFAULT
@@ -165,27 +168,40 @@ class _HipNet(nn.Module):
 
     # ``precision`` is a property: the constructor keyword AND a later ``model.precision = 'fp32'`` go through the same validation,
     # and the next forward re-packs the weights in the new mode (the pack signature holds the resolved request).  Reading it gives the
-    # mode that RUNS: 'f16x3' | 'fp32' -- after a weight-range fallback of 'auto' that is 'fp32' until an in-range checkpoint is loaded.
+    # mode that RUNS: 'f16x3' | 'f16' | 'fp32' ('auto' resolves to 'f16x3' or 'fp32' only, never to 'f16') -- after a weight-range fallback of 'auto' that is 'fp32' until an in-range checkpoint is loaded.
     @property
     def precision(self):
         return self.__dict__.get("_precision_eff")
 
     @precision.setter
     def precision(self, precision):
-        if precision not in ("auto", "fp32", "f16x3"):
-            raise ValueError("precision must be 'auto', 'fp32' or 'f16x3'")
+        if precision not in PRECISIONS:
+            raise ValueError("precision must be one of %s" % (PRECISIONS,))
         requested = precision
         if precision == "auto":
             # the split-fp16 mode carries fp32-class accuracy (2-6e-5 vs the reference goldens, budget 1e-3) at ~3x the
             # rate: take it whenever the network's channel layout admits it (the c64 / c32-sized networks do)
             precision = "f16x3" if self._split_ok else "fp32"
-        elif precision == "f16x3" and not self._split_ok:
-            raise ValueError("precision='f16x3' needs temporal-fusion layers with fold %% 16 == 0 or 64 channels (fold 8), "
+        elif precision in SPLIT_PRECISIONS and not self._split_ok:
+            raise ValueError("precision='%s' needs temporal-fusion layers with fold %% 16 == 0 or 64 channels (fold 8), "
                              "i.e. chns[1:] = (64|128k, 128k) like the c64 and c32 networks, and <= 4 input/output "
-                             "channels; offending layers: %s" % (self._split_bad[:3],))
+                             "channels; offending layers: %s" % (precision, self._split_bad[:3]))
+        if precision == "f16":
+            self._check_f16_options()
         self.precision_requested = requested
         self.__dict__["_precision_eff"] = precision
         self._precision_init = precision       # what the request resolved to; a weight-range fallback of 'auto' to fp32 lasts one pack only
+
+    def _check_f16_options(self):
+        """precision='f16' instantiates the direct form, the fused entry and F(2,3) only: the options that need another kernel are refused
+        here by name, where the caller set them, not by the library in the middle of a forward."""
+        if self.__dict__.get("wide_conv") in ("wino6", "wino26"):
+            raise ValueError("precision='f16' with wide_conv=%r: the one-pass mode runs the Winograd form as F(2,3) only "
+                             "(wide_conv='wino2' or 'direct')" % (self.wide_conv,))
+        if self.__dict__.get("v_handover"):
+            raise ValueError("precision='f16' with v_handover=True: the transformed-domain hand-over is an F(6,3) option of 'f16x3'")
+        if self.__dict__.get("fuse_pairs"):
+            raise ValueError("precision='f16' with fuse_pairs=True: the fused 64-channel pair is an 'f16x3' kernel")
 
     # ``weight_scale`` likewise: the keyword and a later ``model.weight_scale = 'auto'`` are validated alike; the next forward re-packs
     @property
@@ -245,7 +261,8 @@ class _HipNet(nn.Module):
         return ("MI355X engine: chns=%s mid_ch=%d in_ch=%d out_ch=%d act=%s interm_ch=%d blind=%s norm=%s precision=%s "
                 "(requested %s) weight_scale=%s, %d fused conv layers / %d temporal-fusion, %.1f GMAC per 540x960 frame"
                 % (list(n.chns), n.mid_ch, n.net_in_ch, n.out_ch, n.act, n.interm_ch, n.blind, self.norm, self.precision,
-                   self.precision_requested, self.weight_scale, len(n.layers), n.shift_num, n.macs_per_frame(540, 960) / 1e9))
+                   self.precision_requested, self.weight_scale, len(n.layers), n.shift_num, n.macs_per_frame(540, 960) / 1e9)
+                + (" [precision f16: ONE fp16 MFMA pass on the split tensors, hi(w) * hi(x): fp16-class accuracy]" if self.precision == "f16" else ""))
 
     def _tag_owned(self):
         """marks every module of this engine's tree for the registration hooks (see _bump_epoch)"""
@@ -281,8 +298,10 @@ class _HipNet(nn.Module):
             if getattr(self, "_stream_engs", None):
                 self.release_stream_buffers()
             state = self._engine_state()
-            if self.precision == "f16x3":
-                # fp16 range guard of the split mode: a folded weight (norm='bn' with a tiny running_var) beyond fp16's range
+            if self._precision_init == "f16":
+                self._check_f16_options()      # (wide_conv / fuse_pairs / v_handover are plain attributes: a later assignment is caught here)
+            if self.precision in SPLIT_PRECISIONS:
+                # fp16 range guard of the split modes: a folded weight (norm='bn' with a tiny running_var) beyond fp16's range
                 # cannot be carried as a hi+lo pair.  'auto' falls back to exact fp32, an explicit 'f16x3' refuses.
                 # (Activations beyond +-65504 saturate in the split store; unbounded-ReLU networks fed [0,1] images stay
                 # orders of magnitude below that)
@@ -298,8 +317,8 @@ class _HipNet(nn.Module):
                                       "precision='auto' falls back to exact fp32 for this network" % wmax)
                         self.__dict__["_precision_eff"] = "fp32"
                     else:
-                        raise ValueError("precision='f16x3': max |weight| after the BatchNorm fold is %.3g, outside fp16's "
-                                         "range (use precision='fp32' or 'auto')" % wmax)
+                        raise ValueError("precision='%s': max |weight| after the BatchNorm fold is %.3g, outside fp16's "
+                                         "range (use precision='fp32' or 'auto')" % (self.precision, wmax))
             self._packed = PackedNet(self.net, state, device, self.precision, self.wide_conv, fuse_pairs=self.fuse_pairs,
                                      f32_handover=self.f32_handover, v_handover=self.v_handover,
                                      weight_scale=self.weight_scale == "auto")
@@ -365,7 +384,10 @@ class BSVD(_HipNet):
       precision   : 'f16x3' (split-fp16 3-pass MFMA with fp32 accumulation: fp32-class accuracy -- 2-6e-5 max-abs on
                     bsvd_c64, budget 1e-3 -- at ~3x the throughput; needs 64-channel or 128k-channel temporal-fusion layers:
                     fold 8 or fold % 16 == 0), 'fp32' (exact fp32 MFMA, bitwise the fmaf chain include/bsvd_hip.h spells out -- tests/test_gpu_fp32_chain.py) or 'auto' (default: 'f16x3'
-                    when the network admits it, else 'fp32'; ``self.precision`` holds the choice).
+                    when the network admits it, else 'fp32'; ``self.precision`` holds the choice).  'f16': the split mode's tensors and
+                    weight packs with ONE fp16 MFMA pass, hi(w) * hi(x), fp32 accumulation -- fp16-CLASS accuracy (operands rounded
+                    to 11 bits, like the reference's own fp16 autocast; outside the 1e-3 budget of the other two modes), never chosen
+                    by 'auto'; same network requirements as 'f16x3'; not with wide_conv='wino6' / 'wino26', fuse_pairs or v_handover.
       norm        : 'none' or 'bn' (the reference default; eval mode only: the BatchNorm layers hold their parameters
                     under the reference's names and are folded into the packed conv weights).
       weight_scale : 'off' (default) or 'auto': in the split mode pack 2^e w per layer and undo the exact power-of-two scale on the

@@ -29,7 +29,7 @@ struct Route { RouteKind kind; int arg; };
 static int check_common(const BsvdConvArgs *a)
 {
     if (!a) { set_error("bsvd_conv3x3: args is NULL"); return -1; }
-    if (a->dtype != BSVD_F32 && a->dtype != BSVD_F16X3) { set_error("bsvd_conv3x3: dtype %d not supported (BSVD_F32, BSVD_F16X3)", a->dtype); return -2; }
+    if (a->dtype != BSVD_F32 && a->dtype != BSVD_F16X3 && a->dtype != BSVD_F16) { set_error("bsvd_conv3x3: dtype %d not supported (BSVD_F32, BSVD_F16X3)", a->dtype); return -2; }
     if (!a->x || !a->y || !(a->w_packed || a->w_wino_packed)) { set_error("bsvd_conv3x3: x, y and w_packed (or w_wino_packed) must be non-NULL"); return -3; }
     if (a->frames <= 0 || a->H <= 0 || a->W <= 0) { set_error("bsvd_conv3x3: bad clip size %d x %d x %d", a->frames, a->H, a->W); return -4; }
     if (a->Cin <= 0 || (a->Cin & 15) || a->Cout <= 0 || (a->Cout & 15)) { set_error("bsvd_conv3x3: Cin=%d / Cout=%d must be positive multiples of 16 (pad channels)", a->Cin, a->Cout); return -5; }
@@ -52,6 +52,20 @@ static bool out_scale_ok(float v, float *resolved)
     return v == 0.0f || (isfinite(v) && v > 0.0f && isnormal(v) && frexpf(v, &e) == 0.5f);
 }
 
+// the split modes share one data contract: BSVD_F16X3 (three MFMA passes) and BSVD_F16 (one pass on the same containers and packs)
+static inline bool split_dtype(int dtype) { return dtype == BSVD_F16X3 || dtype == BSVD_F16; }
+
+// BSVD_F16: what the one-pass mode does not instantiate is refused here, before any launch, with a code of its own and the option's name
+static int check_one_pass(const BsvdConvArgs *a)
+{
+    if (a->dtype != BSVD_F16) return 0;
+    if (a->pre_w_packed) { set_error("bsvd_conv3x3: BSVD_F16: the fused pair (pre_w_packed) is a BSVD_F16X3 kernel only"); return -24; }
+    if (a->x_v || a->y_v) { set_error("bsvd_conv3x3: BSVD_F16: transformed-domain tensors (x_v / y_v = %d / %d) are BSVD_F16X3 options only", a->x_v, a->y_v); return -24; }
+    if (a->w_wino_packed && a->wino_m != 2 && a->wino_m != 42) { set_error("bsvd_conv3x3: BSVD_F16: the Winograd form runs as F(2,3) only (wino_m 2 or 42), got wino_m %d", a->wino_m); return -24; }
+    if (a->x_planar_ch > 0 && !a->head_w_packed) { set_error("bsvd_conv3x3: BSVD_F16: the unfused planar entry (x_planar_ch without head_w_packed) is not an MFMA layer; launch it as BSVD_F16X3"); return -24; }
+    return 0;
+}
+
 // per-layer power-of-two weight scale (ABI v12): checked in front of every launch path; writes the three resolved factors
 static int check_scales(const BsvdConvArgs *a, ConvParams *p)
 {
@@ -62,7 +76,7 @@ static int check_scales(const BsvdConvArgs *a, ConvParams *p)
     for (const auto &s : sc) {
         if (!out_scale_ok(s.v, s.dst)) { set_error("bsvd_conv3x3: %s = %g must be 0 (= 1) or a finite, positive, normal power of two", s.nm, (double)s.v); return -23; }
         if (*s.dst == 1.0f) continue;
-        if (a->dtype != BSVD_F16X3) { set_error("bsvd_conv3x3: %s = %g: the weight scale is an option of BSVD_F16X3", s.nm, (double)s.v); return -23; }
+        if (!split_dtype(a->dtype)) { set_error("bsvd_conv3x3: %s = %g: the weight scale is an option of BSVD_F16X3", s.nm, (double)s.v); return -23; }
         if (!s.pack) { set_error("bsvd_conv3x3: %s = %g without the pack it belongs to", s.nm, (double)s.v); return -23; }
     }
     if (p->out_scale != 1.0f && a->w_wino_packed && a->wino_m >= 10 && a->wino_m < 20) { set_error("bsvd_conv3x3: out_scale is not available for wino_m %d (the all-positions-per-wave measurement kernel)", a->wino_m); return -23; }
@@ -99,9 +113,9 @@ static void fill_params(const BsvdConvArgs *a, ConvParams *p)
     if (p->halo_prev) vec = vec && (a->halo_prev_pstride & 3) == 0 && (a->halo_prev_coff & 3) == 0 && aligned16(a->halo_prev);
     if (p->halo_next) vec = vec && (a->halo_next_pstride & 3) == 0 && (a->halo_next_coff & 3) == 0 && aligned16(a->halo_next);
     p->vec_ok = vec ? 1 : 0;
-    p->ablate = 0;
+    p->one_pass = a->dtype == BSVD_F16 ? 1 : 0;
     p->flip = a->tile_order ? 1 : 0;
-    p->prec = a->dtype == BSVD_F16X3 ? 1 : 0;
+    p->prec = split_dtype(a->dtype) ? 1 : 0;
     p->extra_split = a->extra_split;
     p->y_planar_ch = a->y_planar_ch; p->y_clamp = a->y_clamp; p->y_lo = a->y_lo; p->y_hi = a->y_hi;
     p->head_w = nullptr; p->head_bias = nullptr; p->head_cin = 0;
@@ -115,7 +129,7 @@ static int check_v(const BsvdConvArgs *a, ConvParams *p)
 {
     if (!a->x_v && !a->y_v) return 0;
     const int m = a->wino_m % 10;
-    if (a->dtype != BSVD_F16X3 || !a->w_wino_packed) { set_error("bsvd_conv3x3: x_v / y_v are options of the Winograd form (BSVD_F16X3 + w_wino_packed)"); return -22; }
+    if (!split_dtype(a->dtype) || !a->w_wino_packed) { set_error("bsvd_conv3x3: x_v / y_v are options of the Winograd form (BSVD_F16X3 + w_wino_packed)"); return -22; }
     if ((a->x_v && a->x_v != m) || (a->y_v && a->y_v != m)) { set_error("bsvd_conv3x3: x_v / y_v (%d / %d) must be the form's m = %d", a->x_v, a->y_v, m); return -22; }
     if ((a->x_v && a->x_f32) || (a->y_v && a->y_f32)) { set_error("bsvd_conv3x3: a tensor is either plain fp32 or transformed, not both"); return -22; }
     if (a->y_v && a->epilogue != BSVD_EPI_PLAIN) { set_error("bsvd_conv3x3: y_v needs the PLAIN epilogue"); return -22; }
@@ -134,8 +148,8 @@ static int check_v(const BsvdConvArgs *a, ConvParams *p)
 // x_f32 / y_f32: plain fp32 channels where the split mode carries fp16 pairs
 static int check_f32(const BsvdConvArgs *a)
 {
-    if (a->x_f32 && !(a->dtype == BSVD_F16X3 && a->w_wino_packed)) { set_error("bsvd_conv3x3: x_f32 is the Winograd form's input option (BSVD_F16X3 + w_wino_packed)"); return -21; }
-    if (a->y_f32 && (a->dtype != BSVD_F16X3 || a->y_planar_ch > 0 || a->x_planar_ch > 0 || a->epilogue == BSVD_EPI_RESID || a->pre_w_packed || a->head_w_packed ||
+    if (a->x_f32 && !(split_dtype(a->dtype) && a->w_wino_packed)) { set_error("bsvd_conv3x3: x_f32 is the Winograd form's input option (BSVD_F16X3 + w_wino_packed)"); return -21; }
+    if (a->y_f32 && (!split_dtype(a->dtype) || a->y_planar_ch > 0 || a->x_planar_ch > 0 || a->epilogue == BSVD_EPI_RESID || a->pre_w_packed || a->head_w_packed ||
                      (a->epilogue == BSVD_EPI_PS_ADD && !a->w_wino_packed))) {
         set_error("bsvd_conv3x3: y_f32 needs BSVD_F16X3 and a PLAIN NHWC layer (direct or Winograd form) or a PS_ADD layer of the Winograd form"); return -21;
     }
@@ -181,7 +195,7 @@ static int check_pair(const BsvdConvArgs *a, ConvParams *p, Route *r)
 // fused network entry: planar input -> (x_planar_ch -> Cin conv, act) -> (Cin -> Cout conv, act), one launch
 static int check_entry(const BsvdConvArgs *a, ConvParams *p, Route *r)
 {
-    if (a->dtype != BSVD_F16X3) { set_error("bsvd_conv3x3: the fused entry (head_w_packed) is a BSVD_F16X3 kernel"); return -18; }
+    if (!split_dtype(a->dtype)) { set_error("bsvd_conv3x3: the fused entry (head_w_packed) is a BSVD_F16X3 kernel"); return -18; }
     if (a->x_planar_ch != 3 && a->x_planar_ch != 4) { set_error("bsvd_conv3x3: fused entry supports 3 or 4 planar input channels, got %d", a->x_planar_ch); return -18; }
     if ((a->Cin & 31) || a->Cout > 64 || a->epilogue != BSVD_EPI_PLAIN || a->y_planar_ch > 0) {
         set_error("bsvd_conv3x3: fused entry needs Cin %% 32 == 0, Cout <= 64 and the PLAIN epilogue (Cin %d, Cout %d)", a->Cin, a->Cout); return -18;
@@ -220,7 +234,7 @@ static int check_planar(const BsvdConvArgs *a, ConvParams *p, Route *r)
 static int conv3x3_check(const BsvdConvArgs *a, ConvParams *p, Route *r)
 {
     int rc;
-    if ((rc = check_common(a)) || (rc = check_scales(a, p))) return rc;
+    if ((rc = check_common(a)) || (rc = check_one_pass(a)) || (rc = check_scales(a, p))) return rc;
     fill_params(a, p);
     if ((rc = check_v(a, p)) || (rc = check_f32(a))) return rc;
     if (!aligned16(p->w)) { set_error("bsvd_conv3x3: w_packed / w_wino_packed must be 16-byte aligned"); return -13; }

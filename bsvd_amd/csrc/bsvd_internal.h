@@ -24,9 +24,9 @@ struct ConvParams {
     int32_t act, epilogue;
     int32_t ntx, nty, nct;   // tiles in x, y and output-channel tiles
     int32_t vec_ok;          // 1: every 4-channel group of the gather comes from one source, 16-B aligned
-    int32_t ablate;          // unused; removing it moves the kernarg layout — a change of its own
+    int32_t one_pass;        // host side only (no kernel reads it): 1 = BSVD_F16, the split mode's one-pass instantiations (prec stays 1); in the slot the unused `ablate` held
     int32_t flip;            // 1: walk the tiles in reverse order (BsvdConvArgs.tile_order; see launch_cfg)
-    int32_t prec;            // 0 = exact fp32, 1 = split16 (BSVD_F16X3)
+    int32_t prec;            // 0 = exact fp32, 1 = split16 (BSVD_F16X3, and BSVD_F16 with one_pass)
     int32_t extra_split;     // planar-output layer in split mode: the residual base is a split16 NHWC tensor
     int32_t y_planar_ch;     // > 0: y is planar [frames][y_planar_ch][H][W] fp32 (split mode: written by the MFMA kernel)
     int32_t y_clamp;         // clamp the planar output to [y_lo, y_hi]

@@ -41,6 +41,13 @@
 // 32x32 accumulator tile through a wave-private LDS scratch so that 4 ADJACENT lanes store the 4 x 8 channels of one
 // pixel (128 contiguous bytes) as 16-byte vectors (hi, lo); the exact-fp32 epilogue stores from registers.
 //
+//
+// PREC = 2 (BSVD_F16, one pass): the split16 data contract -- the same tensors, weight packs, staging, halos and epilogues -- with ONE
+// v_mfma_f32_32x32x16_f16 per K=16 block, hi(w) x hi(x).  The lo quads of the patch are still staged to LDS (the containers are what they
+// are) but never read into an MFMA operand, and the lo halves of the weights are never fetched: no result depends on them.  fp16-class
+// accuracy (operands rounded to 11 bits, fp32 accumulation); skip / residual operands are still decoded from full pairs and the result is
+// stored as the canonical pair.  The tiles and their occupancy are the three-pass mode's.
+//
 // Reference ops replaced: see include/bsvd_hip.h (bsvd_conv3x3).
 #include <stdio.h>
 #include <stdlib.h>
@@ -228,7 +235,7 @@ constexpr int occ_of()
     // (3 = 168 VGPRs + a 20-B spill: 2.3 % slower)
     if (C::STRIDE == 2 && PREC == 0 && C::OCC > 2) return 2;
     // split-fp16 single-buffer tile with the next chunk held in registers (see the refill note above): 2 waves/SIMD
-    if (!C::DBUF && PREC == 1 && C::OCC > 2) return 2;
+    if (!C::DBUF && PREC != 0 && C::OCC > 2) return 2;
     return C::OCC;
 }
 
@@ -294,10 +301,11 @@ __global__ __launch_bounds__(256, (PREF ? 2 : occ_of<C, PREC>())) void conv3x3_k
 {
     // ---- tile families: every compile-time choice below is made by one of these names
     constexpr bool FRONT = HEADF || PREF;      // the main conv's input chunks are produced inside the tile, not loaded
-    constexpr bool FAT = PREC == 1 && C::ACC128;       // the 128-accumulator split tile (wide layers, large grids)
-    constexpr bool REGPF = PREC == 1 && !C::DBUF;      // the single-buffer split tile (stride 2): register double buffer, see occ_of
-    constexpr bool APF = PREC == 1 && C::DBUF && (C::NT == 1 || FAT);      // K loop that requests tap k+1's pixel fragments inside tap k
-    constexpr bool LITE = FAT;                 // ... into the SAME registers (no second fragment set); see the APF loop
+    constexpr bool ONEP = PREC == 2;           // one MFMA pass per K = 16 block (BSVD_F16): no lo operand is fetched anywhere below
+    constexpr bool FAT = PREC != 0 && C::ACC128;       // the 128-accumulator split tile (wide layers, large grids)
+    constexpr bool REGPF = PREC != 0 && !C::DBUF;      // the single-buffer split tile (stride 2): register double buffer, see occ_of
+    constexpr bool APF = PREC != 0 && C::DBUF && (C::NT == 1 || FAT);      // K loop that requests tap k+1's pixel fragments inside tap k
+    constexpr bool LITE = FAT && !ONEP;        // ... into the SAME registers (no second fragment set); see the APF loop
     constexpr bool ZSKIP = FAST && FAT && !MIXF;       // all-zero temporal-shift chunks are left out of the K loop
     static_assert(!FAT || (C::DBUF && C::STRIDE == 1 && !FRONT), "the fat tile is a plain double-buffered stride-1 tile");
     static_assert(!FRONT || APF, "both fused fronts run NT == 1 tiles: only the APF loop knows them");
@@ -305,7 +313,7 @@ __global__ __launch_bounds__(256, (PREF ? 2 : occ_of<C, PREC>())) void conv3x3_k
     float *const patch_buf = smem;                              // 2 x PATCH_FLOATS
 
     TL(0);
-    if constexpr (PREC == 1) fp16_saturate_on();      // MODE.FP16_OVFL (bsvd_internal.h): every fp16 conversion of the split mode saturates
+    if constexpr (PREC != 0) fp16_saturate_on();      // MODE.FP16_OVFL (bsvd_internal.h): every fp16 conversion of the split mode saturates
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -375,11 +383,20 @@ __global__ __launch_bounds__(256, (PREF ? 2 : occ_of<C, PREC>())) void conv3x3_k
 #pragma unroll
         for (int mt = 0; mt < C::MT; ++mt)
 #pragma unroll
-            for (int g = 0; g < 2; ++g)
+            for (int g = 0; g < (ONEP ? 1 : 2); ++g)      // (one pass: the hi quads only)
                 a[mt][g] = *reinterpret_cast<const f32x4 *>(a_ptr(pc, ky, kx, mt, g));
     };
     auto mfma32 = [&](const f32x4 (&a)[C::MT][2], const f32x4 (&b)[C::NT][2]) {
-        if constexpr (PREC == 1) {
+        if constexpr (ONEP) {
+#pragma unroll
+            for (int mt = 0; mt < C::MT; ++mt)
+#pragma unroll
+                for (int nt = 0; nt < C::NT; ++nt)
+                    acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, b[nt][0]), __builtin_bit_cast(f16x8, a[mt][0]),
+                                                                         acc[mt][nt], 0, 0, 0);
+            return;
+        }
+        if constexpr (PREC != 0) {
             // split16: a[mt][0] = 8 hi halves, a[mt][1] = 8 lo halves of this lane's k-slots; same for b[nt][.]
 #pragma unroll
             for (int mt = 0; mt < C::MT; ++mt)
@@ -426,8 +443,8 @@ __global__ __launch_bounds__(256, (PREF ? 2 : occ_of<C, PREC>())) void conv3x3_k
                     // fp32: channel c of a source sits at float offset co + (c - first channel of the slice); split16: the
                     // pieces of a full frame keep their place inside their chunk -- co names the chunk (co & ~15: chunk 0 of a neighbour
                     // frame, a later one where the frame sits inside a wider holding tensor), its low bits are not a byte offset
-                    c.soff = PREC == 1 ? (unsigned)(s.next_co & ~15) * 4u : (unsigned)s.next_co * 4u;
-                    c.soff2 = PREC == 1 ? (unsigned)(s.prev_co & ~15) * 4u : (unsigned)s.prev_co * 4u;
+                    c.soff = PREC != 0 ? (unsigned)(s.next_co & ~15) * 4u : (unsigned)s.next_co * 4u;
+                    c.soff2 = PREC != 0 ? (unsigned)(s.prev_co & ~15) * 4u : (unsigned)s.prev_co * 4u;
                     return c;
                 }
             }
@@ -450,7 +467,7 @@ __global__ __launch_bounds__(256, (PREF ? 2 : occ_of<C, PREC>())) void conv3x3_k
 #pragma unroll
             for (int nt = 0; nt < C::NT; ++nt) {
                 b[nt][0] = buf_load4(rs_w, vb[nt], so);
-                b[nt][1] = buf_load4(rs_w, vb[nt], so + g_bytes);
+                if constexpr (!ONEP) b[nt][1] = buf_load4(rs_w, vb[nt], so + g_bytes);      // (one pass: the lo halves of the slab stay where they are)
             }
         };
 
@@ -471,7 +488,7 @@ __global__ __launch_bounds__(256, (PREF ? 2 : occ_of<C, PREC>())) void conv3x3_k
                     if (c.mixed) {
                         const unsigned pix = (unsigned)(gy * p.W + gx);
                         f32x4 a, b;
-                        if constexpr (PREC == 1) {       // pieces: 0 = hi 0..7, 1 = hi 8..15, 2 = lo 0..7, 3 = lo 8..15
+                        if constexpr (PREC != 0) {       // pieces: 0 = hi 0..7, 1 = hi 8..15, 2 = lo 0..7, 3 = lo 8..15
                             const bool second = pq & 1;
                             const unsigned o1 = c.compact1 ? (pq >> 1) * 16u : pq * 16u, o2 = c.compact2 ? (pq >> 1) * 16u : pq * 16u;
                             a = buf_load4(c.rs, ok && !second ? pix * c.ps4 + o1 : BSVD_OOB, c.soff);
@@ -583,7 +600,7 @@ __global__ __launch_bounds__(256, (PREF ? 2 : occ_of<C, PREC>())) void conv3x3_k
         constexpr int RPH = C::TH + 4, RPW = C::TW + 4;
         [[maybe_unused]] unsigned char *const rawp = reinterpret_cast<unsigned char *>(smem) + C::LDS_BYTES;
         [[maybe_unused]] auto head_pair = [&](int pair) {
-            static_assert(!HEADF || (C::QPL && C::STRIDE == 1 && C::DBUF && PREC == 1), "fused entry: quad-planar stride-1 split tile");
+            static_assert(!HEADF || (C::QPL && C::STRIDE == 1 && C::DBUF && PREC != 0), "fused entry: quad-planar stride-1 split tile");
             constexpr int NPIX = C::PH * C::PW, NRT = (NPIX + 31) / 32;
             const float *hb = p.head_bias + pair * 32 + 8 * lh;      // this lane's two groups of 8 channels: +0 (chunk 2*pair), +16 (chunk 2*pair+1)
             const f32x4 bia[2][2] = {{*reinterpret_cast<const f32x4 *>(hb), *reinterpret_cast<const f32x4 *>(hb + 4)},
@@ -607,10 +624,13 @@ __global__ __launch_bounds__(256, (PREF ? 2 : occ_of<C, PREC>())) void conv3x3_k
                     const u32x4 r1 = *reinterpret_cast<const u32x4 *>(rp + (ya * RPW + (ta - 3 * ya)) * 16);
                     const u32x4 r2 = *reinterpret_cast<const u32x4 *>(rp + (yb * RPW + (tb - 3 * yb)) * 16);
                     const f16x8 xh = __builtin_bit_cast(f16x8, u32x4{r1[0], r1[1], r2[0], r2[1]});
-                    const f16x8 xl = __builtin_bit_cast(f16x8, u32x4{r1[2], r1[3], r2[2], r2[3]});
-                    const f16x8 wh = __builtin_bit_cast(f16x8, wbase[sidx * 128]), wl = __builtin_bit_cast(f16x8, wbase[sidx * 128 + 1]);
-                    hacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, xl, hacc, 0, 0, 0);
-                    hacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl, xh, hacc, 0, 0, 0);
+                    const f16x8 wh = __builtin_bit_cast(f16x8, wbase[sidx * 128]);
+                    if constexpr (!ONEP) {
+                        const f16x8 xl = __builtin_bit_cast(f16x8, u32x4{r1[2], r1[3], r2[2], r2[3]});
+                        const f16x8 wl = __builtin_bit_cast(f16x8, wbase[sidx * 128 + 1]);
+                        hacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, xl, hacc, 0, 0, 0);
+                        hacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl, xh, hacc, 0, 0, 0);
+                    }
                     hacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, xh, hacc, 0, 0, 0);
                 }
                 const int gy = iy0 + py, gx = ix0 + px;
@@ -883,8 +903,8 @@ __global__ __launch_bounds__(256, (PREF ? 2 : occ_of<C, PREC>())) void conv3x3_k
             // its own loop: it stages its share of every chunk and meets the chunk barriers, but reads no fragments and issues
             // no MFMAs.  (Guarding the reads / MFMAs of the common loop with a wave-uniform branch instead cost every wave its
             // cross-tap schedule: 19.49 -> 19.83 ms per C1 clip.)
-            // (LITE tiles only, so never with a fused front: their live loop has barriers the staging-only loop lacks)
-            const bool wlive = LITE ? oy0 + 2 * C::MT * wm < p.Ho : true;
+            // (FAT tiles only, so never with a fused front: their live loop has barriers the staging-only loop lacks)
+            const bool wlive = FAT ? oy0 + 2 * C::MT * wm < p.Ho : true;
             if (!wlive) {
                 for (int cb = 0; cb < ncb; ++cb) {
                     ChunkSrc cn = chunk_src(cb + 1 < ncb ? cb + 1 : cb);
@@ -911,9 +931,10 @@ __global__ __launch_bounds__(256, (PREF ? 2 : occ_of<C, PREC>())) void conv3x3_k
                 [[maybe_unused]] f32x4 s0[C::P], s1[C::P], s2[C::P];
 #pragma unroll
                 for (int i = 0; i < C::P; ++i) s1[i] = s2[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-                f32x4 hiA[C::MT], hiB[C::MT], loA[C::MT], loB[C::MT];
+                f32x4 hiA[C::MT], hiB[C::MT];
+                [[maybe_unused]] f32x4 loA[C::MT], loB[C::MT];
                 load_hi(pcur, 0, 0, hiA);
-                load_lo(pcur, 0, 0, loA);
+                if constexpr (!ONEP) load_lo(pcur, 0, 0, loA);
                 // both register rings rotate statically: weights b0 -> b1 -> b2 (filled two steps ahead); patch slices s0 -> s1 -> s2, loaded into
                 // slot tap % 3 and stored one tap later (two taps later: -0.1 %, r02)
 #define BSVD_APF_TAP(T, HC, LC, HN, LN, BCUR, BFILL, SNEW, SOLD)                                                           \
@@ -939,7 +960,31 @@ __global__ __launch_bounds__(256, (PREF ? 2 : occ_of<C, PREC>())) void conv3x3_k
                         if ((T) >= 1 && (T) <= C::NSLICE) slice_store(pnext, ((T) - 1) * C::ROWS_PER_SLICE, SOLD);        \
                     ++step;                                                                                              \
                 }
-                if constexpr (LITE) {
+                // One pass (BSVD_F16): no lo fragments and no pass to hide a request behind, so the hi fragments of tap k + 1 are requested in front
+                // of tap k's MFMAs into the OTHER register set, on every APF tile -- the fat tile's second set takes the registers its lo set had.
+#define BSVD_APF_TAP1(T, HC, HN, BCUR, BFILL, SNEW, SOLD)                                                                  \
+                {                                                                                                        \
+                    load_b(step + 2 < nsteps ? step + 2 : nsteps - 1, BFILL);                                            \
+                    if constexpr (!FRONT) slice_load(cn, (T) * C::ROWS_PER_SLICE, SNEW);    /* rows >= PH: zeros */      \
+                    __builtin_amdgcn_sched_barrier(0);                                                                   \
+                    if constexpr ((T) < 8) load_hi(pcur, ((T) + 1) / 3, ((T) + 1) % 3, HN);                              \
+                    __builtin_amdgcn_sched_barrier(0);                                                                   \
+                    pass(HC, BCUR, 0);                                                      /* hi(w) x hi(x) */           \
+                    if constexpr (!FRONT)                                                                                \
+                        if ((T) >= 1 && (T) <= C::NSLICE) slice_store(pnext, ((T) - 1) * C::ROWS_PER_SLICE, SOLD);        \
+                    ++step;                                                                                              \
+                }
+                if constexpr (ONEP) {
+                    BSVD_APF_TAP1(0, hiA, hiB, b0, b2, s0, s2)
+                    BSVD_APF_TAP1(1, hiB, hiA, b1, b0, s1, s0)
+                    BSVD_APF_TAP1(2, hiA, hiB, b2, b1, s2, s1)
+                    BSVD_APF_TAP1(3, hiB, hiA, b0, b2, s0, s2)
+                    BSVD_APF_TAP1(4, hiA, hiB, b1, b0, s1, s0)
+                    BSVD_APF_TAP1(5, hiB, hiA, b2, b1, s2, s1)
+                    BSVD_APF_TAP1(6, hiA, hiB, b0, b2, s0, s2)
+                    BSVD_APF_TAP1(7, hiB, hiA, b1, b0, s1, s0)
+                    BSVD_APF_TAP1(8, hiA, hiB, b2, b1, s2, s1)
+                } else if constexpr (LITE) {
                     BSVD_APF_TAP(0, hiA, loA, hiA, loA, b0, b2, s0, s2)
                     BSVD_APF_TAP(1, hiA, loA, hiA, loA, b1, b0, s1, s0)
                     BSVD_APF_TAP(2, hiA, loA, hiA, loA, b2, b1, s2, s1)
@@ -961,6 +1006,7 @@ __global__ __launch_bounds__(256, (PREF ? 2 : occ_of<C, PREC>())) void conv3x3_k
                 BSVD_APF_TAP(8, hiA, loA, hiB, loB, b2, b1, s2, s1)
                 }
 #undef BSVD_APF_TAP
+#undef BSVD_APF_TAP1
                 __syncthreads();
             }
             }
@@ -1082,7 +1128,7 @@ __global__ __launch_bounds__(256, (PREF ? 2 : occ_of<C, PREC>())) void conv3x3_k
     //      Everything read from global memory is requested ahead of its use (bias once per tile, the PixelShuffle skip
     //      operand one item ahead), and the item loop is specialised at compile time on (epilogue, activation): at 2-3
     //      waves/SIMD its VALU work is not hidden behind other waves' MFMAs.
-    if constexpr (PREC == 1 && C::NT == 1) {
+    if constexpr (PREC != 0 && C::NT == 1) {
         // network exit in split mode: channels 0..7 of the single 32-channel tile sit in registers 0..7 of elane half 0;
         // the y_planar_ch live ones go out as planar fp32 [frames][ch][H][W] with the residual (DenBlock.none_minus,
         // bsvd_arch.py:408-414) and the callers' clamp (validation_seq_infer.py:24) fused.  32 lanes = 2 rows x 16
@@ -1133,14 +1179,14 @@ __global__ __launch_bounds__(256, (PREF ? 2 : occ_of<C, PREC>())) void conv3x3_k
         }
     }
     const int Cq = p.Cout >> 2;   // PS_ADD: channels of the shuffled output
-    constexpr int NB = PREC == 1 ? 1 : 2;                    // 8-channel groups per (elane, nt) whose bias is kept
+    constexpr int NB = PREC != 0 ? 1 : 2;                    // 8-channel groups per (elane, nt) whose bias is kept
     const int q = elane & 3;
     f32x4 bq[C::NT][NB][2];
 #pragma unroll
     for (int nt = 0; nt < C::NT; ++nt)
 #pragma unroll
         for (int h = 0; h < NB; ++h) {
-            const int n8 = n0 + wn * (C::NT * 32) + nt * 32 + (PREC == 1 ? 8 * q : 8 * (2 * h + elh));
+            const int n8 = n0 + wn * (C::NT * 32) + nt * 32 + (PREC != 0 ? 8 * q : 8 * (2 * h + elh));
             bq[nt][h][0] = bq[nt][h][1] = f32x4{0.f, 0.f, 0.f, 0.f};
             if (p.bias && n8 < p.Cout) {
                 bq[nt][h][0] = *reinterpret_cast<const f32x4 *>(p.bias + n8);
@@ -1155,15 +1201,15 @@ __global__ __launch_bounds__(256, (PREF ? 2 : occ_of<C, PREC>())) void conv3x3_k
         // PLAIN / RESID: everything that depends on the elane is computed once; an item only adds compile-time multiples of
         // the (wave-uniform) row stride -- every instruction of a finishing wave waits for a gap between the co-resident
         // wave's MFMAs, so per-item 64-bit address arithmetic was a measurable part of the epilogue
-        const int l_ox = PREC == 1 ? ox0 + (elane >> 2) : ox0 + (eli & 15);
-        const int l_oy = oy0 + 2 * C::MT * wm + (PREC == 1 ? 0 : (eli >> 4));
-        const int l_ch = n0 + wn * (C::NT * 32) + (PREC == 1 ? 8 * q : 8 * elh);
+        const int l_ox = PREC != 0 ? ox0 + (elane >> 2) : ox0 + (eli & 15);
+        const int l_oy = oy0 + 2 * C::MT * wm + (PREC != 0 ? 0 : (eli >> 4));
+        const int l_ch = n0 + wn * (C::NT * 32) + (PREC != 0 ? 8 * q : 8 * elh);
         const int64_t l_pix = (int64_t)l_oy * p.Wo + l_ox;
         const int64_t rowstride = (int64_t)p.Wo * p.Cout;
         // (BsvdConvArgs.y_f32, PLAIN split layers: plain fp32 channels for a consumer that runs the Winograd form -- no split, no clamp)
-        const bool y_f32 = PREC == 1 && EPI == BSVD_EPI_PLAIN && p.y_f32 != 0;
+        const bool y_f32 = PREC != 0 && EPI == BSVD_EPI_PLAIN && p.y_f32 != 0;
         float *const l_base = p.y + (int64_t)f * p.y_fs + l_pix * p.Cout +
-                              ((PREC == 1 && !y_f32) ? (l_ch >> 4) * 16 + ((l_ch >> 3) & 1) * 4 : l_ch);
+                              ((PREC != 0 && !y_f32) ? (l_ch >> 4) * 16 + ((l_ch >> 3) & 1) * 4 : l_ch);
         // PixelShuffle items of the split mode, Cq % 32 == 0 (every c64 / c32-sized network): a 32-channel MFMA tile lies inside
         // ONE sub-pixel plane, so the sub-pixel, the channel base and the row are wave-uniform and an item's address is
         // (elane part, computed once) + (scalar part).  The generic form below divides by Cq and does 64-bit multiplies per
@@ -1208,15 +1254,15 @@ __global__ __launch_bounds__(256, (PREF ? 2 : occ_of<C, PREC>())) void conv3x3_k
                 }
             }
             if constexpr (EPI != BSVD_EPI_PS_ADD) {
-                const int row = 2 * mt + (PREC == 1 ? sidx : 0);             // rows below the elane's base row
-                const int chadd = nt * 32 + (PREC == 1 ? 0 : 16 * sidx);     // channels (= floats in both layouts) above l_ch
+                const int row = 2 * mt + (PREC != 0 ? sidx : 0);             // rows below the elane's base row
+                const int chadd = nt * 32 + (PREC != 0 ? 0 : 16 * sidx);     // channels (= floats in both layouts) above l_ch
                 t.n8 = t.c8 = l_ch + chadd;
                 t.live = l_oy + row < p.Ho && l_ox < p.Wo && t.n8 < p.Cout;
                 t.opix = l_pix + (int64_t)row * p.Wo;
                 t.dst = l_base + row * rowstride + chadd;
                 return t;
             }
-            if constexpr (PREC == 1) {       // s = which 16 of the tile's 32 pixels; 4 adjacent lanes share a pixel
+            if constexpr (PREC != 0) {       // s = which 16 of the tile's 32 pixels; 4 adjacent lanes share a pixel
                 const int m = (elane + 64 * sidx) >> 2;
                 oy = oy0 + 2 * C::MT * wm + 2 * mt + (m >> 4);
                 ox = ox0 + (m & 15);
@@ -1231,7 +1277,7 @@ __global__ __launch_bounds__(256, (PREF ? 2 : occ_of<C, PREC>())) void conv3x3_k
                 const int sub = t.n8 / Cq;
                 t.c8 = t.n8 - sub * Cq;                                      // first of 8 channels in the shuffled tensor
                 t.opix = (int64_t)(2 * oy + (sub >> 1)) * (2 * p.Wo) + (2 * ox + (sub & 1));
-                t.dst = p.y + (int64_t)f * p.y_fs + t.opix * Cq + (PREC == 1 ? (t.c8 >> 4) * 16 + ((t.c8 >> 3) & 1) * 4 : t.c8);
+                t.dst = p.y + (int64_t)f * p.y_fs + t.opix * Cq + (PREC != 0 ? (t.c8 >> 4) * 16 + ((t.c8 >> 3) & 1) * 4 : t.c8);
             } else {
                 t.c8 = t.n8;
                 t.opix = (int64_t)oy * p.Wo + ox;
@@ -1245,7 +1291,7 @@ __global__ __launch_bounds__(256, (PREF ? 2 : occ_of<C, PREC>())) void conv3x3_k
         auto skip_load = [&](const Item &t, f32x4 (&e)[2]) {
             e[0] = e[1] = f32x4{0.f, 0.f, 0.f, 0.f};
             if (!(has_skip && t.live)) return;
-            if constexpr (PREC == 1) {                                       // split16 skip tensor, same layout as y
+            if constexpr (PREC != 0) {                                       // split16 skip tensor, same layout as y
                 const float *ep = t.esrc ? t.esrc : p.extra + (int64_t)f * p.extra_fs + t.opix * p.extra_ps + coff16(t.c8);
                 e[0] = *reinterpret_cast<const f32x4 *>(ep);
                 e[1] = *reinterpret_cast<const f32x4 *>(ep + 8);
@@ -1279,7 +1325,7 @@ __global__ __launch_bounds__(256, (PREF ? 2 : occ_of<C, PREC>())) void conv3x3_k
                 if (i + 1 < NITEM) resid_load(item_of(i + 1), enxt);
             float v[8];
             TLP_BEGIN();
-            if constexpr (PREC == 1) {
+            if constexpr (PREC != 0) {
                 // (r03: requesting both items of tile k, staging tile k+1 behind those reads with no wait in between -- a wave's LDS
                 //  instructions execute in order -- and only then converting moved nothing, 19.65 vs 19.67 ms: the timeline build
                 //  (tools/timeline.py, -DBSVD_TIMELINE=2) puts 80 % of the epilogue into the convert + store part, 20 % into LDS.)
@@ -1320,7 +1366,7 @@ __global__ __launch_bounds__(256, (PREF ? 2 : occ_of<C, PREC>())) void conv3x3_k
                 }
                 if constexpr (EPI == BSVD_EPI_PS_ADD) {
                     if (has_skip) {
-                        if constexpr (PREC == 1) {
+                        if constexpr (PREC != 0) {
                             const f16x8 eh = __builtin_bit_cast(f16x8, ecur[0]), el = __builtin_bit_cast(f16x8, ecur[1]);
 #pragma unroll
                             for (int j = 0; j < 8; ++j) v[j] += (float)eh[j] + (float)el[j];
@@ -1341,7 +1387,7 @@ __global__ __launch_bounds__(256, (PREF ? 2 : occ_of<C, PREC>())) void conv3x3_k
                     float *dst = t.dst;
                     *reinterpret_cast<f32x4 *>(dst) = f32x4{v[0], v[1], v[2], v[3]};
                     *reinterpret_cast<f32x4 *>(dst + 4) = f32x4{v[4], v[5], v[6], v[7]};
-                } else if constexpr (PREC == 1) {
+                } else if constexpr (PREC != 0) {
                     float *dst = t.dst;
                     constexpr bool bounded = (ACT == BSVD_ACT_RELU6 && EPI == BSVD_EPI_PLAIN);
                     f16x8 hi, lo;
@@ -1381,7 +1427,7 @@ __global__ __launch_bounds__(256, (PREF ? 2 : occ_of<C, PREC>())) void conv3x3_k
     using std::true_type;
     if (p.epilogue == BSVD_EPI_PLAIN) with_act(integral_constant<int, BSVD_EPI_PLAIN>{}, false_type{});
     else if (p.epilogue == BSVD_EPI_PS_ADD) {
-        if constexpr (PREC == 1) {
+        if constexpr (PREC != 0) {
             // UpBlock has no activation (bsvd_arch.py:263-267): the uniform-address form is instantiated for act 'none' only
             if ((Cq & 31) == 0 && (p.extra == nullptr || p.extra_cs == 1) && p.act == BSVD_ACT_NONE)
                 finish(integral_constant<int, BSVD_EPI_PS_ADD>{}, integral_constant<int, BSVD_ACT_NONE>{}, true_type{});
@@ -1398,7 +1444,7 @@ static int launch_cfg(const ConvParams &pin, hipStream_t stream, char *name = nu
 {
     if (name) {      // dry run: report the instantiation bsvd_conv3x3 would launch (used by bench.py's per-kernel timing)
         snprintf(name, name_len, "conv3x3_kernel<%d,%d,%d,%d,%d>[%s]%s%s%s%s", C::MT, C::NT, C::WM, C::WN, C::STRIDE,
-                 PREC == 1 ? "f16x3" : "f32", FAST ? (MIXF ? "[fold8]" : "") : "[generic]", pin.y_planar_ch > 0 ? "[planar out]" : "",
+                 PREC == 2 ? "f16" : PREC == 1 ? "f16x3" : "f32", FAST ? (MIXF ? "[fold8]" : "") : "[generic]", pin.y_planar_ch > 0 ? "[planar out]" : "",
                  HEADF ? "[fused entry]" : "", PREF ? "[fused pair]" : "");
         return 0;
     }
@@ -1423,10 +1469,10 @@ static int launch_cfg(const ConvParams &pin, hipStream_t stream, char *name = nu
 }
 
 // the fused network entry exists for the quad-planar 64-channel tile only (static_assert in head_pair)
-template <class C>
+template <class C, int PREC>
 static int launch_headf(const ConvParams &p, hipStream_t stream, char *name, int name_len)
 {
-    if constexpr (C::QPL) return launch_cfg<C, true, 1, false, true>(p, stream, name, name_len);
+    if constexpr (C::QPL) return launch_cfg<C, true, PREC, false, true>(p, stream, name, name_len);
     else { set_error("bsvd_conv3x3: no fused-entry kernel for this tile"); return -18; }
 }
 
@@ -1456,9 +1502,13 @@ static int launch_f32(const ConvParams &p, hipStream_t stream, char *name, int n
     return launch_cfg<C, true, 0>(p, stream, name, name_len);
 }
 
-int launch_conv3x3(const ConvParams &p, int stride, hipStream_t stream, char *name, int name_len)
+// the split modes: PREC = 1 three passes (BSVD_F16X3), 2 one pass (BSVD_F16) -- the same tile per layer family in both
+template <int PREC>
+static int launch_split(const ConvParams &p, int stride, hipStream_t stream, char *name, int name_len)
 {
-    if (p.prec == 1) {
+    if constexpr (PREC == 2) {       // (the ABI layer refuses it first; the fused pair exists for three passes only)
+        if (p.pre_w) { set_error("bsvd_conv3x3: BSVD_F16 has no fused pair (pre_w_packed)"); return -24; }
+    }
         // split16.  Wide layers: 128-px x 64-ch wave tiles (half the weight bytes per MFMA, twice the step length) at ONE
         // wave per SIMD with the full 512-register file: 430 vs 414 TFLOP/s for the 64x64 tile at 3 waves/SIMD.  (At 2
         // waves/SIMD the same tile needs > 256 registers and spills in the main loop: 10x slower.  <4,1,2,2,1> for
@@ -1480,17 +1530,18 @@ int launch_conv3x3(const ConvParams &p, int stride, hipStream_t stream, char *na
         }
         if (p.head_w) {                  // fused network entry (validated by the ABI layer): the 64-channel tile with the first conv inside
             if (stride != 1 || p.fold != 0 || p.Cout > 64 || (p.Cin & 31)) { set_error("bsvd_conv3x3: fused entry needs stride 1, fold 0, Cin %% 32 == 0, Cout <= 64"); return -18; }
-            return launch_headf<ConvCfg<4, 1, 2, 2, 1>>(p, stream, name, name_len);
+            return launch_headf<ConvCfg<4, 1, 2, 2, 1>, PREC>(p, stream, name, name_len);
         }
         if (p.y_planar_ch > 0) {         // network exit: 256 px x 32 ch tiles, planar fp32 epilogue
             if (stride != 1 || p.fold != 0 || p.Cout > 32) { set_error("bsvd_conv3x3: planar split output needs stride 1, fold 0, Cout <= 32"); return -16; }
             if (p.pre_w && p.Cin > 64) { set_error("bsvd_conv3x3: fused pair needs Cin = 32 or 64 (two 32-channel pairs of the first conv)"); return -20; }
-            if (p.pre_w) return launch_pref<ConvCfg<2, 1, 4, 1, 1>>(p, stream, name, name_len);       // fused pair: out0 -> exit
-            return launch_cfg<ConvCfg<2, 1, 4, 1, 1>, true, 1>(p, stream, name, name_len);
+            if constexpr (PREC == 1) if (p.pre_w) return launch_pref<ConvCfg<2, 1, 4, 1, 1>>(p, stream, name, name_len);       // fused pair: out0 -> exit
+            return launch_cfg<ConvCfg<2, 1, 4, 1, 1>, true, PREC>(p, stream, name, name_len);
         }
         if (p.pre_w) {                   // fused 64-channel pair (validated by the ABI layer): the narrow tile with the first conv inside
             if (stride != 1 || p.fold != 0 || p.Cout > 64 || (p.Cin & 31) || p.Cin > 64) { set_error("bsvd_conv3x3: fused pair needs stride 1, fold 0, Cin = 32 or 64, Cout <= 64"); return -20; }
-            return launch_pref<ConvCfg<4, 1, 2, 2, 1>>(p, stream, name, name_len);
+            if constexpr (PREC == 1) return launch_pref<ConvCfg<4, 1, 2, 2, 1>>(p, stream, name, name_len);
+            else return -24;             // (not reached: refused at the top)
         }
         if (stride == 2) {
             // (the tile's register double buffer reads every chunk from the frame itself: a stride-2 layer with a temporal shift -- none exists in the
@@ -1507,7 +1558,7 @@ int launch_conv3x3(const ConvParams &p, int stride, hipStream_t stream, char *na
             //  frames/s: a workgroup with half the MFMAs pays the same prologue and epilogue.  profiles/r06k_stride2_small_grid_*.txt)
             // (tools/kernel_resources.sh shows a 68-byte private segment for <4,1,1,4,2>: a reservation only -- the kernel's ISA contains no scratch, flat-scratch or
             //  private buffer instruction; 154 VGPRs, three workgroups per CU)
-            return launch_cfg<ConvCfg<4, 1, 1, 4, 2, false>, true, 1>(p, stream, name, name_len);
+            return launch_cfg<ConvCfg<4, 1, 1, 4, 2, false>, true, PREC>(p, stream, name, name_len);
         }
         // The fat tiles run one workgroup per CU, so they need a grid of several rounds of 256; small launches
         // (streaming mode: one frame per launch) keep the 64x64 tiles at 3 workgroups per CU.
@@ -1519,8 +1570,8 @@ int launch_conv3x3(const ConvParams &p, int stride, hipStream_t stream, char *na
         if (p.Cout > 64) {
             // wave tile of the 256-px x 128-ch workgroup: 128 px x 64 ch (256 px x 32 ch -- half the weight bytes per MFMA, twice the pixel-fragment
             // reads -- 19.21 -> 19.60 ms, r03); small grids (single-frame launches): 128 px x 128 ch workgroups (256 px x 64 ch: 291 -> 281 frames/s, r03)
-            if (fat_wide >= fat_min) return launch_cfg<ConvCfg<4, 2, 2, 2, 1>, true, 1>(p, stream, name, name_len);
-            return launch_cfg<ConvCfg<2, 2, 2, 2, 1>, true, 1>(p, stream, name, name_len);
+            if (fat_wide >= fat_min) return launch_cfg<ConvCfg<4, 2, 2, 2, 1>, true, PREC>(p, stream, name, name_len);
+            return launch_cfg<ConvCfg<2, 2, 2, 2, 1>, true, PREC>(p, stream, name, name_len);
         }
         if (p.fold == 8) {                                                                                      // c32-sized nets
             // a half chunk of fp16 pairs has two shapes: the compact [hi x8 | lo x8] slice (pstride 8) and its place inside a split16 frame --
@@ -1533,14 +1584,18 @@ int launch_conv3x3(const ConvParams &p, int stride, hipStream_t stream, char *na
                           p.halo_prev_ps, p.halo_prev_co, p.halo_next_ps, p.halo_next_co);
                 return -17;
             }
-            return launch_cfg<ConvCfg<2, 2, 4, 1, 1>, true, 1, true>(p, stream, name, name_len);
+            return launch_cfg<ConvCfg<2, 2, 4, 1, 1>, true, PREC, true>(p, stream, name, name_len);
         }
         // the 64-channel layers: 128-px x 32-ch wave tiles (<4,1,2,2,1>, 2 waves per SIMD) instead of 64 px x 64 ch at 3 waves per SIMD: half the weight
         // bytes per MFMA (the 64 x 64 tile pulled 4 KB of weights per wave and tap through the L1: ~42 B/clk/CU of its 64), twice the pixel-fragment
         // reads -- a loss with the padded LDS layout (r01), a 7 % gain with the conflict-free quad-planar one (r03: 6.42 -> 5.94 ms per clip).
         // (512-px fat tiles were tried: 9.6 vs 6.8 ms)
-        return launch_cfg<ConvCfg<4, 1, 2, 2, 1>, true, 1>(p, stream, name, name_len);
-    }
+        return launch_cfg<ConvCfg<4, 1, 2, 2, 1>, true, PREC>(p, stream, name, name_len);
+}
+
+int launch_conv3x3(const ConvParams &p, int stride, hipStream_t stream, char *name, int name_len)
+{
+    if (p.prec == 1) return p.one_pass ? launch_split<2>(p, stride, stream, name, name_len) : launch_split<1>(p, stride, stream, name, name_len);
     // exact fp32.  Cout <= 64 (the 540x960-level layers of bsvd_c64): 256 px x 64 ch tiles; wider layers: 128 px x 128 ch.
     // Stride 2 always takes the 128 x 128 tile with a single patch buffer (its 17x33 input patch is what bounds LDS).
     if (stride == 1)

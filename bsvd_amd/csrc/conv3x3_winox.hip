@@ -240,10 +240,14 @@ __device__ __forceinline__ XChunkSrc x_chunk_src(const XTile t, int cbl)      //
 // groups (ds_bpermute), applies BT, splits and stores A x (16 B hi + 16 B lo).  The two positions of a tile's first / last group that need a
 // pixel of the NEIGHBOURING TILE are written as partial sums and recorded -- with the tile's own edge columns -- in the frame's edge block; the
 // patch pass behind the launch (v_patch_kernel) completes them.
-template <int M, int NH, int NTW, int MT, bool PERSIST, int XF, int GTR, int FG = 0, bool YV = false>
+// ONEP (BSVD_F16): one MFMA pass per step, hi(U) x hi(V) -- the operand is the hi of each TRANSFORMED value's pair.  The transform, the LDS planes
+// (hi and lo quarters), the exchange and the epilogue are the three-pass kernel's; the lo quarters are never read into a fragment and the lo
+// halves of the weight slabs are never fetched.
+template <int M, int NH, int NTW, int MT, bool PERSIST, int XF, int GTR, int FG = 0, bool YV = false, bool ONEP = false>
 __device__ __forceinline__ void winox_tile(const ConvParams &p)
 {
     constexpr bool XV = XF == 2;
+    static_assert(!ONEP || (!XV && !YV && !PERSIST), "one pass: pixel-domain tensors, one tile per workgroup");
     static_assert(!YV || (FG == 0 && !PERSIST), "transformed-domain output: the plain tile grid");
     static_assert(!XV || (FG == 0 && !PERSIST), "transformed-domain input: the plain tile grid");
     using C = XCfg<M, NH, NTW, MT, PERSIST, FG == 2>;
@@ -365,7 +369,7 @@ __device__ __forceinline__ void winox_tile(const ConvParams &p)
             // (a channel tile beyond Cout: a zero-size descriptor -- a scalar select, no per-lane address register)
             const __amdgpu_buffer_rsrc_t rs = make_rsrc(p.w, n0 + hh * (NTW * 32) + 32 * nt < p.Cout ? w_bytes : 0u);
             b[nt][0] = buf_load4(rs, vb[nt], so);
-            b[nt][1] = buf_load4(rs, vb[nt], so + g_bytes);
+            if constexpr (!ONEP) b[nt][1] = buf_load4(rs, vb[nt], so + g_bytes);
         }
     };
 
@@ -641,7 +645,7 @@ __device__ __forceinline__ void winox_tile(const ConvParams &p)
             constexpr int NMT = decltype(nmt_)::value;
             f32x4 afr[2][2];          // fragments one (ky, mt) step ahead, see the interleaved schedule
 #pragma unroll
-            for (int pt = 0; pt < 2; ++pt) afr[0][pt] = *reinterpret_cast<const f32x4 *>(pcur + pt * 2 * C::PLANE);
+            for (int pt = 0; pt < (ONEP ? 1 : 2); ++pt) afr[0][pt] = *reinterpret_cast<const f32x4 *>(pcur + pt * 2 * C::PLANE);
             static_for<0, 3 * NMT>([&](auto k_) __attribute__((always_inline)) {
                 constexpr int S_ = decltype(k_)::value, KY = S_ / NMT, mt = S_ % NMT;
                 const f32x4 (&b)[NTW][2] = bring[KY];
@@ -649,13 +653,13 @@ __device__ __forceinline__ void winox_tile(const ConvParams &p)
                     if constexpr (S_ < 3 * NMT - 1) {
                         constexpr int KY1 = (S_ + 1) / NMT, mt1 = (S_ + 1) % NMT;
 #pragma unroll
-                        for (int pt = 0; pt < 2; ++pt)
+                        for (int pt = 0; pt < (ONEP ? 1 : 2); ++pt)
                             afr[(S_ + 1) & 1][pt] = *reinterpret_cast<const f32x4 *>(pcur + pt * 2 * C::PLANE + C::frag_row(mt1, KY1) * 128);
                     }
                     const f32x4 (&a)[2] = afr[S_ & 1];
                     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                    for (int pass = 0; pass < 3; ++pass)
+                    for (int pass = ONEP ? 2 : 0; pass < 3; ++pass)
 #pragma unroll
                         for (int nt = 0; nt < NTW; ++nt) {
                             // pass 0: hi(w) x lo(v), 1: lo(w) x hi(v), 2: hi(w) x hi(v)
@@ -984,6 +988,13 @@ __global__ __launch_bounds__((XCfg<M, NH, NTW, MT, PERSIST>::NTHREADS), (XCfg<M,
     winox_tile<M, NH, NTW, MT, PERSIST, XF, XCfg<M, NH, NTW, MT, PERSIST>::TR, 0, YV>(p);
 }
 
+// the one-pass (BSVD_F16) entry of the same body: F(2,3) on the half-height tile of small grids
+template <int M, int NH, int NTW, int MT, int XF>
+__global__ __launch_bounds__((XCfg<M, NH, NTW, MT, false>::NTHREADS), (XCfg<M, NH, NTW, MT, false>::NW / 4 * XCfg<M, NH, NTW, MT, false>::WGS)) void winox_kernel_1p(const ConvParams p)
+{
+    winox_tile<M, NH, NTW, MT, false, XF, XCfg<M, NH, NTW, MT, false>::TR, 0, false, true>(p);
+}
+
 constexpr bool wx_tail_folds(int m) { return m == 2; }
 
 // 16-row tile grid whose LAST row band has <= 8 live rows (Ho mod 16 in 1..8: the 135-row layers of a 540 x 960 frame, the 120-row ones of
@@ -1008,6 +1019,20 @@ __global__ __launch_bounds__((XCfg<M, NH, NTW, 4, false>::NTHREADS), (XCfg<M, NH
         if (p.nty >= 2 && p.Ho - ty * 16 <= 8) winox_tile<M, NH, NTW, 2, false, XF, 16, 0, YV>(p);
         else winox_tile<M, NH, NTW, 4, false, XF, 16, 0, YV>(p);
     }
+}
+
+// ... and its one-pass (BSVD_F16) twin: the folding form's two bodies (F(2,3), pixel-domain tensors)
+template <int M, int NH, int NTW, int XF>
+__global__ __launch_bounds__((XCfg<M, NH, NTW, 4, false>::NTHREADS), (XCfg<M, NH, NTW, 4, false>::NW / 4)) void winox_kernel_tail_1p(const ConvParams p)
+{
+    static_assert(wx_tail_folds(M) && XF != 2, "one pass: the folding form on pixel-domain tensors");
+    const WxGrid G = wx_grid(p.nty, p.ntx, p.nct, p.Ho, true);
+    const int ntiles = p.frames * G.per_frame;
+    const int bid = blockIdx.x, xcd = bid & 7;
+    int lid = wx_xcd_range(ntiles, xcd).first + (bid >> 3);
+    if (p.flip) lid = ntiles - 1 - lid;
+    if (G.fold && lid % G.per_frame >= G.nreg) winox_tile<M, NH, NTW, 4, false, XF, 16, 2, false, true>(p);
+    else winox_tile<M, NH, NTW, 4, false, XF, 16, 1, false, true>(p);
 }
 
 // The patch pass behind a y_v launch: position 0 of a tile's first group and position A - 1 of its last group need one pixel of the
@@ -1063,10 +1088,22 @@ static int launch_v_patch(const ConvParams &p, hipStream_t stream)
     return (int)hipGetLastError();
 }
 
-template <int M, int NH, int NTW, int MT = 4, bool PERSIST = false, int XF = 0, bool YV = false>
+template <int M, int NH, int NTW, int MT = 4, bool PERSIST = false, int XF = 0, bool YV = false, bool ONEP = false>
 static int launch_winox_cfg(const ConvParams &pin, hipStream_t stream, char *name, int name_len, int max_wgs = BSVD_CUS)
 {
     using C = XCfg<M, NH, NTW, MT, PERSIST>;
+    // BSVD_F16 (one pass): the product's F(2,3) configuration on pixel-domain tensors -- pairs or plain fp32 in, pairs or plain fp32 out
+    if constexpr (!ONEP) {
+        if (pin.one_pass) {
+            if constexpr (XF == 0 && !YV && !PERSIST && C::NTHREADS == 512 && M == 2) {
+                if (pin.x_v || pin.y_v) { set_error("bsvd_conv3x3: BSVD_F16 has no transformed-domain tensors (x_v / y_v)"); return -24; }
+                return launch_winox_cfg<M, NH, NTW, MT, PERSIST, 0, false, true>(pin, stream, name, name_len, max_wgs);
+            } else { set_error("bsvd_conv3x3: BSVD_F16 runs the Winograd form as F(2,3) only (wino_m 2 / 42), got wino_m %d", pin.wino_m); return -24; }
+        }
+    }
+    if constexpr (ONEP) {
+        if constexpr (XF == 0) { if (pin.x_f32) return launch_winox_cfg<M, NH, NTW, MT, PERSIST, 1, false, true>(pin, stream, name, name_len, max_wgs); }
+    } else
     if constexpr (XF == 0 && !PERSIST && C::NTHREADS == 512 && (M == 2 || M == 6)) {      // the product configurations exist for every input format
         if (pin.x_f32) return launch_winox_cfg<M, NH, NTW, MT, PERSIST, 1>(pin, stream, name, name_len, max_wgs);
         if (pin.x_v) return launch_winox_cfg<M, NH, NTW, MT, PERSIST, 2>(pin, stream, name, name_len, max_wgs);
@@ -1077,14 +1114,14 @@ static int launch_winox_cfg(const ConvParams &pin, hipStream_t stream, char *nam
         if (pin.x_f32 || pin.x_v) { set_error("bsvd_conv3x3: x_f32 / x_v are not available for this Winograd variant"); return -19; }
     }
     // transformed-domain OUTPUT: the product's F(6,3) configuration (its tile grid never folds; the epilogue's pixel groups are the reader's)
-    if constexpr (!YV) {
+    if constexpr (!YV && !ONEP) {
         if (pin.y_v) {
             if constexpr (!PERSIST && C::NTHREADS == 512 && M == 6) return launch_winox_cfg<M, NH, NTW, MT, PERSIST, XF, true>(pin, stream, name, name_len, max_wgs);
             else { set_error("bsvd_conv3x3: y_v is not available for this Winograd variant (F(6,3) only)"); return -19; }
         }
     }
     if (name) {
-        snprintf(name, name_len, "winox_kernel<F(%d,3),%dx%d>[f16x3]%s%s%s%s", M, NH, NTW, MT == 2 ? "[8 rows]" : "", PERSIST ? "[persistent]" : "", XF == 2 ? "[V in]" : XF ? "[f32 in]" : "", YV ? "[V out]" : "");
+        snprintf(name, name_len, "winox_kernel<F(%d,3),%dx%d>[%s]%s%s%s%s", M, NH, NTW, ONEP ? "f16" : "f16x3", MT == 2 ? "[8 rows]" : "", PERSIST ? "[persistent]" : "", XF == 2 ? "[V in]" : XF ? "[f32 in]" : "", YV ? "[V out]" : "");
         return 0;
     }
     ConvParams p = pin;
@@ -1099,15 +1136,21 @@ static int launch_winox_cfg(const ConvParams &pin, hipStream_t stream, char *nam
     if constexpr (TAILK) {
         static_assert(XCfg<M, NH, NTW, 4, false, wx_tail_folds(M) && XF != 2 && !YV>::LDS_BYTES == C::LDS_BYTES, "the folded tile's transform buffers fit under the exchange");
         static std::atomic<int> granted_t[MAX_DEVICES];
-        hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void *>(&winox_kernel_tail<M, NH, NTW, XF, YV>), C::LDS_BYTES, granted_t);
+        void (*kern)(const ConvParams);
+        if constexpr (ONEP) kern = &winox_kernel_tail_1p<M, NH, NTW, XF>;
+        else kern = &winox_kernel_tail<M, NH, NTW, XF, YV>;
+        hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void *>(kern), C::LDS_BYTES, granted_t);
         if (e != hipSuccess) return (int)e;
-        hipLaunchKernelGGL((winox_kernel_tail<M, NH, NTW, XF, YV>), dim3((unsigned)nblk), dim3(C::NTHREADS), C::LDS_BYTES, stream, p);
+        hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(C::NTHREADS), C::LDS_BYTES, stream, p);
     } else {
         static std::atomic<int> granted[MAX_DEVICES];
-        hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void *>(&winox_kernel<M, NH, NTW, MT, PERSIST, XF, YV>), C::LDS_BYTES, granted);
+        void (*kern)(const ConvParams);
+        if constexpr (ONEP) kern = &winox_kernel_1p<M, NH, NTW, MT, XF>;
+        else kern = &winox_kernel<M, NH, NTW, MT, PERSIST, XF, YV>;
+        hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void *>(kern), C::LDS_BYTES, granted);
         if (e != hipSuccess) return (int)e;
         const unsigned grid = PERSIST && nblk > max_wgs ? (unsigned)max_wgs : (unsigned)nblk;
-        hipLaunchKernelGGL((winox_kernel<M, NH, NTW, MT, PERSIST, XF, YV>), dim3(grid), dim3(C::NTHREADS), C::LDS_BYTES, stream, p);
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(C::NTHREADS), C::LDS_BYTES, stream, p);
     }
     const int rc = (int)hipGetLastError();
     if constexpr (YV) { if (rc == 0) return launch_v_patch<M>(p, stream); }
@@ -1197,7 +1240,7 @@ static const char *wino_codes_message()
 
 const char *wino_unsupported(const ConvParams &p, int stride)
 {
-    if (p.prec != 1) return "dtype must be BSVD_F16X3";
+    if (p.prec != 1) return "dtype must be BSVD_F16X3";      // (or BSVD_F16: its prec is 1 as well)
     if (!wino_code(p.wino_m)) return wino_codes_message();
     if (stride != 1) return "stride must be 1";
     if (p.epilogue == BSVD_EPI_RESID || p.y_planar_ch > 0 || p.head_w) return "only PLAIN / PS_ADD NHWC layers";

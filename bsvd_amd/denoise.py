@@ -175,12 +175,13 @@ class DenoisingModel:
     # ---- what basicsr.test_pipeline drives (BasicSR/basicsr/test.py:37-41) ----------------------------------------
     def validation(self, dataloader, current_iter, tb_logger, save_img=False):
         """denoising_model.py:192-209.  ``val.fp16`` put the reference's convs under autocast; the engine's arithmetic is
-        fixed by ``network_g.precision`` (split-fp16 3-pass or exact fp32, both fp32-class), so the flag only logs."""
+        fixed by ``network_g.precision`` (split-fp16 3-pass or exact fp32, both fp32-class; 'f16', one fp16 MFMA pass, is the engine's
+        counterpart of that autocast), so the flag only logs."""
         if self.opt.get("dist", False):
             return self.dist_validation(dataloader, current_iter, tb_logger, save_img)
         if (self.opt.get("val") or {}).get("fp16", False):
-            _logger().info("val.fp16 is set: the MI355X engine keeps its own arithmetic (precision=%s)",
-                           getattr(self.net_g, "precision", "?"))
+            _logger().info("val.fp16 is set: the MI355X engine keeps its own arithmetic (precision=%s); network_g.precision: f16 "
+                           "is the engine's counterpart of the reference's fp16 autocast", getattr(self.net_g, "precision", "?"))
         return self.nondist_validation(dataloader, current_iter, tb_logger, save_img)
 
     def dist_validation(self, dataloader, current_iter, tb_logger, save_img):

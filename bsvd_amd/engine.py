@@ -16,6 +16,31 @@ from .netspec import EPI_PLAIN, EPI_PS_ADD, EPI_RESID, out_hwc  # noqa: F401
 from .schedule import Halo  # noqa: F401
 
 
+# the split modes: fp16-pair tensors and weight packs, three MFMA passes ('f16x3', BSVD_F16X3) or one ('f16', BSVD_F16: the same packs,
+# containers, rings, halo packs and edge layers -- only the dtype of the MFMA layers' launches differs)
+SPLIT_PRECISIONS = ("f16x3", "f16")
+
+
+def pack_dtype(precision, edge):
+    """dtype of a layer's direct-form weight pack: split (BSVD_F16X3 -- an F16X3 pack serves 'f16' too; there is no BSVD_F16 pack) for every
+    layer of a split mode but ``edge``, the unfused planar entry, whose fp32 VALU kernel reads an fp32 pack"""
+    return _lib.BSVD_F16X3 if (precision in SPLIT_PRECISIONS and not edge) else _lib.BSVD_F32
+
+
+def launch_dtype(precision, mfma=True):
+    """BsvdConvArgs.dtype of a launch: 'f16' issues BSVD_F16 (one pass) for exactly the MFMA layers; the unfused planar entry
+    (``mfma=False``: an fp32 VALU kernel that only WRITES pairs) keeps BSVD_F16X3"""
+    if precision not in SPLIT_PRECISIONS:
+        return _lib.BSVD_F32
+    return _lib.BSVD_F16 if (precision == "f16" and mfma) else _lib.BSVD_F16X3
+
+
+def is_mfma_launch(x_planar, head):
+    """Does a launch run on the matrix cores?  Every layer of a split mode but the UNFUSED planar entry (planar input without the fused
+    entry's first conv: the fp32 VALU head kernel, which only writes pairs)."""
+    return not (x_planar and head is None)
+
+
 def require_hip():
     if not torch.cuda.is_available():
         raise RuntimeError("bsvd_amd needs a HIP device (MI355X); torch.cuda.is_available() is False. "
@@ -31,7 +56,7 @@ def head_fusable(inc0, inc3, precision):
     """Can InputCvBlock's two convs (bsvd_arch.py:207-216) run as ONE launch (BsvdConvArgs.head_w_packed)?  Split-fp16 mode,
     a 3/4-channel planar entry layer whose (padded) output is whole 32-channel pairs, and a plain stride-1 second conv with
     <= 64 output channels under the same activation.  ``BSVD_FUSE_HEAD=0`` switches the fusion off (A/B measurements)."""
-    return (precision == "f16x3" and os.environ.get("BSVD_FUSE_HEAD", "1") != "0"
+    return (precision in SPLIT_PRECISIONS and os.environ.get("BSVD_FUSE_HEAD", "1") != "0"
             and inc0.cin in (3, 4) and inc0.cin_pad == 16 and inc0.stride == 1 and not inc0.tsm and inc0.epilogue == EPI_PLAIN
             and inc0.cout_pad % 32 == 0 and inc3.cin_pad == inc0.cout_pad and inc3.cout_pad <= 64 and inc3.stride == 1
             and not inc3.tsm and inc3.epilogue == EPI_PLAIN and inc0.act == inc3.act)
@@ -42,6 +67,7 @@ def pair_fusable(a, b, precision):
     temporal shift, a's (padded) output = b's input in ONE or TWO whole 32-channel pairs (the kernel carries two), b with <= 64 output channels and a PLAIN or RESID
     epilogue (the planar exit included).  The 64-channel full-resolution pairs of a DenBlock: OutputCvBlock out0 -> out3 and, where the
     block has no planar entry, InputCvBlock inc0 -> inc3 (bsvd_arch.py:194-226, 287-306)."""
+    # ('f16' has no fused pair: the kernel exists for three passes only)
     return (precision == "f16x3" and a.stride == 1 and b.stride == 1 and not a.tsm and not b.tsm and a.epilogue == EPI_PLAIN
             and b.epilogue in (EPI_PLAIN, EPI_RESID) and a.cin_pad % 16 == 0 and a.cin > 4 and a.cout_pad == b.cin_pad
             and b.cin_pad % 32 == 0 and b.cin_pad <= 64 and b.cout_pad <= 64)
@@ -186,7 +212,7 @@ def wino_eligible(sp, precision, min_cin=WINO_MIN_CIN):
     the temporal-fusion convs (bsvd_arch.py:21-50) and the UpBlock convs (:257-267) at >= 128 input channels.  The choice
     depends on the LAYER only (never on the clip length or frame size), so that every schedule -- clip, stream, sharded,
     MIMO -- runs the same arithmetic per layer and stays bit-identical to the others."""
-    return (precision == "f16x3" and sp.stride == 1 and sp.cin_pad >= max(128, min_cin) and sp.cout_pad % 32 == 0
+    return (precision in SPLIT_PRECISIONS and sp.stride == 1 and sp.cin_pad >= max(128, min_cin) and sp.cout_pad % 32 == 0
             and sp.epilogue in (EPI_PLAIN, EPI_PS_ADD) and (not sp.tsm or sp.fold % 16 == 0))
 
 
@@ -217,13 +243,17 @@ class PackedNet:
         # fp32 accumulator (BsvdConvArgs.out_scale = 2^-e).  {spec.key: e} of the ordinary packs, {second conv's key: e} of the fused
         # entry's first-conv packs; both EMPTY without the option: the packs and launches are then what they always were.  A property of the
         # layer alone, so every schedule stays bit-identical to the others.
-        self.weight_scale = bool(weight_scale) and precision == "f16x3"
+        self.split = precision in SPLIT_PRECISIONS
+        if precision == "f16" and (self.wino_m not in (0, 2) or self.wino_abi not in (0, 2) or fuse_pairs or v_handover):
+            raise ValueError("precision='f16' runs the direct form, the fused entry and F(2,3) only: not with wide_conv=%r, fuse_pairs=%r, "
+                             "v_handover=%r" % (wide_conv, fuse_pairs, v_handover))
+        self.weight_scale = bool(weight_scale) and self.split
         self.scale_exp, self.head_scale_exp = {}, {}
         self.tensors = {}
         self.order = {sp.key: i for i, sp in enumerate(net.layers)}      # position in the layer-major walk (tile_order parity)
         # the entry layer (planar 3/4-channel input) runs on the fp32 VALU kernel and keeps an fp32 pack; every other
         # layer, the planar-output exit layer included, is split-packed for the MFMA kernel
-        edge = {net.layers[0].key} if precision == "f16x3" else set()
+        edge = {net.layers[0].key} if self.split else set()
         with torch.cuda.device(device):
             self._measure_wmax(net, state, edge)
             self._pack_layers(lib, net, state, edge)
@@ -249,7 +279,7 @@ class PackedNet:
         """max |w| of every layer the Winograd form could take and, in the split mode, of every split-packed layer (the small-weight
         notice), in ONE host round trip (a float() per layer is a device sync per layer); then the weight-scale exponents from them."""
         cand = [sp for sp in net.layers if (self.wino_m and wino_eligible(sp, self.precision, self.wino_min_cin)) or
-                (self.precision == "f16x3" and sp.key not in edge)]
+                (self.split and sp.key not in edge)]
         self._wmax = {}
         if cand:
             mx = torch.stack([self._fetch(state, sp.key + ".weight").abs().max() if state[sp.key + ".weight"].numel()
@@ -285,7 +315,7 @@ class PackedNet:
                 continue
             n = lib.bsvd_packed_weight_elems(sp.cin_pad, sp.cout_pad)
             wp = torch.empty(n, dtype=torch.float32, device=device)
-            dt = _lib.BSVD_F16X3 if (self.precision == "f16x3" and sp.key not in edge) else _lib.BSVD_F32
+            dt = pack_dtype(self.precision, sp.key in edge)
             rc = lib.bsvd_pack_weights(w.data_ptr(), b.data_ptr() if b is not None else None, sp.cin, sp.cout,
                                        sp.cin_pad, sp.cout_pad, 1 if sp.epilogue == EPI_PS_ADD else 0, dt,
                                        wp.data_ptr(), bp.data_ptr(), _stream_ptr())
@@ -294,7 +324,7 @@ class PackedNet:
 
     def _warn_small_weights(self, net):
         """Names, once per pack, the split-packed layers whose max |w| is below F16X3_SMALL_WEIGHT."""
-        if self.precision != "f16x3":
+        if not self.split:
             return
         self.small_weight_layers = [(sp.key, self._wmax[sp.key]) for sp in net.layers
                                     if sp.key in self._wmax and 0.0 < self._wmax[sp.key] < F16X3_SMALL_WEIGHT]
@@ -330,8 +360,8 @@ class PackedNet:
         precedence over the fp32 hand-over for those pairs.  Both decided from the layer forms alone."""
         self.f32_out, self.f32_in = set(), set()
         self.v_out, self.v_in = {}, {}
-        f32 = (F32_HANDOVER_DEFAULT if f32_handover is None else f32_handover) and self.precision == "f16x3"
-        vh = (V_HANDOVER_DEFAULT if v_handover is None else v_handover) and self.precision == "f16x3"
+        f32 = (F32_HANDOVER_DEFAULT if f32_handover is None else f32_handover) and self.split
+        vh = (V_HANDOVER_DEFAULT if v_handover is None else v_handover) and self.split
         for blk in (getattr(net, "temp1", None), getattr(net, "temp2", None)):
             if blk is None:
                 continue
@@ -391,8 +421,10 @@ class HipExecutor:
         self.lib = require_hip()
         self.packed = packed
         self.device = packed.device
-        self.split = packed.precision == "f16x3"      # NHWC activations are split16 (hi|lo fp16 pairs per chunk)
-        self.dtype = _lib.BSVD_F16X3 if self.split else _lib.BSVD_F32
+        self.split = packed.precision in SPLIT_PRECISIONS      # NHWC activations are split16 (hi|lo fp16 pairs per chunk)
+        # 'f16': the MFMA layers launch as BSVD_F16 (one pass) on the same packs; the unfused planar entry and the halo helpers keep BSVD_F16X3
+        self.dtype = launch_dtype(packed.precision, mfma=False)
+        self.mfma_dtype = launch_dtype(packed.precision, mfma=True)
         self.launches = 0
         # tuning override of the direct form's fat-tile threshold (BsvdConvArgs.fat_min_wgs; 0 = library default).  Read HERE, on the
         # host side of the ABI, once per executor -- the library itself reads no environment
@@ -406,7 +438,7 @@ class HipExecutor:
     def to_nhwc(self, x_nchw, c_pad):
         """[T,C,H,W] fp32 contiguous device tensor -> [T,H,W,c_pad]"""
         if self.split:
-            raise NotImplementedError("precision='f16x3' enters/leaves through the planar edge layers only")
+            raise NotImplementedError("precision='%s' enters/leaves through the planar edge layers only" % self.packed.precision)
         T, C, H, W = x_nchw.shape
         x_nchw = x_nchw.contiguous()
         y = torch.empty((T, H, W, c_pad), dtype=torch.float32, device=x_nchw.device)
@@ -417,7 +449,7 @@ class HipExecutor:
 
     def to_nchw(self, x_nhwc, c, clamp=None):
         if self.split:
-            raise NotImplementedError("precision='f16x3' enters/leaves through the planar edge layers only")
+            raise NotImplementedError("precision='%s' enters/leaves through the planar edge layers only" % self.packed.precision)
         T, H, W, c_pad = x_nhwc.shape
         y = torch.empty((T, c, H, W), dtype=torch.float32, device=x_nhwc.device)
         lo, hi = (0.0, 0.0) if clamp is None else clamp
@@ -586,7 +618,7 @@ class HipExecutor:
         a.frames, a.H, a.W = T, H, W
         a.Cin, a.Cout = sp.cin_pad, sp.cout_pad
         a.stride = sp.stride
-        a.act, a.epilogue, a.dtype = _lib.ACT[sp.act], sp.epilogue, self.dtype
+        a.act, a.epilogue, a.dtype = _lib.ACT[sp.act], sp.epilogue, (self.mfma_dtype if is_mfma_launch(x_planar, head) else self.dtype)
         # consecutive layers walk their tiles in opposite directions: each starts where its producer finished (Infinity Cache)
         a.tile_order = self.packed.order.get(sp.key, 0) & 1
         a.fat_min_wgs = self.fat_min_wgs

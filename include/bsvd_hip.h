@@ -27,6 +27,7 @@
  *   - dtype: BSVD_F32 is the exact-fp32 mode (v_mfma_f32_32x32x2_f32, bitwise an fmaf chain); BSVD_F16X3 the
  *     split-fp16 3-pass mode (see the enum).  In BSVD_F16X3 the edge layers convert: planar fp32 in -> split16,
  *     split16 -> planar fp32 out; the packed weights of MFMA layers are split16 too (bsvd_pack_weights dtype).
+ *     BSVD_F16 is BSVD_F16X3's data contract with one MFMA pass, hi(w) * hi(x) (see the enum).
  */
 // Arithmetic of BSVD_F32, bit for bit ("bitwise an fmaf chain" above, spelled out; the CPU model oracle/chain_ref.c restates it,
 // tests/test_gpu_fp32_chain.py compares the bits on the MI355X, profiles/fp32_chain_bits.txt is the record).  Per output value, with x the
@@ -58,13 +59,28 @@ extern "C" {
  * an fp16 pair hi = fp16(v), lo = fp16(v - hi); a 16-channel chunk of a pixel is stored as [hi x16 | lo x16] in the
  * same 64 bytes the fp32 layout uses (so shapes, strides and halo offsets are identical), and each K = 16 block is
  * three fp16 MFMAs (hi*hi + lo*hi + hi*lo, fp32 accumulate).  fp32-class accuracy (2-4e-5 max-abs on bsvd_c64) at
- * several times the fp32-MFMA rate.  BSVD_F16 (plain fp16) is reserved and not implemented: it misses the 1e-3
- * parity bar (1-3e-2 measured). */
+ * several times the fp32-MFMA rate.
+ *
+ * BSVD_F16: the BSVD_F16X3 data contract with ONE MFMA pass.  Tensors, halos, strides, rings and weight packs are byte for byte
+ * BSVD_F16X3's -- an F16X3 pack (bsvd_pack_weights / bsvd_pack_weights_wino with wino_m = 2 / bsvd_pack_head_weights) serves BOTH modes;
+ * there is no BSVD_F16 pack and the pack entry points refuse the value.  Each K = 16 block is one fp16 MFMA, hi(w) * hi(x) with
+ * hi = fp16(v) (Winograd form: the hi of each transformed value's pair), fp32 accumulate; the lo halves of weights and activations are
+ * never fetched as MFMA operands and no result depends on them.  Behind the accumulator nothing changes: fmaf(acc, out_scale, bias),
+ * activation, PS_ADD / RESID / clamp in fp32 with the skip / residual operands decoded from FULL pairs, the result stored as the
+ * canonical pair (or plain fp32 for y_f32, planar fp32 at the exit).  fp16-class accuracy: operands rounded to 11 bits (the reference's
+ * own GPU arithmetic is fp16 autocast); it misses the 1e-3 parity bar of the other two modes and is never chosen automatically.
+ * Kernels: every direct-form split tile, the fused entry (head_w_packed) and the F(2,3) Winograd form (wino_m 2 / 42; x_f32 / y_f32 /
+ * PS_ADD included).  Refused with -24 before any launch: pre_w_packed, x_v / y_v, any other wino_m, and the unfused planar entry
+ * (x_planar_ch without head_w_packed: an fp32 VALU kernel, launched as BSVD_F16X3).  The BSVD_F16X3 refusals apply unchanged.
+ *
+ * Numbering.  The value 1 was reserved for a plain-fp16 mode with fp16 STORAGE and stays retired: every library up to and including
+ * this one answers -2 to it (the recorded validation answers pin that).  BSVD_F16 is 3, added without a new BSVD_ABI_VERSION -- the
+ * struct is unchanged; discover the mode with bsvd_conv3x3_variant (-2 from a library that lacks it, else a name with "[f16]"). */
 // "fp32-class" holds for weights around init scale.  lo is an fp16 SUBNORMAL for |v| < 2^-3 (kept by conversions and MFMAs, asserted in
 // tests/test_gpu_range.py), so a pair resolves 2^-24 absolute whatever its size and a layer's relative error is about 2.6e-8 / std(w):
 // 6e-7 at std 0.03, 1e-5 at 2^-4 of that, 1e-4 at 2^-8, plain-fp16 class (2e-3) at 2^-12; a stored output resolves 2^-25 absolute.
 // DESIGN.md 4.1b has the table measured on the MI355X.  The remedy is the per-layer power-of-two weight scale, BsvdConvArgs.out_scale (ABI v12).
-enum { BSVD_F32 = 0, BSVD_F16 = 1, BSVD_F16X3 = 2 };
+enum { BSVD_F32 = 0, /* 1: retired, refused */ BSVD_F16X3 = 2, BSVD_F16 = 3 };
 enum { BSVD_ACT_NONE = 0, BSVD_ACT_RELU = 1, BSVD_ACT_RELU6 = 2 }; /* get_act_function, bsvd_arch.py:185-192 */
 enum {
     BSVD_EPI_PLAIN = 0,   /* y = act(conv + bias)                                                     */
