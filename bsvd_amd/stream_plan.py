@@ -13,7 +13,8 @@ drives the SAME state machine with a recording executor instead:
   identified by a signature (layer, frames, buffer addresses).  In the steady state the signature repeats with the ring
   period (10 steps); pipeline fill / flush steps repeat from clip to clip;
 * a plan seen for the second time is captured into a **HIP graph** (``bsvd_graph_*``, include/bsvd_hip.h) and replayed
-  with one call per step afterwards; until then it is issued with one ``bsvd_conv3x3_batch`` call.  For
+  with one call per step afterwards; until then it is issued with one ``bsvd_conv3x3_batch`` call (the table of step keys holds
+  ``max_graphs`` entries, least recently used out first -- a graph among them is destroyed only after a device drain).  For
   ``streaming_forward`` (the whole list in hand) DenBlock 1 of step k and DenBlock 2 of step k-1 are two parallel
   branches of one graph -- the single-frame launches of the quarter-resolution layers do not fill 256 CUs on their own;
 * with the whole list in hand a step may also carry a **chunk** of n consecutive frames instead of one (ring slots are
@@ -188,11 +189,46 @@ class StreamEngine:
         self.plans = {}
         self.graphs = OrderedDict()
         self.max_graphs = max_graphs
-        self.stats = {"graph_replays": 0, "graph_captures": 0, "batch_launches": 0, "steps": 0}
+        self.stats = {"graph_replays": 0, "graph_captures": 0, "batch_launches": 0, "steps": 0, "graph_evictions": 0}
         self.layerwise = False      # measurement aid: issue every plan layer by layer through ex.conv (per-launch HIP events)
         self._cap = self._side = None
         self._lag = None            # streaming_forward: DenBlock 1's output of the previous step, not yet fed to DenBlock 2
         self._mode = None
+
+    # ---- the graph table's size ----------------------------------------------------------------
+    MIN_GRAPHS = RING_PERIOD + 1
+
+    @property
+    def max_graphs(self):
+        """Entries ``graphs`` may hold (step keys seen once, and captured graphs); the least recently used ones beyond it are evicted.
+        A stream's steady state cycles through RING_PERIOD keys: a table that cannot hold one period of them (and the key that
+        arrives next) would evict every graph before its replay comes round and capture for ever, so a smaller value is refused."""
+        return self._max_graphs
+
+    @max_graphs.setter
+    def max_graphs(self, n):
+        if int(n) < self.MIN_GRAPHS:
+            raise ValueError("max_graphs = %d: the steady state of a stream replays %d graphs in turn (one per step of the ring period); "
+                             "the table must hold more than that, at least %d" % (n, RING_PERIOD, self.MIN_GRAPHS))
+        self._max_graphs = int(n)
+
+    def _drain(self):
+        torch.cuda.synchronize(self.ex.device)
+
+    def _evict(self):
+        """Drops the least recently used entries beyond ``max_graphs``.  A graph executable among them may still be replaying (on the
+        caller's stream, or LiveStream's compute stream): release()'s rule holds here too -- the device is drained before one is
+        destroyed.  (Once per max_graphs distinct step keys: the drain costs nothing that matters.)"""
+        doomed = []
+        while len(self.graphs) > self._max_graphs:
+            _, old = self.graphs.popitem(last=False)
+            if old[0] is not None:
+                doomed.append(old[0])
+        if doomed:
+            self._drain()
+            for exe in doomed:
+                self.ex.lib.bsvd_graph_destroy(exe)
+            self.stats["graph_evictions"] += len(doomed)
 
     # ---- state ---------------------------------------------------------------------------------
     def reset(self):
@@ -215,7 +251,7 @@ class StreamEngine:
         stream, the capture / side streams): the device is drained first, so neither a graph is destroyed under a running
         replay nor a ring block handed back to the caching allocator while a kernel on another stream still uses it."""
         if self.hip:
-            torch.cuda.synchronize(self.ex.device)
+            self._drain()
         for g, _ in self.graphs.values():
             if g is not None:
                 self.ex.lib.bsvd_graph_destroy(g)
@@ -322,15 +358,13 @@ class StreamEngine:
             _lib.check(lib.bsvd_graph_end(cap, ctypes.byref(exe), ctypes.byref(nn)), "bsvd_graph_end")
             self.graphs[key] = (exe, nn.value)
             self.stats["graph_captures"] += 1
-            while len(self.graphs) > self.max_graphs:
-                _, old = self.graphs.popitem(last=False)
-                if old[0] is not None:
-                    lib.bsvd_graph_destroy(old[0])
+            self._evict()
             _lib.check(lib.bsvd_graph_launch(exe, cur), "bsvd_graph_launch")
             self.stats["graph_replays"] += 1
             return
         if g is None:
             self.graphs[key] = (None, 0)          # first sighting: remember, issue directly
+            self._evict()
         for p in list(plans_main) + list(plans_side):
             if p.n:
                 _lib.check(lib.bsvd_conv3x3_batch(p.args, p.n, cur), "bsvd_conv3x3_batch")

@@ -118,6 +118,73 @@ def test_variant_dry_run_reports_dispatch():
     assert variant(Cin=12)[0] == -5
 
 
+def test_last_error_is_per_thread():
+    """include/bsvd_hip.h: "no global state besides a thread-local error string".  Thread A fails 1000 dry runs (bsvd_conv3x3_variant launches
+    nothing), each with a message only that call can have produced, and must read back its own; thread B, whose string holds the text of
+    one failure of its own, makes valid calls beside it and must never see A's text: its string stays what it was."""
+    import threading
+    from bsvd_amd import _lib
+    lib = _lib.load()
+    N = 1000
+    start = threading.Barrier(2)
+    stop = threading.Event()
+    failures = []
+
+    def args(**kw):
+        a = _lib.BsvdConvArgs()
+        a.x = a.y = a.w_packed = 256
+        a.frames, a.H, a.W, a.Cin, a.Cout, a.stride = 1, 8, 8, 64, 64, 1
+        for k, v in kw.items():
+            setattr(a, k, v)
+        return a
+
+    def fails():
+        buf = ctypes.create_string_buffer(96)
+        start.wait(timeout=30)
+        for i in range(N):
+            if stop.is_set():
+                return
+            cin = 16 * i + 1 + i % 15                      # never a multiple of 16, another number in every call
+            rc = lib.bsvd_conv3x3_variant(ctypes.byref(args(Cin=cin)), buf, 96)
+            msg = lib.bsvd_last_error()
+            assert rc == -5 and msg == b"bsvd_conv3x3: Cin=%d / Cout=64 must be positive multiples of 16 (pad channels)" % cin, (i, rc, msg)
+
+    def succeeds():
+        buf = ctypes.create_string_buffer(96)
+        assert lib.bsvd_conv3x3_variant(ctypes.byref(args(stride=3)), buf, 96) == -6
+        mine = lib.bsvd_last_error()
+        assert mine == b"bsvd_conv3x3: stride 3"
+        ok = args()
+        start.wait(timeout=30)
+        for i in range(N):
+            if stop.is_set():
+                return
+            rc = lib.bsvd_conv3x3_variant(ctypes.byref(ok), buf, 96)
+            msg = lib.bsvd_last_error()
+            assert rc == 0 and buf.value.startswith(b"conv3x3_kernel<") and msg == mine, (i, rc, buf.value, msg)
+
+    def guarded(fn):
+        def run():
+            try:
+                fn()
+            except BaseException as e:         # noqa: B036 -- collected and re-raised in the main thread
+                failures.append(e)
+                stop.set()
+                start.abort()
+        return run
+
+    assert lib.bsvd_conv3x3_variant(ctypes.byref(args(stride=5)), ctypes.create_string_buffer(96), 96) == -6
+    threads = [threading.Thread(target=guarded(f)) for f in (fails, succeeds)]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join(timeout=60)
+    assert not any(t.is_alive() for t in threads)
+    if failures:
+        raise failures[0]
+    assert lib.bsvd_last_error() == b"bsvd_conv3x3: stride 5"          # the main thread's own string: untouched by both
+
+
 def test_product_has_no_cpu_fallback():
     """Without a HIP device the product must fail loudly instead of computing on the CPU."""
     import torch

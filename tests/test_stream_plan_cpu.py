@@ -196,3 +196,44 @@ def test_mixing_the_two_step_protocols_inside_one_stream_is_refused():
     eng.feed_lagged(x, (3, None))
     with pytest.raises(RuntimeError):
         eng.feed(x, (3, None))
+
+
+def test_eviction_drains_before_it_destroys_and_keeps_one_period():
+    """``max_graphs``: the least recently used entries go, a graph executable among them only after the device has been drained
+    (release()'s own rule: no graph is destroyed under a running replay); a table smaller than one ring period's working set is
+    refused.  Host logic only: the handles are numbers, the library and the drain are recorded."""
+    net = make_netspec([16, 32, 64], 16, 4, 3, "relu6", 16)
+    st = seeded_state(bsvd_keys([16, 32, 64], 16, 4, 3, 16), 5)
+    ex = OracleExecutor(st)
+    with pytest.raises(ValueError, match="max_graphs"):
+        StreamEngine(net, ex, 8, 8, 4, alloc=lambda shape: torch.zeros(shape), max_graphs=RING_PERIOD)
+    eng = StreamEngine(net, ex, 8, 8, 4, alloc=lambda shape: torch.zeros(shape))
+    assert eng.max_graphs == 1024
+    with pytest.raises(ValueError, match="at least %d" % (RING_PERIOD + 1)):
+        eng.max_graphs = RING_PERIOD
+    assert eng.max_graphs == 1024
+    events = []
+
+    class _Lib:
+        @staticmethod
+        def bsvd_graph_destroy(exe):
+            events.append(("destroy", exe))
+
+    ex.lib = _Lib
+    eng._drain = lambda: events.append(("drain",))
+    eng.max_graphs = RING_PERIOD + 1
+    for i in range(RING_PERIOD + 1):
+        eng.graphs[("k", i)] = (100 + i, 1) if i % 2 else (None, 0)          # captured graphs and keys seen once, oldest first
+    eng._evict()
+    assert not events and len(eng.graphs) == RING_PERIOD + 1                   # at the limit: nothing goes
+    eng.graphs.move_to_end(("k", 1))                                          # a replay makes its key the most recent
+    for i in range(3):
+        eng.graphs[("new", i)] = (200 + i, 1)
+    eng._evict()
+    assert len(eng.graphs) == RING_PERIOD + 1 and ("k", 1) in eng.graphs and all(("new", i) in eng.graphs for i in range(3))
+    assert events == [("drain",), ("destroy", 103)]                           # ("k", 0) and ("k", 2) held no graph; ONE drain, before the destroy
+    assert eng.stats["graph_evictions"] == 1
+    del events[:]
+    eng.graphs[("newer", 0)] = (None, 0)
+    eng._evict()                                                               # the oldest now: ("k", 4), seen once: no graph, no drain
+    assert events == [] and ("k", 4) not in eng.graphs
