@@ -114,6 +114,10 @@ enum {
  * fixed: its second half for halo_prev, its first for halo_next; coff % 16 is ignored (a neighbour frame is passed with coff = fold resp. 0).
  * A pstride that is neither, or a chunk that does not lie inside the pixel (coff - coff % 16 + 16 > pstride), returns -17.
  */
+// Channel counts: every multiple of 16 is served in every dtype, not only the powers of two of the shipped
+// networks (measured at the widths between them: profiles/channel_widths.txt).  Refused: a Cin or Cout that
+// is no positive multiple of 16 (-5); PS_ADD with Cout % 64 != 0 (-10); in the split dtypes a fold that is
+// neither a multiple of 16 nor 8 with Cout <= 64 (-17); w_wino_packed with Cout % 32 != 0 or fold % 16 != 0 (-19).
 typedef struct BsvdConvArgs {
     const void *x;              /* [frames][H][W][Cin]                                              */
     int64_t x_frame_stride;     /* elements between consecutive frames of x                          */

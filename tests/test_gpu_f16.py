@@ -92,6 +92,14 @@ DIRECT = {
     "128-256 ps_add fat": (128, 256, 1, False, "none", 1, 1, [(17, 20)], 1, "conv3x3_kernel<4,2,2,2,1>[f16]"),
     "64-128 stride 2": (64, 128, 2, False, "relu6", 0, 2, [(18, 36), (21, 37)], 0, "conv3x3_kernel<4,1,1,4,2>[f16]"),
     "64-64 fold8": (64, 64, 1, True, "relu6", 0, 3, [(20, 24), (21, 37)], 0, "conv3x3_kernel<2,2,4,1,1>[f16][fold8]"),
+    # widths off the power-of-two grid (tests/test_gpu_widths.py): partly live channel tiles and granules, 3 / 5 / 24 chunks, Cout / 4 = 48
+    "48-48": (48, 48, 1, False, "relu6", 0, 2, [(21, 37)], 0, "conv3x3_kernel<4,1,2,2,1>[f16]"),
+    "128-192": (128, 192, 1, False, "relu6", 0, 2, [(20, 24)], 0, "conv3x3_kernel<2,2,2,2,1>[f16]"),
+    "128-192 fat": (128, 192, 1, False, "relu6", 0, 2, [(20, 24)], 1, "conv3x3_kernel<4,2,2,2,1>[f16]"),
+    "80-64 stride 2": (80, 64, 2, False, "relu6", 0, 2, [(18, 36)], 0, "conv3x3_kernel<4,1,1,4,2>[f16]"),
+    "128-192 ps_add": (128, 192, 1, False, "none", 1, 1, [(17, 21)], 0, "conv3x3_kernel<2,2,2,2,1>[f16]"),
+    "384-384 fold48": (384, 384, 1, True, "relu6", 0, 3, [(10, 19)], 0, "conv3x3_kernel<2,2,2,2,1>[f16]"),
+    "384-384 fold48 fat": (384, 384, 1, True, "relu6", 0, 3, [(10, 19)], 1, "conv3x3_kernel<4,2,2,2,1>[f16]"),      # (the zero-chunk skip: 3 chunks per absent source)
 }
 
 
@@ -235,6 +243,8 @@ WINO = {
     "128-128 fold16": (128, 128, True, "relu6", 0, 3),
     "256-256 fold32": (256, 256, True, "relu", 0, 2),
     "128-256 ps_add": (128, 256, False, "none", 1, 1),
+    "128-192": (128, 192, False, "relu", 0, 2),              # the second 128-channel tile half live
+    "384-384 fold48": (384, 384, True, "relu6", 0, 2),       # 24 chunks, three per temporal source, three channel tiles
 }
 
 

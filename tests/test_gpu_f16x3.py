@@ -70,8 +70,21 @@ CASES = [
 ]
 
 
+def _pad_ch(t, c):
+    """NHWC tensor with zero channels appended up to c (the engine's padding channels); c == the tensor's width: the tensor itself"""
+    return t if t.shape[-1] == c else torch.cat([t, t.new_zeros(t.shape[:-1] + (c - t.shape[-1],))], dim=-1)
+
+
 @pytest.mark.parametrize("cin,cout,stride,tsm,act,epi,T,H,W", CASES)
-def test_layer_split_vs_oracle(cin, cout, stride, tsm, act, epi, T, H, W):
+def test_layer_split_vs_oracle(cin, cout, stride, tsm, act, epi, T, H, W, fat=0, variant=None):
+    check_layer_split(cin, cout, stride, tsm, act, epi, T, H, W, fat, variant)
+
+
+def check_layer_split(cin, cout, stride, tsm, act, epi, T, H, W, fat=0, variant=None):
+    """cin / cout are the REAL channel counts: a count that is no multiple of 16 rides on zero padding channels (netspec.pad16), and the
+    padding channels of the result must hold exact zeros in both halves.  fat: HipExecutor.fat_min_wgs; variant: the instantiation that must run.
+    Returns one row per halo form: (case, halo form, variant, max-abs, needed margin, asserted margin)."""
+    rows = []
     from bsvd_amd.netspec import ConvSpec
     from bsvd_amd.schedule import Halo
     rs = np.random.RandomState(cin + cout + stride)
@@ -79,14 +92,16 @@ def test_layer_split_vs_oracle(cin, cout, stride, tsm, act, epi, T, H, W):
     st = seeded_state([("e0.weight", (16, 4, 3, 3)), ("e0.bias", (16,)), ("l.weight", (cout, cin, 3, 3)),
                        ("l.bias", (cout,)), ("e1.weight", (3, 16, 3, 3)), ("e1.bias", (3,))], 7)
     gex, oex = _exec(_Net(sp), st), OracleExecutor(st, double=True)
-    x = torch.from_numpy(rs.standard_normal((T, H, W, cin)).astype(np.float32))
+    gex.fat_min_wgs = fat or gex.fat_min_wgs
+    gex.record_variants = True
+    x = _pad_ch(torch.from_numpy(rs.standard_normal((T, H, W, cin)).astype(np.float32)), sp.cin_pad)
     Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
     extra = extra_dev = None
     eps, ecs = 0, 1
     if epi == 1:
-        extra = torch.from_numpy(rs.standard_normal((T, 2 * Ho, 2 * Wo, cout // 4)).astype(np.float32))
+        extra = _pad_ch(torch.from_numpy(rs.standard_normal((T, 2 * Ho, 2 * Wo, cout // 4)).astype(np.float32)), sp.out_channels_pad)
         extra = from_split(to_split(extra))            # what the engine would hold
-        extra_dev, eps = to_split(extra).to(_dev()), cout // 4
+        extra_dev, eps = to_split(extra).to(_dev()), sp.out_channels_pad
     elif epi == 2:                                     # temp1's residual base: the planar fp32 network input
         extra = torch.from_numpy(rs.standard_normal((T, 4, Ho, Wo)).astype(np.float32))
         extra_dev, eps, ecs = extra.to(_dev()), 1, Ho * Wo
@@ -102,7 +117,11 @@ def test_layer_split_vs_oracle(cin, cout, stride, tsm, act, epi, T, H, W):
     for hp, hn in halos:
         want = oex.conv(sp, xq, hp, hn, extra, eps, ecs)
         d = lambda h: None if h is None else Halo(to_split(h.t).to(_dev()), h.pstride, h.coff)
-        got = from_split(gex.conv(sp, to_split(x).to(_dev()), d(hp), d(hn), extra_dev, eps, ecs).cpu())
+        raw = gex.conv(sp, to_split(x).to(_dev()), d(hp), d(hn), extra_dev, eps, ecs).cpu()
+        assert variant is None or gex.last_variant == variant, (gex.last_variant, variant)
+        got = from_split(raw)
+        if sp.out_channels_pad > sp.out_channels:      # "padded channels hold zeros" (include/bsvd_hip.h): hi AND lo (PS_ADD: behind a skip tensor whose padding holds zeros)
+            assert all(not h[..., sp.out_channels:].any() for h in S.halves(raw)), "a padding channel of y is not zero"
         err = maxabs(got.numpy(), want.numpy())
         print("layer %s max-abs %.3e (|y| max %.1f)" % ((cin, cout, stride, tsm, epi), err, float(want.abs().max())))
         assert err < TIGHT
@@ -114,7 +133,10 @@ def test_layer_split_vs_oracle(cin, cout, stride, tsm, act, epi, T, H, W):
         cerr = S.chain_err(sp, xq, st["l.weight"], st["l.bias"], halo_prev=hp, halo_next=hn, extra=extra, extra_pstride=eps, extra_cstride=ecs)
         need = S.needed(got, model, cerr)
         print("    vs the three-pass model: needs margin %.3f of %d" % (need, S.M_DIRECT))
+        rows.append(((cin, cout, stride, tsm, act, epi, T, H, W), "none" if hp is None else "compact" if hp.pstride == sp.fold else "frame",
+                     gex.last_variant, err, need, S.M_DIRECT))
         assert need <= S.M_DIRECT, need
+    return rows
 
 
 FAT_CASES = [

@@ -188,3 +188,69 @@ def test_random_wide_layers_with_fp32_handover(seed):
     T, H, W = int(rs.randint(1, 4)), int(rs.randint(1, 21)), int(rs.randint(1, 49))
     print("case", form, cin, cout, tsm, act, epi, T, H, W)
     F.test_wino_layer_with_fp32_input_and_output_vs_oracle(form, cin, cout, tsm, act, epi, T, H, W)
+
+
+# ---- channel widths off the 16 / 32 / 64 / 128 / 256 / 512 grid (tests/test_gpu_widths.py holds the hand-picked cases)
+
+def _draw_widths(rs):
+    """_draw(split=True) with the widths the power-of-two draws leave out; cin / cout are REAL channel counts (40 rides on 48, 70 on 80)"""
+    epi = int(rs.choice([0, 0, 0, 1]))
+    stride = 1 if epi else int(rs.choice([1, 1, 2]))
+    tsm = bool(epi == 0 and stride == 1 and rs.rand() < 0.4)
+    act = str(rs.choice(["relu6", "relu", "none"])) if epi == 0 else "none"
+    T = int(rs.randint(1, 4))
+    H, W = int(rs.randint(1, 41)), int(rs.randint(1, 41))
+    cin = int(rs.choice([128, 256, 384, 512])) if tsm else int(rs.choice([16, 40, 48, 80, 96, 112, 144, 192, 384]))
+    cout = cin if tsm else int(rs.choice([192, 320, 384])) if epi == 1 else int(rs.choice([48, 70, 80, 96, 112, 160, 192, 384]))
+    if max(cin, cout) >= 128:            # keep the CPU oracle quick (the cap of _draw)
+        H, W = min(H, 20), min(W, 24)
+    if max(cin, cout) >= 384:            # ... and the float32 chain of the yardstick: 9 x 384 numpy steps per halo form
+        H, W = min(H, 10), min(W, 17)
+    return cin, cout, stride, tsm, act, epi, T, H, W
+
+
+@pytest.mark.parametrize("seed", range(24))
+def test_random_layer_split_fp16_off_grid_widths(seed):
+    """each draw on the tile family its PADDED width and stride select (launch_split in conv3x3_mfma.hip; these grids stay below the
+    128-accumulator tile's threshold): stride 2 the 128-channel stride-2 tile, Cout <= 64 the narrow tile, wider layers the 128 x 128 one"""
+    import test_gpu_f16x3 as S
+    from bsvd_amd.netspec import pad16
+    args = _draw_widths(np.random.RandomState(11000 + seed))
+    cout, stride = args[1], args[2]
+    variant = "conv3x3_kernel<%s>[f16x3]" % ("4,1,1,4,2" if stride == 2 else "4,1,2,2,1" if pad16(cout) <= 64 else "2,2,2,2,1")
+    print("case", args, variant)
+    S.test_layer_split_vs_oracle(*args, variant=variant)
+
+
+@pytest.mark.parametrize("seed", range(24))
+def test_random_layer_split_fp16_off_grid_widths_on_the_128_accumulator_tile(seed):
+    """the same generator, other seeds, wide layers only (narrow draws are widened by 64 channels), HipExecutor.fat_min_wgs = 1"""
+    import test_gpu_f16x3 as S
+    cin, cout, stride, tsm, act, epi, T, H, W = _draw_widths(np.random.RandomState(12000 + seed))
+    stride = 1
+    if not tsm and cout <= 64:
+        cout += 64              # 48 -> 112
+    if max(cin, cout) >= 128:
+        H, W = min(H, 20), min(W, 24)
+    if max(cin, cout) >= 384:
+        H, W = min(H, 10), min(W, 17)
+    print("case", (cin, cout, stride, tsm, act, epi, T, H, W))
+    S.test_layer_split_vs_oracle(cin, cout, stride, tsm, act, epi, T, H, W, fat=1, variant="conv3x3_kernel<4,2,2,2,1>[f16x3]")
+
+
+@pytest.mark.parametrize("seed", range(24))
+def test_random_wide_layer_winograd_forms_off_grid_widths(seed):
+    """test_random_wide_layer_winograd_forms at cin 128 / 144 / 192 / 384 and cout 96 / 160 / 192 / 384 (PixelShuffle: 4 x 48 / 80 / 96)"""
+    import test_gpu_wino as WN
+    rs = np.random.RandomState(13000 + seed)
+    form = WN.PRODUCT_FORMS[seed % 2]
+    epi = int(rs.choice([0, 0, 1]))
+    tsm = bool(epi == 0 and rs.rand() < 0.5)
+    cin = int(rs.choice([128, 384])) if tsm else int(rs.choice([128, 144, 192, 384]))
+    cout = cin if tsm else 4 * int(rs.choice([48, 80, 96])) if epi == 1 else int(rs.choice([96, 160, 192, 384]))
+    act = str(rs.choice(["relu6", "relu", "none"])) if epi == 0 else "none"
+    T, H, W = int(rs.randint(1, 4)), int(rs.randint(1, 21)), int(rs.randint(1, 49))
+    if max(cin, cout) >= 384:            # the float32 Winograd yardstick on the CPU, four halo forms
+        W = min(W, 24)
+    print("case", form, cin, cout, tsm, act, epi, T, H, W)
+    WN.test_wino_layer_vs_oracle(form, cin, cout, tsm, act, epi, T, H, W)

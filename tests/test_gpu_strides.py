@@ -247,6 +247,13 @@ FAMILIES = {
     "f16x3 entry 3": (_entry, (3, 32, 64, "relu", 2, 21, 37), "[fused entry]", "Ad"),
     "f16x3 pair": (_pair, (64, 2, 19, 21), "<4,1,2,2,1>[f16x3][fused pair]", "AD"),
     "f16x3 pair, exit": (_pair, (3, 2, 19, 21), "<2,1,4,1,1>[f16x3][planar out][fused pair]", "ACD"),
+    # ---- split fp16, direct form, channel widths off the power-of-two grid (tests/test_gpu_widths.py): a masked-channel store behind the last
+    #      pixel of a frame lands in the frame slack or the guard band here, nowhere else in the suite
+    "f16x3 narrow, Cout 48": (_layer, ("f16x3", 48, 48, 1, False, "relu6", 0) + S3, "<4,1,2,2,1>[f16x3]", "AD"),
+    "f16x3 wide, Cout 80": (_layer, ("f16x3", 80, 80, 1, False, "relu6", 0) + S3, "<2,2,2,2,1>[f16x3]", "AD"),
+    "f16x3 fat, Cout 80": (_layer, ("f16x3", 80, 80, 1, False, "relu6", 0) + S3 + ("none", "none", None, "direct", 0, 1), "<4,2,2,2,1>[f16x3]", "A"),
+    "f16x3 PS_ADD, Cout 192": (_layer, ("f16x3", 128, 192, 1, False, "none", 1, 2, 9, 13, "none", "ps"), "<2,2,2,2,1>[f16x3]", "ACD"),
+    "f16x3 stride 2, 80 -> 64": (_layer, ("f16x3", 80, 64, 2, False, "relu6", 0, 2, 21, 19), "<4,1,1,4,2>", "AD"),
     # ---- plain-fp32 hand-over
     "f16x3 direct producer, y_f32": (_layer, ("f16x3", 128, 128, 1, False, "relu6", 0, 3, 19, 50, "none", "none", None, "direct", 0, 0, False, True),
                                      "[f16x3]", "A"),
@@ -269,6 +276,8 @@ for _m, _auto, _fixed in ((2, 2, 42), (6, 6, 46)):
         "F(%d,3) PS_ADD one frame" % _m: (_layer, ("f16x3", 256, 512, 1, False, "none", 1, 1, 27, 50, "none", "ps", None, _w, _auto), _k, "AC"),
         "F(%d,3) f32 in" % _m: (_layer, _tsm + (3, 19, 50, "full", "none", None, _w, _fixed, 0, True, False), _full + "*[f32 in]", "ABD"),
         "F(%d,3) f32 in and out" % _m: (_layer, _tsm + (3, 19, 50, "full", "none", None, _w, _fixed, 0, True, True), _full + "*[f32 in]", "AB"),
+        # (Cout 192: the second 128-channel tile of F(2,3) half live, three 64-channel tiles of F(6,3))
+        "F(%d,3) Cout 192" % _m: (_layer, ("f16x3", 128, 192, 1, False, "relu6", 0, 3, 19, 50, "none", "none", None, _w, _fixed), _full, "AD"),
     })
 
 LAYOUTS = {"A": {}, "B": dict(halo_layout="wide"), "b": dict(halo_layout="compact"), "F": dict(halo_layout="half"), "C": dict(widen_extra=16),

@@ -45,7 +45,13 @@ PRODUCT_FORMS = ["wino2", "wino6"]
 @pytest.mark.parametrize("wide_conv", PRODUCT_FORMS)
 @pytest.mark.parametrize("cin,cout,tsm,act,epi,T,H,W", CASES)
 def test_wino_layer_vs_oracle(wide_conv, cin, cout, tsm, act, epi, T, H, W):
+    check_wino_layer(wide_conv, cin, cout, tsm, act, epi, T, H, W)
+
+
+def check_wino_layer(wide_conv, cin, cout, tsm, act, epi, T, H, W):
+    """Returns one row per halo form (the product forms): (case, halo form, variant, max-abs, needed margin, asserted margin)."""
     from bsvd_amd.netspec import ConvSpec
+    rows = []
     from bsvd_amd.schedule import Halo
     rs = np.random.RandomState(cin + cout + H)
     sp = ConvSpec("l", "l", cin, cout, 1, tsm, act, epi)
@@ -86,7 +92,10 @@ def test_wino_layer_vs_oracle(wide_conv, cin, cout, tsm, act, epi, T, H, W):
             kw = dict(halo_prev=hp, halo_next=hn, extra=extra, extra_pstride=eps, extra_cstride=1)
             need = S.needed(got, S.wino_model(sp, xq, st["l.weight"], m, st["l.bias"], **kw), S.wino_err(sp, xq, st["l.weight"], m, st["l.bias"], **kw))
             print("    vs the Winograd model: needs margin %.3f of %d" % (need, S.M_WINO[m]))
+            rows.append(((wide_conv, cin, cout, tsm, act, epi, T, H, W), "none" if hp is None and hn is None else "next only" if hp is None
+                         else "compact" if hp.pstride == sp.fold else "frame", gex.last_variant, err, need, S.M_WINO[m]))
             assert need <= S.M_WINO[m], need
+    return rows
 
 
 def _conv_with_code(gex, sp, x, code, hp=None, hn=None):

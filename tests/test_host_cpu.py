@@ -103,3 +103,69 @@ def test_out_hwc_is_the_shape_the_oracle_conv_returns(name, H, W, want):
     y = ex.conv(sp, x)
     assert out_hwc(sp, H, W) == want
     assert tuple(y.shape) == (2,) + want == ex.out_shape(sp, x)
+
+
+# the networks of tests/test_gpu_widths.py: widths off the 16 / 32 / 64 / 128 / 256 / 512 grid that the split modes accept
+WIDTH_NETS = {
+    "48-128-384": (dict(chns=[48, 128, 384], mid_ch=40, act="relu6", interm_ch=40), False,
+                   ["d0c1", "d0c2", "d1c1", "d1c2", "u2c1", "u2c2", "up2", "u1c1", "u1c2", "up1"]),
+    "80-64-128": (dict(chns=[80, 64, 128], mid_ch=48, act="relu6", interm_ch=70), False, ["d1c1", "d1c2", "u2c1", "u2c2", "up2"]),
+    "96-256-512": (dict(chns=[96, 256, 512], mid_ch=64, act="relu6", interm_ch=64), False,
+                   ["d0c1", "d0c2", "d1c1", "d1c2", "u2c1", "u2c2", "up2", "u1c1", "u1c2", "up1"]),
+    "blind 64-128-384": (dict(chns=[64, 128, 384], mid_ch=64, act="relu", interm_ch=30, blind=True), True,
+                         ["d0c1", "d0c2", "d1c1", "d1c2", "u2c1", "u2c2", "up2", "u1c1", "u1c2", "up1"]),
+}
+
+
+@pytest.mark.parametrize("name", list(WIDTH_NETS))
+def test_networks_at_widths_off_the_power_of_two_grid(name):
+    """the constructor takes them in both split modes; the entry fuses, and the Winograd form takes a layer, exactly where the netspec's widths
+    say; every ring has the depth stream_plan.ring_depth states and the padded shape netspec.out_hwc states (fold 48 / 64 included);
+    the ring / plan engine equals the clip schedule through the oracle-backed executor."""
+    import bsvd_amd
+    from bsvd_amd.engine import head_fusable, wino_eligible
+    from bsvd_amd.netspec import out_hwc
+    from bsvd_amd.schedule import bsvd_clip
+    from bsvd_amd.stream_plan import StreamEngine, ring_depth
+    kw, fused, wino = WIDTH_NETS[name]
+    for precision in ("f16x3", "f16"):
+        m = bsvd_amd.BSVD(in_ch=4, out_ch=3, norm="none", pretrain_ckpt=None, precision=precision, **kw)
+        assert m.precision == precision
+    net = m.net
+    assert bsvd_amd.BSVD(in_ch=4, out_ch=3, norm="none", pretrain_ckpt=None, **kw).precision == "f16x3"          # ... and 'auto' picks the split mode
+    assert head_fusable(net.temp1["inc0"], net.temp1["inc3"], "f16x3") == fused
+    for blk in (net.temp1, net.temp2):
+        assert [n for n, sp in blk.items() if wino_eligible(sp, "f16x3")] == wino
+        assert all(sp.fold % 16 == 0 or (sp.fold == 8 and sp.cout_pad <= 64) for sp in blk.values())
+        assert all(sp.cin_pad % 16 == 0 and sp.cout_pad % (64 if sp.epilogue == 1 else 16) == 0 for sp in blk.values())
+    blind = kw.get("blind", False)
+    st = seeded_state(bsvd_keys(kw["chns"], kw["mid_ch"], 4, 3, kw["interm_ch"], blind), 23)
+    T, H, W = 5, 8, 12
+    x = torch.from_numpy(np.random.RandomState(7).standard_normal((T, net.net_in_ch, H, W)).astype(np.float32))
+    y0 = bsvd_clip(OracleExecutor(st, double=True), net, x, None, x_planar=True, y_planar=(3, None))
+    eng = StreamEngine(net, OracleExecutor(st, double=True), H, W, net.net_in_ch, alloc=lambda shape: torch.zeros(shape, dtype=torch.float32), poison=True)
+    for blk in (net.temp1, net.temp2):
+        h, w = H, W
+        for lname, sp in blk.items():
+            h, w, c = out_hwc(sp, h, w)
+            ring = eng.rings[sp.key]
+            exit_ = blk is net.temp2 and lname == "out3"
+            assert len(ring) == ring_depth(lname, blk is net.temp1 and lname == "out3", exit_), (lname, len(ring))
+            assert tuple(ring[0].shape) == ((1, 3, h, w) if exit_ else (1, h, w, c)) and c == sp.out_channels_pad, (lname, ring[0].shape)
+    outs = []
+    for t in range(T + net.shift_num):
+        y = eng.feed(x[t:t + 1] if t < T else None, (3, None))
+        outs.append(None if y is None else y.clone())
+    assert eng.feed(None, (3, None)) is None
+    got = torch.cat([o for o in outs if o is not None])
+    err = maxabs(got.numpy(), y0.numpy())
+    print("%s: stream vs clip through the oracle-backed executor: max-abs %.2e (max |y| %.1f)" % (name, err, float(y0.abs().max())))
+    assert got.shape == y0.shape and err < 1e-4 and not bool(torch.isnan(got).any())      # (the bound of the fused-pair test above)
+
+
+def test_widths_the_split_modes_cannot_serve_are_refused():
+    import bsvd_amd
+    for precision in ("f16x3", "f16"):
+        with pytest.raises(ValueError, match="fold"):      # 96- and 192-channel temporal-fusion layers: fold 12 and 24
+            bsvd_amd.BSVD(chns=[48, 96, 192], mid_ch=48, norm="none", interm_ch=48, pretrain_ckpt=None, precision=precision)
+    assert bsvd_amd.BSVD(chns=[48, 96, 192], mid_ch=48, norm="none", interm_ch=48, pretrain_ckpt=None).precision == "fp32"

@@ -334,3 +334,140 @@ def test_mutations_of_the_winograd_forms_violate_the_gpu_bound(m):
     err = S.wino_err(sp, xh + xl, w, m)
     bad = xh + np.where(_cmask(xl.shape, 32), 0.0, xl)
     assert S.excess(S.wino_model(sp, bad, w, m), model, err, M_WINO[m]) > 1.0
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# channel widths off the 16 / 32 / 64 / 128 / 256 / 512 grid (the cases of tests/test_gpu_widths.py)
+
+WIDTH_LAYERS = [
+    # cin, cout, stride, tsm, act, epi, T, H, W: 3, 5, 9 and 24 chunks; Cout % 32 == 16; Cout / 4 = 48 and 80
+    (48, 48, 1, False, "relu6", 0, 1, 5, 6),
+    (80, 64, 2, False, "relu6", 0, 2, 6, 7),
+    (144, 160, 1, False, "none", 0, 1, 4, 5),
+    (128, 192, 1, False, "none", 1, 1, 3, 4),
+    (64, 320, 1, False, "none", 1, 1, 3, 4),
+    (384, 384, 1, True, "relu6", 0, 2, 3, 4),      # fold 48
+]
+
+
+@pytest.mark.parametrize("cin,cout,stride,tsm,act,epi,T,H,W", WIDTH_LAYERS)
+def test_three_passes_within_the_format_terms_at_odd_chunk_widths(cin, cout, stride, tsm, act, epi, T, H, W):
+    test_three_passes_within_the_format_terms_of_float64(cin, cout, stride, tsm, act, epi, T, H, W)
+
+
+def _pad(a, c):
+    return np.concatenate([a, np.zeros(a.shape[:-1] + (c - a.shape[-1],), dtype=a.dtype)], axis=-1)
+
+
+def test_models_at_padded_widths():
+    """40 -> 70 real channels on 48 -> 80 padded ones (and a PixelShuffle layer with 70 real channels per sub-pixel on 80): the models read the
+    real input channels only, return the PADDED width with exact zeros in the padding channels, and agree with the oracle executor."""
+    rs = np.random.RandomState(4070)
+    for sp, T, H, W in ((ConvSpec("l", "l", 40, 70, 1, False, "relu", 0), 1, 7, 9), (ConvSpec("l", "l", 64, 280, 1, False, "none", 1), 1, 3, 4)):
+        w, b = _state(sp, rs)
+        x = _pad(rs.standard_normal((T, H, W, sp.cin)).astype(np.float32), sp.cin_pad)
+        xh, xl = S.pairs(x)
+        kw = {}
+        if sp.epilogue == 1:
+            e = sum(S.pairs(_pad(rs.standard_normal((T, 2 * H, 2 * W, sp.out_channels)).astype(np.float32), sp.out_channels_pad)))
+            kw = dict(extra=e, extra_pstride=sp.out_channels_pad, extra_cstride=1)
+        y = S.direct_three_pass(sp, xh, xl, w, b, **kw)
+        assert y.shape[-1] == sp.out_channels_pad > sp.out_channels and not bool(y[..., sp.out_channels:].any())
+        garbage = xh.copy()
+        garbage[..., sp.cin:] = 7.0                      # the model never reads a padding channel of x
+        assert torch.equal(S.direct_three_pass(sp, garbage, xl, w, b, **kw), y)
+        extra = None if not kw else torch.as_tensor(kw["extra"]).float()
+        want = OracleExecutor({"l.weight": w, "l.bias": b}, double=True).conv(sp, torch.as_tensor(xh + xl).float(), None, None, extra,
+                                                                              kw.get("extra_pstride", 0), 1)
+        quant, lolo = S.format_terms(sp, xh, xl, w)
+        assert want.shape == y.shape
+        assert float((want.double() - y).abs().max()) <= float((quant + lolo).max()) * (1 + 1e-9) + 2.0 ** -23 * max(1.0, float(y.abs().max()))
+        e = S.chain_err(sp, xh + xl, w, b, **kw)
+        assert 0.0 < e < 2.0 ** -24 * (9 * sp.cin) ** 0.5 * 8 * max(1.0, float(y.abs().max()))
+        if sp.epilogue == 0:
+            for m in (2, 6):
+                yw = S.wino_model(sp, xh + xl, w, m, b)
+                assert yw.shape == y.shape and not bool(yw[..., sp.cout:].any())
+                assert float((yw - y).abs().max()) < (2e-5 if m == 6 else 4e-6) * float(y.abs().max())
+                assert 0.0 < S.wino_err(sp, xh + xl, w, m, b)
+
+
+# Three faults a kernel can have at these widths only, applied to the model.  Each is the identity wherever its condition does not hold (an even
+# chunk count, Cout % 32 == 0, a temporal source that exists), so the unmutated cases pass untouched; where it holds, it must violate
+# needed <= M_DIRECT (M_WINO) on the case of tests/test_gpu_widths.py named here -- at that case's own shape.
+
+def _drop_last_chunk_if_odd(sp, xh, xl):
+    """the K loop's chunk-parity double buffer never consumes the last chunk of an odd count"""
+    if (sp.cin_pad // 16) % 2 == 0:
+        return xh, xl
+    m = _cmask(xh.shape, sp.cin_pad - 16)
+    return np.where(m, 0.0, xh), np.where(m, 0.0, xl)
+
+
+def _half_granule_reads_the_row_below(sp, w):
+    """Cout % 32 == 16: the live half of the last 32-channel granule is fed the weights one 16-channel row further down the pack"""
+    if sp.cout_pad % 32 != 16 or sp.cout_pad < 32:
+        return w
+    w = np.array(w)
+    lo, hi = sp.cout_pad - 16, min(sp.cout, sp.cout_pad)
+    w[lo:hi] = w[lo - 16:hi - 16]
+    return w
+
+
+def _zero_skip_shifted_by_one_chunk(sp, xh, xl, T):
+    """the zero-chunk skip of a frame without a `next` (`prev`) source leaves out chunks [1, 1 + fold/16) ([fold/16 + 1, 2 fold/16 + 1)) instead of
+    the group itself: the first chunk behind the absent group is lost.  Returns the plain layer and the GATHERED halves it reads."""
+    plain = ConvSpec(sp.name, sp.key, sp.cin, sp.cout, sp.stride, False, sp.act, sp.epilogue)
+    out = []
+    for half in (xh, xl):
+        g = S.gather(sp, half).permute(0, 2, 3, 1).contiguous().numpy().copy()          # NHWC, temporal shift applied, no halos
+        g[T - 1, ..., sp.fold:sp.fold + 16] = 0.0
+        g[0, ..., 2 * sp.fold:2 * sp.fold + 16] = 0.0
+        out.append(g)
+    return plain, out[0], out[1]
+
+
+def test_width_mutations_violate_the_gpu_bound():
+    rs = np.random.RandomState(48)
+    need = {}
+
+    def operands(cin, cout, stride, tsm, act, epi, T, H, W):
+        sp = ConvSpec("l", "l", cin, cout, stride, tsm, act, epi)
+        w, b = _state(sp, rs)
+        xh, xl = S.pairs(_pad(rs.standard_normal((T, H, W, cin)).astype(np.float32), sp.cin_pad))
+        return sp, w, b, xh, xl
+
+    # -- the last chunk of an odd count: (48,48) narrow tile, 3 chunks; (80,80) 5 chunks; F(2,3) / F(6,3) at (144,160), 9 chunks
+    for case in ((48, 48, 1, False, "relu6", 0, 2, 21, 37), (80, 80, 1, False, "relu6", 0, 2, 20, 24)):
+        sp, w, b, xh, xl = operands(*case)
+        model, err = S.direct_three_pass(sp, xh, xl, w, b), S.chain_err(sp, xh + xl, w, b)
+        need["odd chunk", case] = S.needed(S.direct_three_pass(sp, *_drop_last_chunk_if_odd(sp, xh, xl), w, b), model, err)
+        assert need["odd chunk", case] > M_DIRECT
+    sp, w, b, xh, xl = operands(144, 160, 1, False, "none", 0, 1, 17, 33)
+    for m in (2, 6):
+        model, err = S.wino_model(sp, xh + xl, w, m, b), S.wino_err(sp, xh + xl, w, m, b)
+        need["odd chunk", "F(%d,3)" % m] = S.needed(S.wino_model(sp, sum(_drop_last_chunk_if_odd(sp, xh, xl)), w, m, b), model, err)
+        assert need["odd chunk", "F(%d,3)" % m] > M_WINO[m]
+    sp, w, b, xh, xl = operands(96, 96, 1, False, "none", 0, 2, 17, 21)                   # 6 chunks: the identity
+    assert _drop_last_chunk_if_odd(sp, xh, xl)[0] is xh
+    # -- the half-live granule: (48,48), (80,80) and the padded (40 -> 70)
+    for case in ((48, 48, 1, False, "relu6", 0, 2, 21, 37), (80, 80, 1, False, "relu6", 0, 2, 20, 24), (40, 70, 1, False, "relu", 0, 1, 33, 37)):
+        sp, w, b, xh, xl = operands(*case)
+        model, err = S.direct_three_pass(sp, xh, xl, w, b), S.chain_err(sp, xh + xl, w, b)
+        need["half granule", case] = S.needed(S.direct_three_pass(sp, xh, xl, _half_granule_reads_the_row_below(sp, w), b), model, err)
+        assert need["half granule", case] > M_DIRECT
+    sp, w, b, xh, xl = operands(64, 96, 1, False, "relu6", 0, 1, 21, 37)                  # 96 = 3 x 32: the identity
+    assert _half_granule_reads_the_row_below(sp, w) is w
+    # -- the zero-chunk skip of fold 48: (384,384) with three frames and no halos (both end frames skip a group)
+    case = (384, 384, 1, True, "relu6", 0, 3, 10, 19)
+    sp, w, b, xh, xl = operands(*case)
+    model, err = S.direct_three_pass(sp, xh, xl, w, b), S.chain_err(sp, xh + xl, w, b)
+    plain, gh, gl = _zero_skip_shifted_by_one_chunk(sp, xh, xl, 3)
+    need["skip map", case] = S.needed(S.direct_three_pass(plain, gh, gl, w, b), model, err)
+    assert need["skip map", case] > M_DIRECT
+    # (the unshifted map IS the layer: gathering first and convolving plainly is the model itself)
+    g = [S.gather(sp, h).permute(0, 2, 3, 1).contiguous().numpy() for h in (xh, xl)]
+    assert torch.equal(S.direct_three_pass(plain, g[0], g[1], w, b), model)
+    print("\nmargins the width mutants need (M_DIRECT %d, M_WINO %s):" % (M_DIRECT, M_WINO))
+    for k, v in need.items():
+        print("    %-14s %-50s %.1f" % (k[0], k[1], v))
