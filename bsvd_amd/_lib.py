@@ -23,10 +23,22 @@ EXPORTS = ("bsvd_abi_version", "bsvd_conv_args_size", "bsvd_build_info", "bsvd_l
            "bsvd_v_frame_elems", "bsvd_v_groups", "bsvd_to_v",
            "bsvd_yuv420_frame_bytes", "bsvd_yuv420_to_planar", "bsvd_planar_to_yuv420",
            "bsvd_u8_to_planar_pad", "bsvd_planar_to_u8_crop", "bsvd_yuv420_picture_bytes", "bsvd_yuv420_to_planar_pad",
-           "bsvd_planar_to_yuv420_crop")
+           "bsvd_planar_to_yuv420_crop",
+           "bsvd_yuv_frame_bytes", "bsvd_yuv_to_planar", "bsvd_planar_to_yuv", "bsvd_yuv_to_planar_pad", "bsvd_planar_to_yuv_crop")
 PIX_FMT = {"nv12": 0, "p010": 1}
 MATRIX = {"bt601": 0, "bt709": 1, "bt2020": 2}
 CHROMA = {"nearest": 0, "linear": 1}
+SUB_420, SUB_422, SUB_444 = 0, 1, 2
+LAYOUT_PLANAR, LAYOUT_SEMIPLANAR, LAYOUT_UYVY, LAYOUT_YUYV = 0, 1, 2, 3
+# the surfaces of bsvd_yuv_to_planar / bsvd_planar_to_yuv, by ffmpeg's names: (subsampling, layout, bits, high_bits).  PIX_FMT above stays
+# the table of the bsvd_yuv420_* entry points.
+YUV_FORMATS = {
+    "yuv420p": (SUB_420, LAYOUT_PLANAR, 8, 0), "yuv420p10le": (SUB_420, LAYOUT_PLANAR, 10, 0),
+    "uyvy422": (SUB_422, LAYOUT_UYVY, 8, 0), "yuyv422": (SUB_422, LAYOUT_YUYV, 8, 0),
+    "nv16": (SUB_422, LAYOUT_SEMIPLANAR, 8, 0), "p210le": (SUB_422, LAYOUT_SEMIPLANAR, 10, 1),
+    "yuv422p": (SUB_422, LAYOUT_PLANAR, 8, 0), "yuv422p10le": (SUB_422, LAYOUT_PLANAR, 10, 0),
+    "yuv444p": (SUB_444, LAYOUT_PLANAR, 8, 0), "yuv444p10le": (SUB_444, LAYOUT_PLANAR, 10, 0),
+}
 
 
 class BsvdConvArgs(ctypes.Structure):
@@ -74,6 +86,14 @@ class BsvdYuvDesc(ctypes.Structure):
     """Mirror of ``struct BsvdYuvDesc`` (include/bsvd_hip.h)."""
     _fields_ = [("pix_fmt", ctypes.c_int32), ("matrix", ctypes.c_int32), ("full_range", ctypes.c_int32), ("chroma", ctypes.c_int32),
                 ("row_pitch", ctypes.c_int32), ("reserved", ctypes.c_int32), ("frame_stride", ctypes.c_int64)]
+
+
+class BsvdYuvSurface(ctypes.Structure):
+    """Mirror of ``struct BsvdYuvSurface`` (include/bsvd_hip.h)."""
+    _fields_ = [("subsampling", ctypes.c_int32), ("layout", ctypes.c_int32), ("bits", ctypes.c_int32), ("high_bits", ctypes.c_int32),
+                ("matrix", ctypes.c_int32), ("full_range", ctypes.c_int32), ("chroma", ctypes.c_int32), ("reserved0", ctypes.c_int32),
+                ("pitch", ctypes.c_int32 * 3), ("reserved1", ctypes.c_int32), ("offset", ctypes.c_int64 * 3),
+                ("frame_stride", ctypes.c_int64), ("reserved2", ctypes.c_int64)]
 
 
 class BsvdLibraryError(RuntimeError):
@@ -162,6 +182,17 @@ def load():
     lib.bsvd_yuv420_to_planar_pad.argtypes = [vp, vp, i32, i32, i32, i32, i32, ctypes.POINTER(BsvdYuvDesc), i32, f32, vp]
     lib.bsvd_planar_to_yuv420_crop.restype = ctypes.c_int
     lib.bsvd_planar_to_yuv420_crop.argtypes = [vp, vp, i32, i32, i32, i32, i32, ctypes.POINTER(BsvdYuvDesc), vp]
+    surf = ctypes.POINTER(BsvdYuvSurface)
+    lib.bsvd_yuv_frame_bytes.restype = i64
+    lib.bsvd_yuv_frame_bytes.argtypes = [i32, i32, surf]
+    lib.bsvd_yuv_to_planar.restype = ctypes.c_int
+    lib.bsvd_yuv_to_planar.argtypes = [vp, vp, i32, i32, i32, surf, i32, f32, vp]
+    lib.bsvd_planar_to_yuv.restype = ctypes.c_int
+    lib.bsvd_planar_to_yuv.argtypes = [vp, vp, i32, i32, i32, surf, vp]
+    lib.bsvd_yuv_to_planar_pad.restype = ctypes.c_int
+    lib.bsvd_yuv_to_planar_pad.argtypes = [vp, vp, i32, i32, i32, i32, i32, surf, i32, f32, vp]
+    lib.bsvd_planar_to_yuv_crop.restype = ctypes.c_int
+    lib.bsvd_planar_to_yuv_crop.argtypes = [vp, vp, i32, i32, i32, i32, i32, surf, vp]
     lib.bsvd_workspace_bytes.restype = i64
     lib.bsvd_workspace_bytes.argtypes = [ctypes.POINTER(BsvdConvArgs)]
     if lib.bsvd_abi_version() != ABI_VERSION:

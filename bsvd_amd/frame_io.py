@@ -5,7 +5,9 @@ reference's clamp + round (``tensor2img``, /root/reference/BasicSR/basicsr/utils
 
 The same two steps for YUV 4:2:0 surfaces (NV12, P010), the formats decoders, capture cards and encoders speak:
 ``yuv420_to_input`` / ``output_to_yuv420`` (include/bsvd_hip.h, bsvd_yuv420_to_planar / bsvd_planar_to_yuv420; 1.5 or 3 bytes per
-pixel over PCIe instead of RGB24's 3, and no colour conversion on the host).
+pixel over PCIe instead of RGB24's 3, and no colour conversion on the host).  And for the surfaces a pipeline meets besides those two --
+planar 4:2:0, 4:2:2 (packed, semi-planar, planar) and planar 4:4:4, 8 and 10 bit, by ffmpeg's names (``_lib.YUV_FORMATS``):
+``yuv_to_input`` / ``output_to_yuv`` (bsvd_yuv_to_planar / bsvd_planar_to_yuv), with a pitch and an offset per plane.
 
 Any picture size: the network needs H and W to be multiples of 4, and the reference's callers reflect-pad the fp32 tensor on the right and
 bottom and crop the result (``denoise.pad_to_multiple_of_4`` / ``crop_padding`` here).  ``pad_to=(Hp, Wp)`` on the way in and
@@ -175,4 +177,124 @@ def output_to_yuv420(y, pix_fmt="nv12", matrix="bt709", full_range=False, chroma
         else:
             _lib.check(lib.bsvd_planar_to_yuv420(y.data_ptr(), out.data_ptr(), T, H, W, ctypes.byref(desc), _stream()),
                        "bsvd_planar_to_yuv420")
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------
+# planar, 4:2:2 and 4:4:4 surfaces (include/bsvd_hip.h, BsvdYuvSurface): the names of _lib.YUV_FORMATS, ffmpeg's
+
+def _triple(v, what, planes):
+    """pitches / offsets: None, or up to ``planes`` non-negative ints (None or 0 = tight / directly behind the plane before)"""
+    if v is None:
+        return (0, 0, 0)
+    try:
+        v = [int(x or 0) for x in v]
+    except TypeError:
+        raise ValueError("%s: expected a sequence of up to %d ints, got %r" % (what, planes, v)) from None
+    if len(v) > planes or any(x < 0 for x in v):
+        raise ValueError("%s %r: the layout has %d plane(s); values must not be negative" % (what, v, planes))
+    return tuple(v) + (0,) * (3 - len(v))
+
+
+def yuv_planes(pix_fmt):
+    """planes of a surface format: 3 (Y, Cb, Cr), 2 (Y, interleaved CbCr) or 1 (packed)"""
+    if pix_fmt not in _lib.YUV_FORMATS:
+        raise ValueError("pix_fmt %r: one of %s" % (pix_fmt, ", ".join(sorted(_lib.YUV_FORMATS))))
+    return {_lib.LAYOUT_PLANAR: 3, _lib.LAYOUT_SEMIPLANAR: 2}.get(_lib.YUV_FORMATS[pix_fmt][1], 1)
+
+
+def _yuv_surface(H, W, pix_fmt, matrix, full_range, chroma, pitches, offsets, picture):
+    """-> (BsvdYuvSurface, frame_bytes); ValueError for a name or a size the library would refuse.  picture: a surface for the pad / crop
+    entry points, whose H and W need not be multiples of 4"""
+    planes = yuv_planes(pix_fmt)
+    for what, name, table in (("matrix", matrix, _lib.MATRIX), ("chroma", chroma, _lib.CHROMA)):
+        if name not in table:
+            raise ValueError("%s %r: one of %s" % (what, name, ", ".join(sorted(table))))
+    sub, layout, bits, high = _lib.YUV_FORMATS[pix_fmt]
+    surf = _lib.BsvdYuvSurface(subsampling=sub, layout=layout, bits=bits, high_bits=high, matrix=_lib.MATRIX[matrix],
+                               full_range=1 if full_range else 0, chroma=_lib.CHROMA[chroma])
+    surf.pitch[:] = _triple(pitches, "pitches", planes)
+    surf.offset[:] = _triple(offsets, "offsets", planes)
+    H, W = int(H), int(W)
+    if not picture and (H <= 0 or W <= 0 or H % 4 or W % 4):
+        raise ValueError("%s frame %d x %d: H and W must be positive multiples of 4 (or use pad_to / crop_to)" % (pix_fmt, H, W))
+    nbytes = _lib.load().bsvd_yuv_frame_bytes(H, W, ctypes.byref(surf))
+    if nbytes < 0:
+        raise ValueError("%s frame %d x %d with pitches %s, offsets %s: H and W must be at least 2%s, a pitch (bytes%s) at least its plane's row"
+                         % (pix_fmt, H, W, pitches, offsets, {_lib.SUB_420: " and even", _lib.SUB_422: ", W even"}.get(sub, ""),
+                            ", even" if bits > 8 else ""))
+    return surf, nbytes
+
+
+def yuv_frame_bytes(H, W, pix_fmt, pitches=None, offsets=None):
+    """Bytes of one frame of a planar, 4:2:2 or 4:4:4 surface (``_lib.YUV_FORMATS``): the end of its last plane.  ``pitches``: bytes per
+    row of each plane, None / 0 = tight; ``offsets``: byte offset of each plane from the frame start, None / 0 for planes 1 and 2 =
+    directly behind the plane before.  Any picture size the format can carry (``pad_to`` / ``crop_to``)."""
+    return _yuv_surface(H, W, pix_fmt, "bt709", False, "linear", pitches, offsets, picture=True)[1]
+
+
+def _surface_buffer(buf, T, nbytes, sixteen, what):
+    """a surface buffer [T, >= frame_bytes] -> its frame stride in bytes"""
+    if buf.dtype != torch.uint8 or not buf.is_cuda or buf.dim() != 2 or not buf.is_contiguous():
+        raise ValueError("%s: expected a contiguous uint8 device tensor [T, frame_bytes] (10-bit callers view their uint16 as bytes)" % what)
+    if (T is not None and buf.shape[0] != T) or buf.shape[0] < 1 or buf.shape[1] < nbytes:
+        raise ValueError("%s: shape %s, expected [%s, %d] (or longer rows: frames row-length bytes apart)"
+                         % (what, tuple(buf.shape), "T" if T is None else T, nbytes))
+    if sixteen and buf.shape[1] % 2:
+        raise ValueError("%s: 10-bit frames must be an even number of bytes apart, got %d" % (what, buf.shape[1]))
+    return buf.shape[1]
+
+
+def yuv_to_input(buf, H, W, pix_fmt="yuv420p", matrix="bt709", full_range=False, chroma="linear", sigma=None, pitches=None, pad_to=None,
+                 offsets=None):
+    """``yuv420_to_input`` for the planar, 4:2:2 and 4:4:4 surfaces (pix_fmt: one of ``_lib.YUV_FORMATS``): buf uint8 device tensor
+    [T, frame_bytes] (``yuv_frame_bytes``) -> fp32 [T,3(+1),H,W] RGB, not clamped.  4:2:2 chroma is upsampled along the row only
+    ('linear': co-sited with the even columns), 4:4:4 not at all.  ``pitches`` / ``offsets``: see ``yuv_frame_bytes``.  ``pad_to=(Hp, Wp)``
+    (Wp a multiple of 4; Hp even for 4:2:0): any picture size the format can carry, reflect-padded on the right and bottom after
+    conversion."""
+    surf, nbytes = _yuv_surface(H, W, pix_fmt, matrix, full_range, chroma, pitches, offsets, picture=pad_to is not None)
+    lib = require_hip()
+    surf.frame_stride = _surface_buffer(buf, None, nbytes, surf.bits > 8, "yuv_to_input")
+    T = buf.shape[0]
+    extra = 0 if sigma is None else 1
+    if pad_to is not None:
+        Hp, Wp = _pair(pad_to, "pad_to")
+        y = torch.empty((T, 3 + extra, max(Hp, 0), max(Wp, 0)), dtype=torch.float32, device=buf.device)
+        with torch.cuda.device(buf.device):
+            _lib.check(lib.bsvd_yuv_to_planar_pad(buf.data_ptr(), y.data_ptr(), T, H, W, Hp, Wp, ctypes.byref(surf), extra,
+                                                  float(sigma or 0.0), _stream()), "bsvd_yuv_to_planar_pad")
+        return y
+    y = torch.empty((T, 3 + extra, H, W), dtype=torch.float32, device=buf.device)
+    with torch.cuda.device(buf.device):
+        _lib.check(lib.bsvd_yuv_to_planar(buf.data_ptr(), y.data_ptr(), T, H, W, ctypes.byref(surf), extra, float(sigma or 0.0),
+                                          _stream()), "bsvd_yuv_to_planar")
+    return y
+
+
+def output_to_yuv(y, pix_fmt="yuv420p", matrix="bt709", full_range=False, chroma="linear", pitches=None, out=None, crop_to=None, offsets=None):
+    """``output_to_yuv420`` for the planar, 4:2:2 and 4:4:4 surfaces: y fp32 device tensor [T,3,H,W] RGB -> uint8 [T, frame_bytes].
+    4:2:2 chroma is filtered along the row only ('nearest': mean of the two columns; 'linear': [1 2 1]/4), 4:4:4 not at all.  ``out``: the
+    caller's buffer [T, >= frame_bytes] -- pitch padding, the bytes between planes and between frames are left as they were; without it
+    the result's padding is zero.  ``crop_to=(H, W)``: the surfaces of ``y[..., :H, :W]``."""
+    if y.dtype != torch.float32 or not y.is_cuda or y.dim() != 4 or y.shape[1] != 3:
+        raise ValueError("expected a float32 device tensor [T,3,H,W]")
+    T, _, H, W = y.shape
+    Hp, Wp = H, W
+    if crop_to is not None:
+        H, W = _pair(crop_to, "crop_to")
+    surf, nbytes = _yuv_surface(H, W, pix_fmt, matrix, full_range, chroma, pitches, offsets, picture=crop_to is not None)
+    lib = require_hip()
+    y = y.contiguous()
+    if out is None:
+        out = (torch.zeros if pitches or offsets else torch.empty)((T, nbytes), dtype=torch.uint8, device=y.device)
+    elif out.device != y.device:
+        raise ValueError("output_to_yuv: out is on %s, y on %s" % (out.device, y.device))
+    surf.frame_stride = _surface_buffer(out, T, nbytes, surf.bits > 8, "output_to_yuv(out=)")
+    with torch.cuda.device(y.device):
+        if crop_to is not None:
+            _lib.check(lib.bsvd_planar_to_yuv_crop(y.data_ptr(), out.data_ptr(), T, Hp, Wp, H, W, ctypes.byref(surf), _stream()),
+                       "bsvd_planar_to_yuv_crop")
+        else:
+            _lib.check(lib.bsvd_planar_to_yuv(y.data_ptr(), out.data_ptr(), T, H, W, ctypes.byref(surf), _stream()),
+                       "bsvd_planar_to_yuv")
     return out

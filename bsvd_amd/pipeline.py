@@ -15,7 +15,10 @@ yielded in submission order.
 ``pix_fmt`` selects what crosses PCIe: 'rgb24' (the default, packed RGB uint8 [H,W,3]) or the YUV 4:2:0 surfaces video sources and
 sinks speak, 'nv12' (uint8) and 'p010' (uint16, 10-bit code in the high bits), as arrays [H*3/2, pitch] -- the Y plane's H rows,
 then the H/2 rows of interleaved CbCr; 1.5 (NV12) or 3 (P010) bytes per pixel each way instead of 3, converted by
-``bsvd_yuv420_to_planar`` / ``bsvd_planar_to_yuv420`` where the uint8 kernels run for 'rgb24'.
+``bsvd_yuv420_to_planar`` / ``bsvd_planar_to_yuv420`` where the uint8 kernels run for 'rgb24'.  The planar, 4:2:2 and 4:4:4 surfaces
+('yuv420p', 'yuv420p10le', 'uyvy422', 'yuyv422', 'nv16', 'p210le', 'yuv422p', 'yuv422p10le', 'yuv444p', 'yuv444p10le'; ffmpeg's names)
+cross as 1-D arrays of the tight frame's samples -- what ``ffmpeg -f rawvideo`` emits --, with ``frame_shape=(H, W)`` given at
+construction, converted by ``bsvd_yuv_to_planar`` / ``bsvd_planar_to_yuv``.
 
 ``pad`` selects what happens to a picture whose H or W is no multiple of 4 (the network has two 2x scales): None (the default) refuses
 it; 'reflect' takes any size -- even H and W for the 4:2:0 surfaces -- and does what the reference's callers do around the model
@@ -28,8 +31,9 @@ import collections
 import numpy as np
 import torch
 
-from .frame_io import (_yuv_desc, frames_to_input, network_size, output_to_frames, output_to_yuv420, yuv420_frame_bytes,
-                       yuv420_picture_bytes, yuv420_to_input)
+from . import _lib
+from .frame_io import (_yuv_desc, _yuv_surface, frames_to_input, network_size, output_to_frames, output_to_yuv, output_to_yuv420,
+                       yuv420_frame_bytes, yuv420_picture_bytes, yuv420_to_input, yuv_to_input)
 
 Colour = collections.namedtuple("Colour", "matrix full_range chroma row_pitch width", defaults=("bt709", False, "linear", None, None))
 Colour.__doc__ = """How a YUV surface is to be read and written: matrix 'bt601' | 'bt709' | 'bt2020', full_range (False = limited / "TV"
@@ -84,21 +88,24 @@ class _Rgb24:
         return output_to_frames(y, crop_to=(geom.h, geom.w) if self.pad else None)
 
 
+def _as_colour(colour):
+    if colour is None:
+        return Colour()
+    if isinstance(colour, dict):
+        unknown = set(colour) - set(Colour._fields)
+        if unknown:
+            raise ValueError("colour: unknown key(s) %s (known: %s)" % (sorted(unknown), ", ".join(Colour._fields)))
+        return Colour(**colour)
+    return Colour(*colour)
+
+
 class _Yuv420:
     """NV12 (uint8) / P010 (uint16) arrays [H*3/2, pitch]: staged as the bytes of the surface, converted by bsvd_yuv420_to_planar /
     bsvd_planar_to_yuv420"""
 
     def __init__(self, pix_fmt, colour, pad=None):
         self.pad = _check_pad(pad)
-        if colour is None:
-            colour = Colour()
-        elif isinstance(colour, dict):
-            unknown = set(colour) - set(Colour._fields)
-            if unknown:
-                raise ValueError("colour: unknown key(s) %s (known: %s)" % (sorted(unknown), ", ".join(Colour._fields)))
-            colour = Colour(**colour)
-        else:
-            colour = Colour(*colour)
+        colour = _as_colour(colour)
         self.pix_fmt, self.colour = pix_fmt, colour
         self.dtype = np.dtype(np.uint8 if pix_fmt == "nv12" else np.uint16)
         self.kw = dict(pix_fmt=pix_fmt, matrix=colour.matrix, full_range=bool(colour.full_range), chroma=colour.chroma)
@@ -133,7 +140,44 @@ class _Yuv420:
         return output_to_yuv420(y, row_pitch=geom.row_pitch, crop_to=(geom.h, geom.w) if self.pad else None, **self.kw)
 
 
-def _pixel_format(pix_fmt, colour, pad=None):
+class _YuvSurface:
+    """the planar, 4:2:2 and 4:4:4 formats of _lib.YUV_FORMATS: 1-D arrays of the tight frame's samples (uint8; uint16 for the 10-bit
+    formats) -- the bytes ``ffmpeg -f rawvideo`` emits --, converted by bsvd_yuv_to_planar / bsvd_planar_to_yuv.  A 1-D array does not
+    say its picture size: frame_shape = (H, W) does, at construction."""
+
+    def __init__(self, pix_fmt, colour, pad=None, frame_shape=None):
+        self.pad = _check_pad(pad)
+        colour = _as_colour(colour)
+        if colour.row_pitch is not None or colour.width is not None:
+            raise ValueError("pix_fmt %r takes tight 1-D frames: colour.row_pitch / colour.width are for 'nv12' / 'p010' "
+                             "(pitched surfaces: frame_io.yuv_to_input(pitches=))" % (pix_fmt,))
+        if frame_shape is None:
+            raise ValueError("pix_fmt %r frames are 1-D arrays of samples: give frame_shape=(H, W)" % (pix_fmt,))
+        try:
+            self.h, self.w = int(frame_shape[0]), int(frame_shape[1])
+        except (TypeError, ValueError, IndexError):
+            raise ValueError("frame_shape: expected (H, W), got %r" % (frame_shape,)) from None
+        self.pix_fmt, self.colour = pix_fmt, colour
+        self.dtype = np.dtype(np.uint16 if _lib.YUV_FORMATS[pix_fmt][2] > 8 else np.uint8)
+        self.kw = dict(pix_fmt=pix_fmt, matrix=colour.matrix, full_range=bool(colour.full_range), chroma=colour.chroma)
+        self.nbytes = _yuv_surface(self.h, self.w, pitches=None, offsets=None, picture=bool(self.pad), **self.kw)[1]   # names and size fail here
+        self.samples = self.nbytes // self.dtype.itemsize
+        self.net = _padded_size(self.h, self.w, pix_fmt) if self.pad else (self.h, self.w)
+
+    def geometry(self, a, clip):
+        if a.dtype != self.dtype or a.ndim != (2 if clip else 1) or a.shape[-1] != self.samples:
+            raise ValueError("expected %s %s [%s%d] (the tight %d x %d frame's samples), got %s %s"
+                             % (self.pix_fmt, self.dtype.name, "T," if clip else "", self.samples, self.h, self.w, a.dtype, a.shape))
+        return _Geometry(self.h, self.w, (a.shape[0], self.nbytes) if clip else (self.nbytes,), None, *self.net)
+
+    def to_input(self, dev_in, geom, sigma):
+        return yuv_to_input(dev_in, geom.h, geom.w, sigma=sigma, pad_to=(geom.net_h, geom.net_w) if self.pad else None, **self.kw)
+
+    def to_output(self, y, geom):
+        return output_to_yuv(y, crop_to=(geom.h, geom.w) if self.pad else None, **self.kw)
+
+
+def _pixel_format(pix_fmt, colour, pad=None, frame_shape=None):
     _check_pad(pad)
     if pix_fmt == "rgb24":
         if colour is not None:
@@ -141,7 +185,9 @@ def _pixel_format(pix_fmt, colour, pad=None):
         return _Rgb24(pad)
     if pix_fmt in ("nv12", "p010"):
         return _Yuv420(pix_fmt, colour, pad)
-    raise ValueError("pix_fmt %r: one of 'rgb24', 'nv12', 'p010'" % (pix_fmt,))
+    if pix_fmt in _lib.YUV_FORMATS:
+        return _YuvSurface(pix_fmt, colour, pad, frame_shape)
+    raise ValueError("pix_fmt %r: one of 'rgb24', 'nv12', 'p010', %s" % (pix_fmt, ", ".join(repr(n) for n in sorted(_lib.YUV_FORMATS))))
 
 
 class _Slot:
@@ -174,12 +220,14 @@ class ClipPipeline:
     """model: a bsvd_amd.BSVD on a HIP device.  sigma: noise std in [0,1] units for the constant noise map (None for a
     blind model).  depth >= 2 overlaps the transfers of one clip with the forward of another.  pix_fmt 'rgb24' | 'nv12' | 'p010' and
     colour (a ``Colour`` or a dict of its fields; YUV only): what ``submit`` takes and the results are, see the module docstring.
-    pad None | 'reflect': 'reflect' takes pictures of any size (even H and W for YUV), padded and cropped on the device."""
+    pad None | 'reflect': 'reflect' takes pictures of any size (even H and W for YUV), padded and cropped on the device.
+    pix_fmt 'yuv420p' | 'yuv420p10le' | 'uyvy422' | 'yuyv422' | 'nv16' | 'p210le' | 'yuv422p' | 'yuv422p10le' | 'yuv444p' | 'yuv444p10le'
+    with frame_shape=(H, W): clips are [T, n] arrays of the tight frames' samples (uint8, uint16 for 10 bit), as ffmpeg's rawvideo."""
 
-    def __init__(self, model, sigma=None, depth=2, pix_fmt="rgb24", colour=None, pad=None):
+    def __init__(self, model, sigma=None, depth=2, pix_fmt="rgb24", colour=None, pad=None, frame_shape=None):
         if depth < 1:
             raise ValueError("depth must be >= 1")
-        self.fmt = _pixel_format(pix_fmt, colour, pad)
+        self.fmt = _pixel_format(pix_fmt, colour, pad, frame_shape)
         self.model, self.sigma = model, sigma
         self.device = model._device()
         if self.device.type != "cuda":
@@ -265,6 +313,10 @@ class LiveStream:
     pix_fmt 'nv12' / 'p010' (with ``colour``, a ``Colour`` or a dict of its fields): feed takes and returns uint8 / uint16 surfaces
     [H*3/2,pitch] instead, converted by ``bsvd_yuv420_to_planar`` / ``bsvd_planar_to_yuv420``; everything else is the same.
 
+    pix_fmt 'yuv420p', 'yuv420p10le', 'uyvy422', 'yuyv422', 'nv16', 'p210le', 'yuv422p', 'yuv422p10le', 'yuv444p', 'yuv444p10le' (the
+    planar, 4:2:2 and 4:4:4 surfaces; ``frame_shape`` is required): feed takes and returns 1-D arrays of the tight frame's samples
+    (uint8, uint16 for 10 bit) -- the bytes ``ffmpeg -f rawvideo`` emits --, converted by ``bsvd_yuv_to_planar`` / ``bsvd_planar_to_yuv``.
+
     pad None | 'reflect': 'reflect' takes frames of any size (even H and W for YUV): reflect-padded to the next multiples of 4 and cropped
     again on the device, same latency, frames back in the fed shape."""
 
@@ -273,7 +325,7 @@ class LiveStream:
         ``latency``) is then final at construction instead of at the first feed."""
         if depth < 1:
             raise ValueError("depth must be >= 1")
-        self.fmt = _pixel_format(pix_fmt, colour, pad)
+        self.fmt = _pixel_format(pix_fmt, colour, pad, frame_shape)
         self.model, self.sigma, self.depth = model, sigma, depth
         self._overlap_wanted = (depth >= 2) if overlap_blocks is None else bool(overlap_blocks)
         self._overlap_explicit = overlap_blocks is not None

@@ -418,6 +418,71 @@ int bsvd_planar_to_yuv420_crop(const float *src, void *dst, int32_t frames, int3
                                const BsvdYuvDesc *desc, void *stream);
 
 /*
+ * YUV surfaces beyond NV12 / P010: the planar, 4:2:2 and 4:4:4 layouts software decoders, `ffmpeg -f rawvideo`, SDI capture cards, V4L2
+ * devices and mastering pipelines hand over.  The entry points above and BsvdYuvDesc are unchanged; these take a BsvdYuvSurface instead.
+ * Added without a new BSVD_ABI_VERSION: discover the five entry points by symbol (dlsym), like the YUV entry points above.
+ *
+ * A surface is described by its subsampling, its layout, its sample width and -- for 10 bit -- where the code sits in the 16-bit
+ * little-endian word: high_bits = 1 is the P010 rule (code = word >> 6 in, word = code << 6 out; the low 6 bits ignored in, zero out),
+ * high_bits = 0 the yuv4xxp10le rule (code = word & 1023 in; the high 6 bits ignored in, zero out).  Exactly ten combinations are served
+ * (ffmpeg's names):
+ *   yuv420p      4:2:0  PLANAR      8        |  yuv420p10le  4:2:0  PLANAR      10 low
+ *   uyvy422      4:2:2  UYVY        8        |  yuyv422      4:2:2  YUYV        8
+ *   nv16         4:2:2  SEMIPLANAR  8        |  p210le       4:2:2  SEMIPLANAR  10 high
+ *   yuv422p      4:2:2  PLANAR      8        |  yuv422p10le  4:2:2  PLANAR      10 low
+ *   yuv444p      4:4:4  PLANAR      8        |  yuv444p10le  4:4:4  PLANAR      10 low
+ * every other one returns -3 naming the field that rules it out (4:2:0 SEMIPLANAR is NV12 / P010: bsvd_yuv420_*).
+ * Layouts: PLANAR = three planes Y, Cb, Cr (chroma planes W/2 x H/2, W/2 x H, W x H samples for 4:2:0, 4:2:2, 4:4:4); SEMIPLANAR = a Y
+ * plane and one plane of interleaved Cb Cr pairs; UYVY = one plane of Cb Y0 Cr Y1 groups; YUYV = one plane of Y0 Cb Y1 Cr groups.
+ * Plane i has pitch[i] BYTES per row (0 = tight) and starts offset[i] bytes from the frame's first byte (offset[0] as given; 0 for planes 1
+ * and 2 = directly behind the last row of the plane before, pitch included); frames are frame_stride bytes apart (0 = tight: the end of the
+ * plane that ends last).  Planes must not share bytes.  pitch / offset of planes the layout does not have must be 0.
+ *
+ * Arithmetic: matrix, range, NOT-clamped decode, encode clamp, legal-code clamp and rounding (half to even) are word for word those of
+ * bsvd_yuv420_to_planar / bsvd_planar_to_yuv420 -- a yuv420p surface gives the bits an NV12 surface of the same samples gives.  Chroma:
+ *   4:2:0  as documented above.
+ *   4:2:2  the horizontal half of it, nothing vertical: sample i is co-sited with luma column 2i.  In, LINEAR: even columns c[i], odd columns
+ *          (c[i] + c[i+1]) / 2, clamped at the picture's right edge; NEAREST: both columns c[i].  Out, LINEAR: [1 2 1] / 4 over columns 2i-1,
+ *          2i, 2i+1, edge-clamped; NEAREST: the mean of the two columns.
+ *   4:4:4  no filter; `chroma` must still be a valid value and is ignored.
+ * bsvd_yuv_to_planar / bsvd_planar_to_yuv: H and W multiples of 4; tensors as for the yuv420 pair.  bsvd_yuv_to_planar_pad /
+ * bsvd_planar_to_yuv_crop: the rules of bsvd_yuv420_to_planar_pad / bsvd_planar_to_yuv420_crop (mirror after conversion, chroma filters
+ * clamp at the picture's own edge, Wp a multiple of 4, pad below the dimension, Hp even with 4:2:0), for pictures of even H and W (4:2:0),
+ * even W and any H >= 2 (4:2:2), any H, W >= 2 (4:4:4).  No byte outside a surface's samples is read or written -- pitch padding, the
+ * bytes between planes and frames, and on input the ignored bits of a 10-bit word are all outside --, and every sample and every element
+ * of the fp32 tensor is written exactly once.
+ * All return -3, naming the argument in bsvd_last_error(), for: a NULL pointer; frames <= 0; a size the entry point does not take; an
+ * unknown enum value; bits other than 8 / 10; a combination that is not served; a reserved field != 0; a pitch below the plane's row; a
+ * negative offset; pitch / offset set for a plane the layout lacks; with 16-bit samples an odd pitch, offset, frame_stride or surface
+ * pointer; frame_stride below one frame; a planar pointer that is not 16-byte aligned; const_channels < 0.  All of it without a device.
+ * bsvd_yuv_frame_bytes: the bytes of one frame -- the end of the plane that ends last, tight or pitched -- for any picture size the
+ * pad / crop pair takes; -1 on bad arguments.
+ */
+enum { BSVD_SUB_420 = 0, BSVD_SUB_422 = 1, BSVD_SUB_444 = 2 };
+enum { BSVD_LAYOUT_PLANAR = 0, BSVD_LAYOUT_SEMIPLANAR = 1, BSVD_LAYOUT_UYVY = 2, BSVD_LAYOUT_YUYV = 3 };
+typedef struct BsvdYuvSurface {
+    int32_t subsampling, layout;
+    int32_t bits;              /* 8 or 10 */
+    int32_t high_bits;         /* 10 bit: 1 = code in the high bits of the word, 0 = in the low bits; 0 with 8 bit */
+    int32_t matrix, full_range, chroma;   /* as in BsvdYuvDesc */
+    int32_t reserved0;         /* must be 0 */
+    int32_t pitch[3];          /* bytes per row of plane i; 0 = tight */
+    int32_t reserved1;         /* must be 0 */
+    int64_t offset[3];         /* bytes from the frame's first byte to plane i; 0 for planes 1, 2 = directly behind the plane before */
+    int64_t frame_stride;      /* bytes; 0 = tight */
+    int64_t reserved2;         /* must be 0 */
+} BsvdYuvSurface;              /* 88 bytes */
+int64_t bsvd_yuv_frame_bytes(int32_t H, int32_t W, const BsvdYuvSurface *surface);
+int bsvd_yuv_to_planar(const void *src, float *dst, int32_t frames, int32_t H, int32_t W, const BsvdYuvSurface *surface,
+                       int32_t const_channels, float const_value, void *stream);
+int bsvd_planar_to_yuv(const float *src, void *dst, int32_t frames, int32_t H, int32_t W, const BsvdYuvSurface *surface,
+                       void *stream);
+int bsvd_yuv_to_planar_pad(const void *src, float *dst, int32_t frames, int32_t H, int32_t W, int32_t Hp, int32_t Wp,
+                           const BsvdYuvSurface *surface, int32_t const_channels, float const_value, void *stream);
+int bsvd_planar_to_yuv_crop(const float *src, void *dst, int32_t frames, int32_t Hp, int32_t Wp, int32_t H, int32_t W,
+                            const BsvdYuvSurface *surface, void *stream);
+
+/*
  * Frame-window sharding: gathers the channel slice [c0, c0+n) of one NHWC frame into
  * a compact [H*W][n] buffer -- the message a rank sends to its temporal neighbour
  * (first frame, c0 = 0 -> the left neighbour's halo_next; last frame, c0 = fold -> the right

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Denoises a raw YUV 4:2:0 stream -- NV12 or P010 frames as any `-f rawvideo` producer pipes them -- through
+"""Denoises a raw YUV stream -- NV12 or P010 frames, or planar / 4:2:2 / 4:4:4 ones (yuv420p, yuv420p10le, uyvy422, yuyv422, nv16,
+p210le, yuv422p, yuv422p10le, yuv444p, yuv444p10le), as any `-f rawvideo` producer pipes them -- through
 bsvd_amd.pipeline.LiveStream(pix_fmt=...): surfaces over PCIe, colour conversion on the device, one graph-replayed pipeline step per
 frame.  Prints one JSON line: frames, frames_per_s (whole run, host to host, file I/O and pipeline fill included), ms_per_feed p50 / p99 and
 steady_frames_per_s (wall clock, reads and writes included) over the steady state, the second half of the feeds.
@@ -7,12 +8,16 @@ steady_frames_per_s (wall clock, reads and writes included) over the steady stat
     python tools/yuv_denoise.py IN OUT --size 1920x1080 --pix-fmt nv12 --sigma 30 [--matrix bt709] [--full-range] [--chroma linear]
                                 [--depth 2] [--ckpt model.pth]                IN / OUT: a file, or - for stdin / stdout
 
-The width and height must be even; a size that is no multiple of 4 (854x480) is reflect-padded to the next one and cropped again on the
+    ffmpeg -i in.mp4 -pix_fmt yuv420p -f rawvideo - | python tools/yuv_denoise.py - - --size 1920x1080 --sigma 30 | ffmpeg -f rawvideo ...
+                                                                                  (--pix-fmt defaults to yuv420p, ffmpeg's own default)
+
+The width and height must be even (4:2:2: the width; 4:4:4: neither); a size that is no multiple of 4 (854x480) is reflect-padded to the next one and cropped again on the
 device (LiveStream(pad='reflect')), the files hold pictures of the size given.  Without --ckpt the weights are seeded random ones (rates, not pictures), like
 tools/live_stream.py."""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
+from bsvd_amd import _lib, frame_io
 
 
 def read_frames(f, nbytes):
@@ -28,7 +33,7 @@ def main(argv=None):
     ap.add_argument("input")
     ap.add_argument("output")
     ap.add_argument("--size", required=True, help="WxH of the pictures, e.g. 1920x1080")
-    ap.add_argument("--pix-fmt", required=True, choices=["nv12", "p010"])
+    ap.add_argument("--pix-fmt", default="yuv420p", choices=["nv12", "p010"] + sorted(_lib.YUV_FORMATS))
     ap.add_argument("--sigma", type=float, required=True, help="noise std in 8-bit code units (e.g. 30)")
     ap.add_argument("--matrix", default="bt709", choices=["bt601", "bt709", "bt2020"])
     ap.add_argument("--full-range", action="store_true")
@@ -38,11 +43,13 @@ def main(argv=None):
     ap.add_argument("--precision", default="f16x3")
     a = ap.parse_args(argv)
     W, H = map(int, a.size.lower().split("x"))
-    if W <= 2 or H <= 2 or W % 2 or H % 2:
-        ap.error("--size %s: width and height must be even (4:2:0) and at least 4" % a.size)
+    surface = a.pix_fmt in _lib.YUV_FORMATS              # the 1-D frames of the planar / 4:2:2 / 4:4:4 formats
+    sub, bits = (_lib.YUV_FORMATS[a.pix_fmt][0], _lib.YUV_FORMATS[a.pix_fmt][2]) if surface else (_lib.SUB_420, 8 if a.pix_fmt == "nv12" else 10)
+    if W <= 2 or H <= 2 or (W % 2 and sub != _lib.SUB_444) or (H % 2 and sub == _lib.SUB_420):
+        ap.error("--size %s: at least 3x3; the width must be even for 4:2:0 and 4:2:2, the height for 4:2:0" % a.size)
     pad = "reflect" if W % 4 or H % 4 else None
-    dtype = np.dtype(np.uint8 if a.pix_fmt == "nv12" else "<u2")
-    nbytes = W * H * 3 // 2 * dtype.itemsize
+    dtype = np.dtype(np.uint8 if bits == 8 else "<u2")
+    nbytes = frame_io.yuv_frame_bytes(H, W, a.pix_fmt) if surface else W * H * 3 // 2 * dtype.itemsize
 
     import torch
     import bsvd_amd
@@ -58,7 +65,7 @@ def main(argv=None):
     ms, done = [], []                              # per feed: time inside feed(), clock when its iteration (read, feed, write) ended
     t0 = time.perf_counter()
     for raw in read_frames(fin, nbytes):
-        frame = np.frombuffer(raw, dtype).reshape(H * 3 // 2, W)
+        frame = np.frombuffer(raw, dtype) if surface else np.frombuffer(raw, dtype).reshape(H * 3 // 2, W)
         t1 = time.perf_counter()
         r = live.feed(frame)
         ms.append((time.perf_counter() - t1) * 1e3)

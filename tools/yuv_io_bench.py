@@ -11,7 +11,11 @@
   host    : tools/yuv_denoise.py (NV12 file in, file out) against tools/live_stream.py (RGB24) as child processes, alternating, twice.
   hostpad : the same two tools at 854x480 (pad='reflect') against 856x480, alternating, twice.
 
-    python tools/yuv_io_bench.py kernels|host|hostpad|all [--size 1080x1920] [--out profiles/yuv420_io.txt]"""
+  formats : bsvd_yuv_to_planar / bsvd_planar_to_yuv on each of the ten planar / 4:2:2 / 4:4:4 surface formats beside the NV12 kernels, one
+            frame per launch, same process, five rounds interleaved (the record behind profiles/yuv_formats.txt).
+  hostfmt : tools/yuv_denoise.py on nv12, yuv420p and uyvy422 files at 1080p and 540 x 960, alternating, twice (same record).
+
+    python tools/yuv_io_bench.py kernels|host|hostpad|all|formats|hostfmt [--size 1080x1920] [--out profiles/yuv420_io.txt]"""
 import argparse, json, os, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -146,9 +150,95 @@ def hostpad(say):
                     % (W, H, rep, j["host_to_host_fps_steady"], j["feed_call_ms"]["p50"], j["feed_call_ms"]["p99"]))
 
 
+def formats(say, H=1080, W=1920):
+    """the record behind profiles/yuv_formats.txt, kernels: bsvd_yuv_to_planar / bsvd_planar_to_yuv on each of the ten surface formats beside
+    bsvd_yuv420_to_planar / bsvd_planar_to_yuv420 on NV12, one frame per launch, same process, rounds interleaved"""
+    import ctypes
+    import torch
+    from bsvd_amd import _lib
+    from bsvd_amd.frame_io import yuv420_frame_bytes, yuv_frame_bytes
+    dev = torch.device("cuda", 0)
+    lib = _lib.load()
+    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    sigma = 30 / 255.0
+    say("formats: %d x %d frames, one per launch, chroma 'linear', BT.709 limited, on %s; device us per launch (= per frame), HIP events around 200 "
+        "launches after 20 warm-ups, 5 rounds interleaved over all rows" % (H, W, torch.cuda.get_device_name(0)))
+
+    def timed(fn):
+        for _ in range(20):
+            fn()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(200):
+            fn()
+        b.record()
+        b.synchronize()
+        return a.elapsed_time(b) * 1e3 / 200
+
+    rs = np.random.RandomState(0)
+    x4 = torch.rand((1, 4, H, W), device=dev)
+    y3 = torch.rand((1, 3, H, W), device=dev)
+    px = H * W
+    nb = yuv420_frame_bytes(H, W, "nv12")
+    s0 = torch.from_numpy(rs.randint(0, 256, (1, nb)).astype(np.uint8)).to(dev)
+    o0 = torch.empty_like(s0)
+    d0 = _lib.BsvdYuvDesc(pix_fmt=_lib.PIX_FMT["nv12"], matrix=_lib.MATRIX["bt709"], full_range=0, chroma=_lib.CHROMA["linear"])
+    keep = [s0, o0, d0]
+    cases = [("bsvd_yuv420_to_planar (nv12)", "dec", lambda: lib.bsvd_yuv420_to_planar(s0.data_ptr(), x4.data_ptr(), 1, H, W, ctypes.byref(d0), 1, sigma, st), nb + px * 16),
+             ("bsvd_planar_to_yuv420 (nv12)", "enc", lambda: lib.bsvd_planar_to_yuv420(y3.data_ptr(), o0.data_ptr(), 1, H, W, ctypes.byref(d0), st), nb + px * 12)]
+    for fmt in sorted(_lib.YUV_FORMATS):
+        sub, layout, bits, high = _lib.YUV_FORMATS[fmt]
+        nb = yuv_frame_bytes(H, W, fmt)
+        s = torch.from_numpy(rs.randint(0, 256, (1, nb)).astype(np.uint8)).to(dev)
+        o = torch.empty_like(s)
+        d = _lib.BsvdYuvSurface(subsampling=sub, layout=layout, bits=bits, high_bits=high, matrix=_lib.MATRIX["bt709"], full_range=0,
+                                chroma=_lib.CHROMA["linear"])
+        keep += [s, o, d]
+        cases.append(("bsvd_yuv_to_planar (%s)" % fmt, "dec",
+                      lambda s=s, d=d: lib.bsvd_yuv_to_planar(s.data_ptr(), x4.data_ptr(), 1, H, W, ctypes.byref(d), 1, sigma, st), nb + px * 16))
+        cases.append(("bsvd_planar_to_yuv (%s)" % fmt, "enc",
+                      lambda o=o, d=d: lib.bsvd_planar_to_yuv(y3.data_ptr(), o.data_ptr(), 1, H, W, ctypes.byref(d), st), nb + px * 12))
+    for name, _, fn, _ in cases:
+        assert fn() == 0, name
+    times = {name: [] for name, _, _, _ in cases}
+    for _ in range(5):
+        for name, _, fn, _ in cases:
+            times[name].append(timed(fn))
+    ref = {kind: sorted(times[name])[2] for name, kind, _, _ in cases[:2]}
+    say("%-38s %10s %10s %10s %9s %8s %9s" % ("launch", "us (min)", "us (med)", "us (max)", "MB moved", "TB/s", "/ nv12"))
+    for name, kind, _, nbytes in cases:
+        t = sorted(times[name])
+        say("%-38s %10.1f %10.1f %10.1f %9.1f %8.2f %9.2f" % (name, t[0], t[2], t[4], nbytes / 1e6, nbytes / t[2] / 1e6, t[2] / ref[kind]))
+    say("(MB moved = the bytes a launch must read + write, fp32 side + surface side; / nv12 = median over the NV12 kernel's of the same direction)")
+
+
+def hostfmt(say, frames=192):
+    """... and streams: tools/yuv_denoise.py host to host on nv12, yuv420p and uyvy422 files of the same size, alternating, twice"""
+    say("host to host: tools/yuv_denoise.py (%d frames from a file, depth 2) with nv12, yuv420p and uyvy422, alternating, twice; steady = wall-clock "
+        "rate over the second half of the feeds, file reads and writes included" % frames)
+    from bsvd_amd.frame_io import yuv420_frame_bytes, yuv_frame_bytes
+    with tempfile.TemporaryDirectory() as tmp:
+        for size in ("1080x1920", "540x960"):
+            H, W = map(int, size.split("x"))
+            for fmt in ("nv12", "yuv420p", "uyvy422"):
+                nb = yuv420_frame_bytes(H, W, fmt) if fmt == "nv12" else yuv_frame_bytes(H, W, fmt)
+                with open(os.path.join(tmp, "in_%s.%s" % (size, fmt)), "wb") as f:
+                    rs = np.random.RandomState(0)
+                    for _ in range(frames):
+                        f.write(rs.randint(0, 256, nb, dtype=np.uint8).tobytes())
+            for rep in range(2):
+                for fmt in ("nv12", "yuv420p", "uyvy422"):
+                    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "yuv_denoise.py"), os.path.join(tmp, "in_%s.%s" % (size, fmt)),
+                                        os.path.join(tmp, "out.yuv"), "--size", "%dx%d" % (W, H), "--pix-fmt", fmt, "--sigma", "30", "--depth", "2"],
+                                       stdout=subprocess.PIPE, text=True, timeout=600, check=True)
+                    j = json.loads(r.stdout.strip().splitlines()[-1])
+                    say("  %s #%d %-8s: steady %.1f frames/s, feed p50 %.2f ms, p99 %.2f ms (whole run with file I/O and pipeline fill: %.1f frames/s)"
+                        % (size, rep, fmt, j["steady_frames_per_s"], j["ms_per_feed"]["p50"], j["ms_per_feed"]["p99"], j["frames_per_s"]))
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=["kernels", "host", "hostpad", "all"])
+    ap.add_argument("what", choices=["kernels", "host", "hostpad", "all", "formats", "hostfmt"])
     ap.add_argument("--size", default="1080x1920", help="HxW of the pictures of the kernels section")
     ap.add_argument("--out", default=None)
     ap.add_argument("--append", action="store_true", help="keep what --out already holds")
@@ -167,3 +257,7 @@ if __name__ == "__main__":
         host(say)
     if a.what in ("hostpad", "all"):
         hostpad(say)
+    if a.what == "formats":                       # the record of the planar / 4:2:2 / 4:4:4 surfaces: profiles/yuv_formats.txt
+        formats(say, *map(int, a.size.lower().split("x")))
+    if a.what == "hostfmt":
+        hostfmt(say)
