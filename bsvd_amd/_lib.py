@@ -24,12 +24,17 @@ EXPORTS = ("bsvd_abi_version", "bsvd_conv_args_size", "bsvd_build_info", "bsvd_l
            "bsvd_yuv420_frame_bytes", "bsvd_yuv420_to_planar", "bsvd_planar_to_yuv420",
            "bsvd_u8_to_planar_pad", "bsvd_planar_to_u8_crop", "bsvd_yuv420_picture_bytes", "bsvd_yuv420_to_planar_pad",
            "bsvd_planar_to_yuv420_crop",
-           "bsvd_yuv_frame_bytes", "bsvd_yuv_to_planar", "bsvd_planar_to_yuv", "bsvd_yuv_to_planar_pad", "bsvd_planar_to_yuv_crop")
+           "bsvd_yuv_frame_bytes", "bsvd_yuv_to_planar", "bsvd_planar_to_yuv", "bsvd_yuv_to_planar_pad", "bsvd_planar_to_yuv_crop",
+           "bsvd_sigma_workspace_bytes", "bsvd_estimate_sigma", "bsvd_fill_sigma_plane")
 PIX_FMT = {"nv12": 0, "p010": 1}
 MATRIX = {"bt601": 0, "bt709": 1, "bt2020": 2}
 CHROMA = {"nearest": 0, "linear": 1}
 SUB_420, SUB_422, SUB_444 = 0, 1, 2
 LAYOUT_PLANAR, LAYOUT_SEMIPLANAR, LAYOUT_UYVY, LAYOUT_YUYV = 0, 1, 2, 3
+SIGMA_BINS = 4096             # bins of bsvd_estimate_sigma's histogram: 1 / 4096 of |r| each
+# the scale from the median bin to sigma, 1 / (4096 * 6 * 0.6744897501960817) (frame_sigma_items.h, SIGMA_K), and where the estimate saturates
+SIGMA_K = float.fromhex("0x1.fa0fc23747344p-15")
+SIGMA_MAX = SIGMA_BINS * SIGMA_K
 # the surfaces of bsvd_yuv_to_planar / bsvd_planar_to_yuv, by ffmpeg's names: (subsampling, layout, bits, high_bits).  PIX_FMT above stays
 # the table of the bsvd_yuv420_* entry points.
 YUV_FORMATS = {
@@ -193,6 +198,12 @@ def load():
     lib.bsvd_yuv_to_planar_pad.argtypes = [vp, vp, i32, i32, i32, i32, i32, surf, i32, f32, vp]
     lib.bsvd_planar_to_yuv_crop.restype = ctypes.c_int
     lib.bsvd_planar_to_yuv_crop.argtypes = [vp, vp, i32, i32, i32, i32, i32, surf, vp]
+    lib.bsvd_sigma_workspace_bytes.restype = i64
+    lib.bsvd_sigma_workspace_bytes.argtypes = [i32]
+    lib.bsvd_estimate_sigma.restype = ctypes.c_int
+    lib.bsvd_estimate_sigma.argtypes = [vp, i32, i32, i32, i32, i32, i32, i64, f32, f32, f32, vp, vp, vp]
+    lib.bsvd_fill_sigma_plane.restype = ctypes.c_int
+    lib.bsvd_fill_sigma_plane.argtypes = [vp, i32, i32, i32, i32, i64, vp, vp]
     lib.bsvd_workspace_bytes.restype = i64
     lib.bsvd_workspace_bytes.argtypes = [ctypes.POINTER(BsvdConvArgs)]
     if lib.bsvd_abi_version() != ABI_VERSION:

@@ -12,7 +12,11 @@ planar 4:2:0, 4:2:2 (packed, semi-planar, planar) and planar 4:4:4, 8 and 10 bit
 Any picture size: the network needs H and W to be multiples of 4, and the reference's callers reflect-pad the fp32 tensor on the right and
 bottom and crop the result (``denoise.pad_to_multiple_of_4`` / ``crop_padding`` here).  ``pad_to=(Hp, Wp)`` on the way in and
 ``crop_to=(H, W)`` on the way out do both inside the conversion kernels (bsvd_*_pad / bsvd_*_crop): the frames stay picture-sized uint8 /
-YUV on the host and over PCIe.  ``network_size(H, W)`` is the (Hp, Wp) the pipelines use.  Without them every function is what it was."""
+YUV on the host and over PCIe.  ``network_size(H, W)`` is the (Hp, Wp) the pipelines use.  Without them every function is what it was.
+
+The noise level: ``sigma`` is a float (the constant the caller knows, as before), ``'auto'`` (one estimate per frame, computed on the device
+from the converted frame and written into that frame's noise-map plane -- ``estimate_sigma``; nothing crosses to the host and nothing waits
+for it), a sequence of per-frame values, or a device tensor [T]."""
 import ctypes
 
 import torch
@@ -38,15 +42,138 @@ def _pair(v, what):
         raise ValueError("%s: expected a pair of ints, got %r" % (what, v)) from None
 
 
-def frames_to_input(frames_u8, sigma=None, hwc=True, pad_to=None):
+# ---------------------------------------------------------------------------------------------------
+# the noise level: estimated per frame on the device, or given per frame (include/bsvd_hip.h, bsvd_estimate_sigma / bsvd_fill_sigma_plane)
+
+SIGMA_BINS = _lib.SIGMA_BINS
+SIGMA_MAX = _lib.SIGMA_MAX          # where the estimate saturates: 1 / (6 * 0.6745) = 0.2471 (63 / 255)
+
+
+def _check_clamp(clamp):
+    """-> (lo, hi) floats with 0 <= lo <= hi, both finite; ValueError otherwise"""
+    try:
+        lo, hi = clamp
+        lo, hi = float(lo), float(hi)
+    except (TypeError, ValueError):
+        raise ValueError("clamp: expected a pair (lo, hi), got %r" % (clamp,)) from None
+    if not (0.0 <= lo <= hi < float("inf")):
+        raise ValueError("clamp %r: 0 <= lo <= hi, both finite" % (clamp,))
+    return lo, hi
+
+
+def _check_gain(gain):
+    try:
+        g = float(gain)
+    except (TypeError, ValueError):
+        raise ValueError("sigma_gain: expected a positive number, got %r" % (gain,)) from None
+    if not (0.0 < g < float("inf")):
+        raise ValueError("sigma_gain %r: must be positive and finite" % (gain,))
+    return g
+
+
+def _sigma_mode(sigma, T=None):
+    """what ``sigma=`` asks for -> ('const', None | float) -- today's path --, ('auto', None), ('host', [T floats]) or ('device', tensor [T]).
+    Needs no device; T (when known) is checked against the length of per-frame values."""
+    if sigma is None:
+        return "const", None
+    if isinstance(sigma, str):
+        if sigma != "auto":
+            raise ValueError("sigma %r: a number, 'auto', a sequence of per-frame values or a device tensor [T]" % (sigma,))
+        return "auto", None
+    if isinstance(sigma, torch.Tensor) and sigma.dim() >= 1:
+        if sigma.dim() != 1 or sigma.dtype != torch.float32:
+            raise ValueError("sigma: a per-frame tensor must be float32 [T], got %s %s" % (sigma.dtype, tuple(sigma.shape)))
+        if T is not None and sigma.shape[0] != T:
+            raise ValueError("sigma: %d per-frame values for %d frames" % (sigma.shape[0], T))
+        return ("device" if sigma.is_cuda else "host"), (sigma if sigma.is_cuda else [float(v) for v in sigma])
+    if isinstance(sigma, (list, tuple)) or (not isinstance(sigma, torch.Tensor) and hasattr(sigma, "__len__") and hasattr(sigma, "__iter__")):
+        try:
+            vals = [float(v) for v in sigma]
+        except (TypeError, ValueError):
+            raise ValueError("sigma: per-frame values must be numbers, got %r" % (sigma,)) from None
+        if T is not None and len(vals) != T:
+            raise ValueError("sigma: %d per-frame values for %d frames" % (len(vals), T))
+        return "host", vals
+    return "const", float(sigma)
+
+
+def _planes(x, what):
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or not x.is_cuda or x.dim() != 4 or not x.is_contiguous():
+        raise ValueError("%s: expected a contiguous float32 device tensor [T,C,H,W]" % what)
+    return x.shape
+
+
+def estimate_sigma(x, picture=None, gain=1.0, clamp=(0.0, SIGMA_MAX), return_hist=False):
+    """x: fp32 device tensor [T,C>=3,Hp,Wp], the tensor the ``*_to_input`` functions build -> fp32 device tensor [T]: one noise-level
+    estimate per frame in [0,1] units, computed on the device, not synchronised with the host.  ``picture=(H, W)``: the top-left part of
+    the planes that is the picture (``pad_to`` callers: the mirror images are not sampled); default: all of it.  The estimate: the
+    Laplacian-difference mask [1 -2 1; -2 4 -2; 1 -2 1] over the interior pixels of the three colour planes, the median of its |response|
+    from a 4096-bin histogram, / (6 * 0.6745); then ``* gain``, clamped to ``clamp``.  Bit-reproducible (integer counts; include/bsvd_hip.h
+    states it operation by operation).  It saturates at ``SIGMA_MAX`` (63 / 255).  ``return_hist=True``: also the uint32 [T,4096] histograms.
+
+    What is known: on synthetic frames with white Gaussian noise it is within 0.7 / 255 of the truth for sigma 2 .. 30 / 255 on
+    frames of 64 x 96 and larger (profiles/sigma_auto.txt).  Nothing has been measured on real footage.  A YUV source with subsampled chroma gives correlated,
+    chroma-smoothed RGB noise: the estimate reads LOW there, which is what ``gain`` is for."""
+    lo, hi = _check_clamp(clamp)
+    gain = _check_gain(gain)
+    T, C, Hp, Wp = _planes(x, "estimate_sigma")
+    if C < 3:
+        raise ValueError("estimate_sigma: the estimate pools the three colour planes, x has %d" % C)
+    H, W = (Hp, Wp) if picture is None else _pair(picture, "picture")
+    lib = require_hip()
+    hist = torch.empty((T, SIGMA_BINS), dtype=torch.int32, device=x.device)
+    out = torch.empty((T,), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(lib.bsvd_estimate_sigma(x.data_ptr(), T, 3, H, W, Hp, Wp, C * Hp * Wp, gain, lo, hi, hist.data_ptr(), out.data_ptr(),
+                                           _stream()), "bsvd_estimate_sigma")
+    return (out, hist.view(torch.uint32)) if return_hist else out
+
+
+def fill_sigma_plane(x, sigma_dev):
+    """x: fp32 device tensor [T,C,Hp,Wp]; its last plane of frame t becomes sigma_dev[t] (fp32 device tensor [T]), in place, on the device"""
+    T, C, Hp, Wp = _planes(x, "fill_sigma_plane")
+    if (not isinstance(sigma_dev, torch.Tensor) or sigma_dev.dtype != torch.float32 or sigma_dev.device != x.device
+            or tuple(sigma_dev.shape) != (T,) or not sigma_dev.is_contiguous()):
+        raise ValueError("fill_sigma_plane: expected a contiguous float32 tensor [%d] on %s" % (T, x.device))
+    if C < 2:
+        raise ValueError("fill_sigma_plane: x has no plane behind its picture planes")
+    lib = require_hip()
+    with torch.cuda.device(x.device):
+        _lib.check(lib.bsvd_fill_sigma_plane(x.data_ptr(), T, C - 1, Hp, Wp, C * Hp * Wp, sigma_dev.data_ptr(), _stream()),
+                   "bsvd_fill_sigma_plane")
+    return x
+
+
+def _with_sigma(y, mode, picture, gain):
+    """the shared second half of the three ``*_to_input`` functions for per-frame sigma: y was converted with its sigma plane at 0;
+    estimate (or upload) the T values, fill the plane"""
+    kind, val = mode
+    if kind == "auto":
+        s = estimate_sigma(y, picture=picture, gain=gain)
+    elif kind == "host":
+        s = torch.tensor(val, dtype=torch.float32).to(y.device)
+    else:
+        if val.device != y.device:
+            raise ValueError("sigma: the per-frame tensor is on %s, the frames on %s" % (val.device, y.device))
+        s = val.contiguous()
+    return fill_sigma_plane(y, s)
+
+
+def frames_to_input(frames_u8, sigma=None, hwc=True, pad_to=None, sigma_gain=1.0):
     """frames_u8: uint8 device tensor [T,H,W,3] (hwc) or [T,3,H,W] -> fp32 [T,3(+1),H,W] in [0,1]; with ``sigma`` (noise
     std in [0,1] units, e.g. 30/255) a constant noise-map channel is appended.  ``pad_to=(Hp, Wp)``: the result is [T,3(+1),Hp,Wp],
-    reflect-padded on the right and bottom (F.pad(..., mode='reflect') of the unpadded result, bit for bit)."""
+    reflect-padded on the right and bottom (F.pad(..., mode='reflect') of the unpadded result, bit for bit).  ``sigma='auto'``: the
+    noise-map plane of frame t holds that frame's own estimate (``estimate_sigma`` of the picture, times ``sigma_gain``); a sequence or a
+    device tensor [T]: the caller's per-frame values."""
     lib = require_hip()
     if frames_u8.dtype != torch.uint8 or not frames_u8.is_cuda or frames_u8.dim() != 4:
         raise ValueError("expected a uint8 device tensor [T,H,W,C] or [T,C,H,W]")
     x = frames_u8.contiguous()
     T, H, W, C = x.shape if hwc else (x.shape[0], x.shape[2], x.shape[3], x.shape[1])
+    mode = _sigma_mode(sigma, T)
+    if mode[0] != "const":
+        gain = _check_gain(sigma_gain)
+        return _with_sigma(frames_to_input(x, 0.0, hwc, pad_to), mode, (H, W), gain)
     extra = 0 if sigma is None else 1
     if pad_to is not None:
         Hp, Wp = _pair(pad_to, "pad_to")
@@ -123,14 +250,20 @@ def _yuv_buffer(buf, T, nbytes, pix_fmt, what):
     return buf.shape[1]
 
 
-def yuv420_to_input(buf, H, W, pix_fmt="nv12", matrix="bt709", full_range=False, chroma="linear", sigma=None, row_pitch=None, pad_to=None):
+def yuv420_to_input(buf, H, W, pix_fmt="nv12", matrix="bt709", full_range=False, chroma="linear", sigma=None, row_pitch=None, pad_to=None,
+                    sigma_gain=1.0):
     """buf: uint8 device tensor [T, frame_bytes] of NV12 / P010 frames (``yuv420_frame_bytes``; rows longer than one frame are
     frames that far apart) -> fp32 [T,3(+1),H,W] RGB, the tensor ``frames_to_input`` builds; with ``sigma`` the constant noise-map
     channel is appended.  matrix 'bt601' | 'bt709' | 'bt2020', limited or full range, chroma upsampling 'nearest' | 'linear'
     (MPEG-2 / H.264 / HEVC default siting).  The result is NOT clamped to [0,1]: the out-of-gamut values of a noisy source are
     information for a denoiser.  ``pad_to=(Hp, Wp)`` (Hp even, Wp a multiple of 4): H and W only need to be even (``yuv420_picture_bytes``)
     and the result is [T,3(+1),Hp,Wp]: the picture converted with its chroma clamped at the picture's own edges, then reflect-padded on
-    the right and bottom."""
+    the right and bottom.  ``sigma='auto'`` / a sequence / a device tensor [T] and ``sigma_gain``: as for ``frames_to_input``; the
+    estimate is taken on the converted RGB, where 4:2:0 chroma has smoothed the noise of two planes: expect it to read low (``sigma_gain``)."""
+    mode = _sigma_mode(sigma, buf.shape[0] if isinstance(buf, torch.Tensor) and buf.dim() == 2 else None)
+    if mode[0] != "const":
+        gain = _check_gain(sigma_gain)
+        return _with_sigma(yuv420_to_input(buf, H, W, pix_fmt, matrix, full_range, chroma, 0.0, row_pitch, pad_to), mode, (int(H), int(W)), gain)
     desc, nbytes = _yuv_desc(H, W, pix_fmt, matrix, full_range, chroma, row_pitch, picture=pad_to is not None)
     lib = require_hip()
     desc.frame_stride = _yuv_buffer(buf, None, nbytes, pix_fmt, "yuv420_to_input")
@@ -246,12 +379,18 @@ def _surface_buffer(buf, T, nbytes, sixteen, what):
 
 
 def yuv_to_input(buf, H, W, pix_fmt="yuv420p", matrix="bt709", full_range=False, chroma="linear", sigma=None, pitches=None, pad_to=None,
-                 offsets=None):
+                 offsets=None, sigma_gain=1.0):
     """``yuv420_to_input`` for the planar, 4:2:2 and 4:4:4 surfaces (pix_fmt: one of ``_lib.YUV_FORMATS``): buf uint8 device tensor
     [T, frame_bytes] (``yuv_frame_bytes``) -> fp32 [T,3(+1),H,W] RGB, not clamped.  4:2:2 chroma is upsampled along the row only
     ('linear': co-sited with the even columns), 4:4:4 not at all.  ``pitches`` / ``offsets``: see ``yuv_frame_bytes``.  ``pad_to=(Hp, Wp)``
     (Wp a multiple of 4; Hp even for 4:2:0): any picture size the format can carry, reflect-padded on the right and bottom after
-    conversion."""
+    conversion.  ``sigma='auto'`` / a sequence / a device tensor [T] and ``sigma_gain``: as for ``yuv420_to_input`` (with subsampled
+    chroma the estimate reads low)."""
+    mode = _sigma_mode(sigma, buf.shape[0] if isinstance(buf, torch.Tensor) and buf.dim() == 2 else None)
+    if mode[0] != "const":
+        gain = _check_gain(sigma_gain)
+        return _with_sigma(yuv_to_input(buf, H, W, pix_fmt, matrix, full_range, chroma, 0.0, pitches, pad_to, offsets), mode,
+                           (int(H), int(W)), gain)
     surf, nbytes = _yuv_surface(H, W, pix_fmt, matrix, full_range, chroma, pitches, offsets, picture=pad_to is not None)
     lib = require_hip()
     surf.frame_stride = _surface_buffer(buf, None, nbytes, surf.bits > 8, "yuv_to_input")

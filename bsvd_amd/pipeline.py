@@ -25,6 +25,10 @@ it; 'reflect' takes any size -- even H and W for the 4:2:0 surfaces -- and does 
 (denoising_model.py, padding_input / crop_output): reflect-pad on the right and bottom up to the next multiples of 4, run the network at that
 size, crop the result.  Pad and crop happen inside the conversion kernels (``frame_io``'s ``pad_to`` / ``crop_to``), so the staging buffers
 and the PCIe transfers stay picture-sized and the results have the shape and dtype of what was fed.
+
+``sigma`` is the noise level of the non-blind models' noise map: a float the caller knows, or 'auto' -- every frame's own estimate, computed
+on the compute stream from the converted frame and written into its noise-map plane (``frame_io.estimate_sigma``; ``sigma_gain`` scales
+it).  The host sees it only afterwards, as ``LiveStream.last_sigma``: 4 bytes that come down with the frame.
 """
 import collections
 
@@ -32,7 +36,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .frame_io import (_yuv_desc, _yuv_surface, frames_to_input, network_size, output_to_frames, output_to_yuv, output_to_yuv420,
+from .frame_io import (_check_gain, _sigma_mode, _yuv_desc, _yuv_surface, frames_to_input, network_size, output_to_frames, output_to_yuv, output_to_yuv420,
                        yuv420_frame_bytes, yuv420_picture_bytes, yuv420_to_input, yuv_to_input)
 
 Colour = collections.namedtuple("Colour", "matrix full_range chroma row_pitch width", defaults=("bt709", False, "linear", None, None))
@@ -81,8 +85,8 @@ class _Rgb24:
             raise ValueError("H and W must be multiples of 4 (pad first: denoise.pad_to_multiple_of_4; or pad='reflect')")
         return _Geometry(h, w, tuple(a.shape), None, h, w)
 
-    def to_input(self, dev_in, geom, sigma):
-        return frames_to_input(dev_in, sigma, pad_to=(geom.net_h, geom.net_w) if self.pad else None)
+    def to_input(self, dev_in, geom, sigma, sigma_gain=1.0):
+        return frames_to_input(dev_in, sigma, pad_to=(geom.net_h, geom.net_w) if self.pad else None, sigma_gain=sigma_gain)
 
     def to_output(self, y, geom):
         return output_to_frames(y, crop_to=(geom.h, geom.w) if self.pad else None)
@@ -132,9 +136,9 @@ class _Yuv420:
         nbytes = (yuv420_picture_bytes if self.pad else yuv420_frame_bytes)(h, w, self.pix_fmt, row_bytes)
         return _Geometry(h, w, (a.shape[0], nbytes) if clip else (nbytes,), None if w == pitch else row_bytes, *net)
 
-    def to_input(self, dev_in, geom, sigma):
+    def to_input(self, dev_in, geom, sigma, sigma_gain=1.0):
         return yuv420_to_input(dev_in, geom.h, geom.w, sigma=sigma, row_pitch=geom.row_pitch,
-                               pad_to=(geom.net_h, geom.net_w) if self.pad else None, **self.kw)
+                               pad_to=(geom.net_h, geom.net_w) if self.pad else None, sigma_gain=sigma_gain, **self.kw)
 
     def to_output(self, y, geom):
         return output_to_yuv420(y, row_pitch=geom.row_pitch, crop_to=(geom.h, geom.w) if self.pad else None, **self.kw)
@@ -170,8 +174,9 @@ class _YuvSurface:
                              % (self.pix_fmt, self.dtype.name, "T," if clip else "", self.samples, self.h, self.w, a.dtype, a.shape))
         return _Geometry(self.h, self.w, (a.shape[0], self.nbytes) if clip else (self.nbytes,), None, *self.net)
 
-    def to_input(self, dev_in, geom, sigma):
-        return yuv_to_input(dev_in, geom.h, geom.w, sigma=sigma, pad_to=(geom.net_h, geom.net_w) if self.pad else None, **self.kw)
+    def to_input(self, dev_in, geom, sigma, sigma_gain=1.0):
+        return yuv_to_input(dev_in, geom.h, geom.w, sigma=sigma, pad_to=(geom.net_h, geom.net_w) if self.pad else None,
+                            sigma_gain=sigma_gain, **self.kw)
 
     def to_output(self, y, geom):
         return output_to_yuv(y, crop_to=(geom.h, geom.w) if self.pad else None, **self.kw)
@@ -190,6 +195,17 @@ def _pixel_format(pix_fmt, colour, pad=None, frame_shape=None):
     raise ValueError("pix_fmt %r: one of 'rgb24', 'nv12', 'p010', %s" % (pix_fmt, ", ".join(repr(n) for n in sorted(_lib.YUV_FORMATS))))
 
 
+def _check_sigma(model, sigma, sigma_gain, what):
+    """the pipelines' ``sigma``: None, a float or 'auto' -- which needs a noise-map channel to write into.  Before anything touches a device."""
+    if isinstance(sigma, str) or sigma is None or not hasattr(sigma, "__len__"):
+        mode = _sigma_mode(sigma)[0]
+    else:
+        raise ValueError("%s: sigma must be None, a number or 'auto' (per-frame values: frame_io.frames_to_input(sigma=[...]))" % what)
+    if mode == "auto" and model.net.net_in_ch == 3:
+        raise ValueError("%s(sigma='auto'): the model is blind (3 input channels): it has no noise map to estimate" % what)
+    return _check_gain(sigma_gain)
+
+
 class _Slot:
     def __init__(self):
         self.pin_in = self.pin_out = None
@@ -199,6 +215,7 @@ class _Slot:
         self.computed = torch.cuda.Event()
         self.downloaded = torch.cuda.Event()
         self.ticket = None          # the in-flight clip occupying this slot
+        self.dev_sigma = self.pin_sigma = None      # LiveStream(sigma='auto'): the step's estimate, 4 bytes beside the frame
 
 
 class _Ticket:
@@ -222,11 +239,14 @@ class ClipPipeline:
     colour (a ``Colour`` or a dict of its fields; YUV only): what ``submit`` takes and the results are, see the module docstring.
     pad None | 'reflect': 'reflect' takes pictures of any size (even H and W for YUV), padded and cropped on the device.
     pix_fmt 'yuv420p' | 'yuv420p10le' | 'uyvy422' | 'yuyv422' | 'nv16' | 'p210le' | 'yuv422p' | 'yuv422p10le' | 'yuv444p' | 'yuv444p10le'
-    with frame_shape=(H, W): clips are [T, n] arrays of the tight frames' samples (uint8, uint16 for 10 bit), as ffmpeg's rawvideo."""
+    with frame_shape=(H, W): clips are [T, n] arrays of the tight frames' samples (uint8, uint16 for 10 bit), as ffmpeg's rawvideo.
+    sigma='auto' (non-blind models): every frame's noise-map plane holds that frame's own estimate, times sigma_gain, computed on the
+    device (``frame_io.estimate_sigma``: what is known about it, and that YUV sources with subsampled chroma read low)."""
 
-    def __init__(self, model, sigma=None, depth=2, pix_fmt="rgb24", colour=None, pad=None, frame_shape=None):
+    def __init__(self, model, sigma=None, depth=2, pix_fmt="rgb24", colour=None, pad=None, frame_shape=None, sigma_gain=1.0):
         if depth < 1:
             raise ValueError("depth must be >= 1")
+        self.sigma_gain = _check_sigma(model, sigma, sigma_gain, "ClipPipeline")
         self.fmt = _pixel_format(pix_fmt, colour, pad, frame_shape)
         self.model, self.sigma = model, sigma
         self.device = model._device()
@@ -260,7 +280,7 @@ class ClipPipeline:
                 slot.uploaded.record()
             with torch.cuda.stream(self.comp):
                 self.comp.wait_event(slot.uploaded)
-                x = self.fmt.to_input(slot.dev_in, geom, self.sigma)
+                x = self.fmt.to_input(slot.dev_in, geom, self.sigma, self.sigma_gain)
                 T, _, H, W = x.shape
                 if self.model._pick_mode(T, H, W) == "clip":
                     y = self.model.clip_forward(x)
@@ -318,13 +338,24 @@ class LiveStream:
     (uint8, uint16 for 10 bit) -- the bytes ``ffmpeg -f rawvideo`` emits --, converted by ``bsvd_yuv_to_planar`` / ``bsvd_planar_to_yuv``.
 
     pad None | 'reflect': 'reflect' takes frames of any size (even H and W for YUV): reflect-padded to the next multiples of 4 and cropped
-    again on the device, same latency, frames back in the fed shape."""
+    again on the device, same latency, frames back in the fed shape.
 
-    def __init__(self, model, sigma=None, depth=2, overlap_blocks=None, frame_shape=None, pix_fmt="rgb24", colour=None, pad=None):
+    sigma='auto' (non-blind models): the noise-map plane of every frame holds that frame's own estimate, times ``sigma_gain``, computed on
+    the compute stream between the conversion and the pipeline step (``frame_io.estimate_sigma``); latency, slot ring and stream order are
+    what they are with a float.  ``last_sigma``: the estimate (a float, [0,1] units) of the most recent input step ``feed`` has already
+    waited for -- i.e. of the frame fed ``depth - 1`` calls ago --, None before that; it comes down on the download stream into the slot's
+    pinned memory beside the frame and is never read earlier.  Nothing is known about the estimate on real footage, and YUV sources with
+    subsampled chroma read low (``sigma_gain``)."""
+
+    def __init__(self, model, sigma=None, depth=2, overlap_blocks=None, frame_shape=None, pix_fmt="rgb24", colour=None, pad=None,
+                 sigma_gain=1.0):
         """frame_shape: optional (H, W) of the frames to come (the picture, also with ``pad``) -- the overlap decision (and with it
         ``latency``) is then final at construction instead of at the first feed."""
         if depth < 1:
             raise ValueError("depth must be >= 1")
+        self.sigma_gain = _check_sigma(model, sigma, sigma_gain, "LiveStream")
+        self.auto_sigma = isinstance(sigma, str)
+        self.last_sigma = None
         self.fmt = _pixel_format(pix_fmt, colour, pad, frame_shape)
         self.model, self.sigma, self.depth = model, sigma, depth
         self._overlap_wanted = (depth >= 2) if overlap_blocks is None else bool(overlap_blocks)
@@ -337,7 +368,7 @@ class LiveStream:
         with torch.cuda.device(self.device):
             self.up, self.comp, self.down = (torch.cuda.Stream(), torch.cuda.Stream(), torch.cuda.Stream())
         self.slots, self.shape, self.geom = None, None, None
-        self.inflight = collections.deque()          # (slot, has_output) in submission order
+        self.inflight = collections.deque()          # (slot, has_output, has_sigma) in submission order
         self.count = 0
         model.reset()
         if frame_shape is not None:
@@ -382,12 +413,17 @@ class LiveStream:
             s.pin_in = torch.empty(geom.staging, dtype=torch.uint8).pin_memory()
             s.pin_out = torch.empty(geom.staging, dtype=torch.uint8).pin_memory()
             s.dev_in = torch.empty((1,) + geom.staging, dtype=torch.uint8, device=self.device)
+            if self.auto_sigma:
+                s.pin_sigma = torch.zeros(1, dtype=torch.float32).pin_memory()
+                s.dev_sigma = torch.empty(1, dtype=torch.float32, device=self.device)
             self.slots.append(s)
 
     def _pop(self):
         """oldest in-flight step -> its uint8 frame, or None if that step emitted nothing (pipeline fill)"""
-        slot, has_out = self.inflight.popleft()
+        slot, has_out, has_sigma = self.inflight.popleft()
         slot.downloaded.synchronize()
+        if has_sigma:
+            self.last_sigma = float(slot.pin_sigma[0])
         return slot.pin_out.numpy().copy().view(self.fmt.dtype).reshape(self.shape) if has_out else None
 
     def _step(self, frame_u8, last=False):
@@ -405,7 +441,9 @@ class LiveStream:
                 x = None
                 if frame_u8 is not None:
                     self.comp.wait_event(slot.uploaded)
-                    x = self.fmt.to_input(slot.dev_in, self.geom, self.sigma)
+                    x = self.fmt.to_input(slot.dev_in, self.geom, self.sigma, self.sigma_gain)
+                    if self.auto_sigma:
+                        slot.dev_sigma.copy_(x[0, -1, 0, :1])          # the plane holds the estimate: one element of it, device to device
                 y = self.model.feed_overlapped(x, last=last) if self.overlap else self.model.feedin_one_element(x)
                 if y is not None:
                     slot.dev_out = self.fmt.to_output(y.float(), self.geom)   # held by the slot until its download completed
@@ -414,8 +452,10 @@ class LiveStream:
                 self.down.wait_event(slot.computed)
                 if y is not None:
                     slot.pin_out.copy_(slot.dev_out[0], non_blocking=True)
+                if self.auto_sigma and frame_u8 is not None:
+                    slot.pin_sigma.copy_(slot.dev_sigma, non_blocking=True)
                 slot.downloaded.record()
-        self.inflight.append((slot, y is not None))
+        self.inflight.append((slot, y is not None, self.auto_sigma and frame_u8 is not None))
 
     def _drain(self, keep, outs):
         while len(self.inflight) > keep:

@@ -483,6 +483,46 @@ int bsvd_planar_to_yuv_crop(const float *src, void *dst, int32_t frames, int32_t
                             const BsvdYuvSurface *surface, void *stream);
 
 /*
+ * The noise level of a frame, estimated on the device.  bsvd_c64 is non-blind: its fourth input channel is the noise map, which the
+ * reference fills with a constant the caller knows (temp_denoise's sigma map, validation_seq_infer.py:19-21).  A camera, SDI or ffmpeg
+ * feed comes without one.  These entry points stand in for that constant: bsvd_estimate_sigma computes one sigma per frame from the planar
+ * fp32 tensor the *_to_planar entry points build, bsvd_fill_sigma_plane writes per-frame values from DEVICE memory into the noise-map
+ * plane -- nothing crosses to the host and nothing on the stream waits for it.  Added without a new BSVD_ABI_VERSION: discover the three
+ * entry points by symbol (dlsym), like the YUV entry points above.
+ *
+ * The estimate, exactly (tests/sigma_model.py reproduces histogram and sigma bit for bit):
+ *   input     x [frames][.][Hp][Wp] fp32, frames `frame_stride` FLOATS apart (>= channels * Hp * Wp), rows Wp apart.  The picture is the
+ *             top-left H x W of each plane (3 <= H <= Hp, 3 <= W <= Wp): the mirror images of a padded tensor are not sampled.
+ *   samples   the interior pixels 1 <= r <= H - 2, 1 <= c <= W - 2 of the first `channels` planes, pooled per frame.
+ *   response  the Laplacian-difference mask [1 -2 1; -2 4 -2; 1 -2 1] in fp32, in this order:
+ *             r = (4 x_c - 2 ((x_n + x_s) + (x_w + x_e))) + ((x_nw + x_ne) + (x_sw + x_se)).  Every coefficient is a power of two.
+ *   bin       q = min(floor(|r| * 4096), 4095) into one histogram of 4096 uint32 counts per frame; a sample whose r is not finite is
+ *             not counted.  Integer adds only: the histogram does not depend on the launch shape.
+ *   finish    N = sum of the counts, k = the first bin with 2 cum[k] >= N, before = cum[k] - h[k]; in double,
+ *             med = k + (N - 2 before) / (2 h[k]); sigma = med * K with K = 1 / (4096 * 6 * 0.6744897501960817) (6: the mask's L2 norm;
+ *             0.6745: the median of |N(0,1)|), then * gain, clamped to [lo, hi], converted to fp32.  N == 0 gives lo.
+ * The median of |r| saturates where half the samples reach the last bin: estimates stop at 1 / (6 * 0.6745) = 0.2471 (63 / 255).
+ * What is known about it: on synthetic frames with white Gaussian noise it is within 0.7 / 255 of the truth for sigma 2 .. 30 / 255 on
+ * frames of 64 x 96 and larger (profiles/sigma_auto.txt).  Nothing has been measured on real footage.  A source with subsampled chroma gives correlated,
+ * chroma-smoothed RGB noise and the estimate reads LOW there: that is what `gain` is for.
+ *
+ * bsvd_sigma_workspace_bytes(frames): the bytes of `workspace`, frames * 4096 * 4; -1 for frames <= 0.
+ * bsvd_estimate_sigma: zeroes the workspace itself, on the stream; afterwards the workspace holds the [frames][4096] uint32 histograms and
+ *   sigma_out[frames] the estimates (fp32, device memory).  Rows move as float4 when x is 16-byte aligned and Wp and frame_stride are
+ *   multiples of 4, as scalars otherwise.  Returns -3, naming the argument in bsvd_last_error(), for: a NULL pointer; a pointer that is not
+ *   4-byte aligned; frames outside 1 .. 65535; channels <= 0; H or W below 3; Hp < H or Wp < W; frame_stride below channels * Hp * Wp;
+ *   channels * (H - 2) * (W - 2) >= 2^32; gain not positive and finite; lo or hi not finite, lo < 0 or lo > hi.  All of it without a device.
+ * bsvd_fill_sigma_plane: x [frames][>= channels + 1][Hp][Wp]; every element of plane `channels` of frame t becomes sigma_dev[t].  float4
+ *   stores when x is 16-byte aligned and Hp * Wp and frame_stride are multiples of 4.  -3 for: a NULL or misaligned pointer; frames outside
+ *   1 .. 65535; channels, Hp or Wp <= 0; frame_stride below (channels + 1) * Hp * Wp.
+ */
+int64_t bsvd_sigma_workspace_bytes(int32_t frames);
+int bsvd_estimate_sigma(const float *x, int32_t frames, int32_t channels, int32_t H, int32_t W, int32_t Hp, int32_t Wp, int64_t frame_stride,
+                        float gain, float lo, float hi, void *workspace, float *sigma_out, void *stream);
+int bsvd_fill_sigma_plane(float *x, int32_t frames, int32_t channels, int32_t Hp, int32_t Wp, int64_t frame_stride, const float *sigma_dev,
+                          void *stream);
+
+/*
  * Frame-window sharding: gathers the channel slice [c0, c0+n) of one NHWC frame into
  * a compact [H*W][n] buffer -- the message a rank sends to its temporal neighbour
  * (first frame, c0 = 0 -> the left neighbour's halo_next; last frame, c0 = fold -> the right

@@ -7,6 +7,9 @@ steady_frames_per_s (wall clock, reads and writes included) over the steady stat
 
     python tools/yuv_denoise.py IN OUT --size 1920x1080 --pix-fmt nv12 --sigma 30 [--matrix bt709] [--full-range] [--chroma linear]
                                 [--depth 2] [--ckpt model.pth]                IN / OUT: a file, or - for stdin / stdout
+    python tools/yuv_denoise.py IN OUT --size 1920x1080 --sigma auto [--sigma-gain 1.0]      the noise level of every frame estimated on the
+                                device (LiveStream(sigma='auto')); the JSON line then carries last_sigma, in 8-bit code units.  Untested on
+                                real footage; with subsampled chroma the estimate reads low, which --sigma-gain corrects
 
     ffmpeg -i in.mp4 -pix_fmt yuv420p -f rawvideo - | python tools/yuv_denoise.py - - --size 1920x1080 --sigma 30 | ffmpeg -f rawvideo ...
                                                                                   (--pix-fmt defaults to yuv420p, ffmpeg's own default)
@@ -28,13 +31,24 @@ def read_frames(f, nbytes):
         yield raw
 
 
+def parse_sigma(text):
+    """--sigma: 'auto', or the noise std in 8-bit code units -> what LiveStream(sigma=) takes"""
+    if text == "auto":
+        return "auto"
+    try:
+        return float(text) / 255.0
+    except ValueError:
+        raise argparse.ArgumentTypeError("--sigma %r: a number (8-bit code units, e.g. 30) or auto" % text) from None
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("input")
     ap.add_argument("output")
     ap.add_argument("--size", required=True, help="WxH of the pictures, e.g. 1920x1080")
     ap.add_argument("--pix-fmt", default="yuv420p", choices=["nv12", "p010"] + sorted(_lib.YUV_FORMATS))
-    ap.add_argument("--sigma", type=float, required=True, help="noise std in 8-bit code units (e.g. 30)")
+    ap.add_argument("--sigma", type=parse_sigma, required=True, help="noise std in 8-bit code units (e.g. 30), or auto: estimated per frame on the device")
+    ap.add_argument("--sigma-gain", type=float, default=1.0, help="factor on the estimate of --sigma auto")
     ap.add_argument("--matrix", default="bt709", choices=["bt601", "bt709", "bt2020"])
     ap.add_argument("--full-range", action="store_true")
     ap.add_argument("--chroma", default="linear", choices=["nearest", "linear"])
@@ -57,7 +71,7 @@ def main(argv=None):
     torch.manual_seed(1234)
     m = bsvd_amd.BSVD(chns=[64, 128, 256], mid_ch=64, norm="none", act="relu6", interm_ch=64, pretrain_ckpt=a.ckpt,
                       precision=a.precision).to(torch.device("cuda", 0)).eval()
-    live = LiveStream(m, sigma=a.sigma / 255.0, depth=a.depth, frame_shape=(H, W), pix_fmt=a.pix_fmt,
+    live = LiveStream(m, sigma=a.sigma, sigma_gain=a.sigma_gain, depth=a.depth, frame_shape=(H, W), pix_fmt=a.pix_fmt,
                       colour={"matrix": a.matrix, "full_range": a.full_range, "chroma": a.chroma}, pad=pad)
     fin = sys.stdin.buffer if a.input == "-" else open(a.input, "rb")
     fout = sys.stdout.buffer if a.output == "-" else open(a.output, "wb")
@@ -86,7 +100,11 @@ def main(argv=None):
     res = {"frames": n_out, "frames_per_s": n_out / total if total > 0 else 0.0,
            "ms_per_feed": {"p50": float(np.percentile(steady, 50)), "p99": float(np.percentile(steady, 99))},
            "steady_frames_per_s": (n_in - k) / (done[-1] - done[k - 1]) if n_in > k >= 1 else 0.0,       # wall clock, reads and writes included
-           "size": "%dx%d" % (W, H), "pix_fmt": a.pix_fmt, "depth": a.depth, "frame_latency_feeds": live.latency, "pad": pad}
+           "size": "%dx%d" % (W, H), "pix_fmt": a.pix_fmt, "depth": a.depth, "frame_latency_feeds": live.latency, "pad": pad,
+           "sigma": "auto" if a.sigma == "auto" else a.sigma * 255.0}
+    if a.sigma == "auto":
+        res["sigma_gain"] = a.sigma_gain
+        res["last_sigma"] = None if live.last_sigma is None else live.last_sigma * 255.0
     print(json.dumps(res), file=sys.stderr if a.output == "-" else sys.stdout, flush=True)
     return res
 
