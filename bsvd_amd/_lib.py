@@ -25,7 +25,8 @@ EXPORTS = ("bsvd_abi_version", "bsvd_conv_args_size", "bsvd_build_info", "bsvd_l
            "bsvd_u8_to_planar_pad", "bsvd_planar_to_u8_crop", "bsvd_yuv420_picture_bytes", "bsvd_yuv420_to_planar_pad",
            "bsvd_planar_to_yuv420_crop",
            "bsvd_yuv_frame_bytes", "bsvd_yuv_to_planar", "bsvd_planar_to_yuv", "bsvd_yuv_to_planar_pad", "bsvd_planar_to_yuv_crop",
-           "bsvd_sigma_workspace_bytes", "bsvd_estimate_sigma", "bsvd_fill_sigma_plane")
+           "bsvd_sigma_workspace_bytes", "bsvd_estimate_sigma", "bsvd_fill_sigma_plane",
+           "bsvd_scene_grid", "bsvd_scene_diff")
 PIX_FMT = {"nv12": 0, "p010": 1}
 MATRIX = {"bt601": 0, "bt709": 1, "bt2020": 2}
 CHROMA = {"nearest": 0, "linear": 1}
@@ -204,6 +205,10 @@ def load():
     lib.bsvd_estimate_sigma.argtypes = [vp, i32, i32, i32, i32, i32, i32, i64, f32, f32, f32, vp, vp, vp]
     lib.bsvd_fill_sigma_plane.restype = ctypes.c_int
     lib.bsvd_fill_sigma_plane.argtypes = [vp, i32, i32, i32, i32, i64, vp, vp]
+    lib.bsvd_scene_grid.restype = ctypes.c_int
+    lib.bsvd_scene_grid.argtypes = [vp, i32, i32, i32, i32, i32, i64, vp, vp]
+    lib.bsvd_scene_diff.restype = ctypes.c_int
+    lib.bsvd_scene_diff.argtypes = [vp, vp, i32, i32, vp, vp]
     lib.bsvd_workspace_bytes.restype = i64
     lib.bsvd_workspace_bytes.argtypes = [ctypes.POINTER(BsvdConvArgs)]
     if lib.bsvd_abi_version() != ABI_VERSION:

@@ -28,6 +28,30 @@ from .schedule import StreamPipeline, bsvd_clip, planar_ok
 _REGISTRATION_EPOCH = [0]
 
 
+def check_cuts(cuts, F):
+    """``cuts``: the frame indices in [0, F) that start a new scene (any iterable of ints, taken as a set; None = none; 0 is allowed
+    and says nothing new: frame 0 always starts a scene).  Returns them sorted, without 0."""
+    if cuts is None:
+        return []
+    if isinstance(cuts, (str, bytes)):
+        raise ValueError("cuts must be an iterable of frame indices, got %r" % (cuts,))
+    out = set()
+    for c in cuts:
+        if isinstance(c, (bool, np.bool_)) or not isinstance(c, (int, np.integer)):
+            raise ValueError("cuts must hold ints (frame indices), got %r of type %s" % (c, type(c).__name__))
+        if not 0 <= c < F:
+            raise ValueError("cut index %d is outside the clip's frames [0, %d)" % (c, F))
+        out.add(int(c))
+    out.discard(0)
+    return sorted(out)
+
+
+def _scenes(cuts, F):
+    """[(a, b)]: the scenes [a, b) of an F-frame clip with the (checked) scene starts ``cuts``"""
+    edges = [0] + list(cuts) + [F]
+    return list(zip(edges[:-1], edges[1:]))
+
+
 def _bump_epoch(module, *_args, **_kwargs):
     # only registrations inside an engine's own module tree count (every module of it is tagged at construction and a sub-module
     # attached later inherits the tag): other models of the process building or mutating themselves leave the engines' caches alone
@@ -334,8 +358,21 @@ class _HipNet(nn.Module):
         p = next(self.parameters())
         return p.device if p.is_cuda else torch.device("cuda", torch.cuda.current_device())
 
-    def clip_forward(self, frames, halo_fn=None):
-        """frames: [T,C,H,W] -> [T,out_ch,H,W], layer-major over the whole clip."""
+    def clip_forward(self, frames, halo_fn=None, cuts=None):
+        """frames: [T,C,H,W] -> [T,out_ch,H,W], layer-major over the whole clip.  ``cuts``: frame indices that start a new scene
+        (check_cuts); every scene runs as a clip of its own into one output, so nothing is mixed across a cut."""
+        cuts = check_cuts(cuts, frames.shape[0])
+        if cuts:
+            if halo_fn is not None:
+                raise ValueError("clip_forward: halo_fn and cuts cannot be combined (a frame-window shard takes its neighbours' "
+                                 "halos at the clip ends; scene cuts inside a shard are not supported)")
+            out = None
+            for a, b in _scenes(cuts, frames.shape[0]):
+                y = self.clip_forward(frames[a:b])
+                if out is None:
+                    out = y.new_empty((frames.shape[0],) + tuple(y.shape[1:]))
+                out[a:b].copy_(y)
+            return out
         dev = self._device()
         with torch.no_grad(), torch.cuda.device(dev):
             ex = self._executor(dev)
@@ -537,9 +574,14 @@ class BSVD(_HipNet):
         eng = self._stream_eng
         return None if eng is None else dict(eng.stats, graphs=sum(1 for g in eng.graphs.values() if g[0]), plans=len(eng.plans))
 
-    def feedin_one_element(self, x):
+    def feedin_one_element(self, x, cut=False):
         """x: [1,C,H,W] tensor or None (flush).  Returns the frame fed ``shift_num`` steps earlier, or None.
-        Runs on preallocated rings; a step whose launch pattern has been seen before is one HIP-graph replay."""
+        Runs on preallocated rings; a step whose launch pattern has been seen before is one HIP-graph replay.
+        ``cut=True``: x starts a new scene.  No temporal-fusion conv mixes it with the frames before it (they see zeros in its place,
+        it sees zeros in theirs, exactly as at a clip's ends); latency and the None protocol are unchanged, nothing is flushed."""
+        if cut and x is None:
+            raise ValueError("cut=True needs a frame: a flush feed (x=None) starts no scene")
+        cut = bool(cut)
         dev = self._device()
         with torch.no_grad(), torch.cuda.device(dev):
             ex = self._executor(dev)
@@ -551,7 +593,7 @@ class BSVD(_HipNet):
             if eng is not None or (x is None and self._pipe is None):
                 if eng is None:
                     return None                  # flush before any frame: nothing is pending (like the reference)
-                y = eng.feed(x, (self.net.out_ch, self.clamp))        # a view of the exit ring: hand the caller a copy
+                y = eng.feed(x, (self.net.out_ch, self.clamp), cut=cut)        # a view of the exit ring: hand the caller a copy
                 return None if y is None else y.to(getattr(self, "_last_dtype", torch.float32), copy=True)
             if self._pipe is None:
                 self._pipe = StreamPipeline(self.net)
@@ -561,7 +603,7 @@ class BSVD(_HipNet):
                 xin = x.to(device=dev, dtype=torch.float32).contiguous()
                 if not pin:
                     xin = ex.to_nhwc(xin, self.net.temp1["inc0"].cin_pad)
-            y = self._pipe.feed(ex, xin, x_planar=pin, y_planar=(self.net.out_ch, self.clamp) if pout else None)
+            y = self._pipe.feed(ex, xin, x_planar=pin, y_planar=(self.net.out_ch, self.clamp) if pout else None, cut=cut)
             if y is None:
                 return None
             if not pout:
@@ -575,14 +617,16 @@ class BSVD(_HipNet):
         with torch.no_grad(), torch.cuda.device(dev):
             return self._stream_engine(self._executor(dev), tuple(frame_shape)) is not None
 
-    def feed_overlapped(self, x, last=False):
+    def feed_overlapped(self, x, last=False, cut=False):
         """Per-frame feed for hosts that pipeline anyway (``pipeline.LiveStream`` with depth >= 2): like ``feedin_one_element``,
         but DenBlock 2 runs ONE STEP BEHIND DenBlock 1 as the second branch of the step's HIP graph, so the single-frame
         launches of two independent layer chains share the chip (540x960: 0.95 instead of 0.89 of the clip rate).  The price
         is one feed of latency: the call returns the frame fed ``shift_num + 1`` feeds earlier (None before that).  End of
         stream: ``shift_num + 1`` feeds of None, then one call with ``last=True`` (drains the lagging DenBlock-2 step), then
         ``reset()``.  Same kernels on the same data as every other schedule: bit-identical frames.  Do not mix with
-        ``feedin_one_element`` inside one stream."""
+        ``feedin_one_element`` inside one stream.  ``cut=True``: x starts a new scene (see feedin_one_element)."""
+        if cut and (x is None or last):
+            raise ValueError("cut=True needs a frame: a flush feed (x=None, last=True) starts no scene")
         dev = self._device()
         with torch.no_grad(), torch.cuda.device(dev):
             ex = self._executor(dev)
@@ -596,25 +640,28 @@ class BSVD(_HipNet):
                     return None
                 raise RuntimeError("feed_overlapped needs the ring engine (stream_rings=True, planar edge layers, enough HBM); "
                                    "use feedin_one_element")
-            y = eng.feed_lagged(x, (self.net.out_ch, self.clamp), last=last)
+            y = eng.feed_lagged(x, (self.net.out_ch, self.clamp), last=last, cut=bool(cut))
             return None if y is None else y.to(getattr(self, "_last_dtype", torch.float32), copy=True)
 
-    def streaming_forward(self, input_seq):
+    def streaming_forward(self, input_seq, cuts=None):
         """Pipeline-style inference over a clip (bsvd_arch.py:501-552): F data feeds, then flush feeds until
         F + shift_num results exist; the first shift_num (None) are dropped; state is reset afterwards.
         With the whole list in hand the engine runs the same pipeline on rings with ``stream_chunk`` frames per step and
-        (``stream_overlap``) DenBlock 2 one step behind DenBlock 1; bit-identical to the frame-by-frame loop."""
+        (``stream_overlap``) DenBlock 2 one step behind DenBlock 1; bit-identical to the frame-by-frame loop.
+        ``cuts``: frame indices that start a new scene (check_cuts).  A chunk never spans a cut: a scene's last chunk is as short
+        as it has to be, also in mid-stream; the result is that of each scene run alone."""
         if isinstance(input_seq, torch.Tensor):
             input_seq = [input_seq[i:i + 1] for i in np.arange(input_seq.shape[0])]
         assert type(input_seq) == list, "convert the input into a sequence"
+        cuts = check_cuts(cuts, len(input_seq))
         if len(input_seq) > 0:
-            out = self._streaming_forward_rings(input_seq)
+            out = self._streaming_forward_rings(input_seq, cuts)
             if out is not None:
                 return out
         outs = []
         try:
-            for x in input_seq:
-                outs.append(self.feedin_one_element(x))
+            for i, x in enumerate(input_seq):
+                outs.append(self.feedin_one_element(x, cut=i in cuts))
             while len(outs) < self.shift_num + len(input_seq):
                 outs.append(self.feedin_one_element(None))
             self.feedin_one_element(None)      # the reference's extra, discarded flush call (:541-542)
@@ -622,7 +669,7 @@ class BSVD(_HipNet):
             self.reset()                       # also after an exception: never leave stale buffers behind
         return torch.cat(outs[self.shift_num:], dim=0)
 
-    def _streaming_forward_rings(self, input_seq):
+    def _streaming_forward_rings(self, input_seq, cuts=()):
         """The pipeline of the loop above on stream_plan.StreamEngine: n = ``stream_chunk`` consecutive frames per pipeline
         step and, with ``stream_overlap``, temp1(step k) and temp2(step k-1) -- which do not depend on each other -- as two
         parallel branches of one HIP graph.  The single-frame launches of the quarter-resolution layers do not fill 256 CUs
@@ -651,20 +698,25 @@ class BSVD(_HipNet):
             out_dtype = x0.dtype if x0.dtype in (torch.float16, torch.bfloat16) else torch.float32
             ypl = (self.net.out_ch, self.clamp)
             out = torch.empty((F, self.net.out_ch) + tuple(x0.shape[-2:]), dtype=out_dtype, device=dev)
-            chunks = [input_seq[i:i + n] for i in range(0, F, n)]
+            chunks = [input_seq[i:min(i + n, b)] for a, b in _scenes(cuts, F) for i in range(a, b, n)]     # no chunk spans a cut
+            starts, i = set(), 0
+            for k, c in enumerate(chunks):
+                if i in cuts:
+                    starts.add(k)
+                i += len(c)
             steps = len(chunks) + self.shift_num + 1                 # incl. the reference's extra, discarded flush call
             eng.clear()
             pos = 0
             try:
                 if self.stream_overlap:
                     for k in range(steps + 1):                       # step k issues temp1(k) and temp2(k-1)
-                        y = eng.feed_lagged(chunks[k] if k < len(chunks) else None, ypl, last=k == steps)
+                        y = eng.feed_lagged(chunks[k] if k < len(chunks) else None, ypl, last=k == steps, cut=k in starts)
                         if y is not None and pos < F:
                             out[pos:pos + y.shape[0]].copy_(y)
                             pos += y.shape[0]
                 else:
                     for k in range(steps):
-                        y = eng.feed(chunks[k] if k < len(chunks) else None, ypl)
+                        y = eng.feed(chunks[k] if k < len(chunks) else None, ypl, cut=k in starts)
                         if y is not None and pos < F:
                             out[pos:pos + y.shape[0]].copy_(y)
                             pos += y.shape[0]
@@ -674,15 +726,16 @@ class BSVD(_HipNet):
                 eng.clear()
 
     # ---- clip forward (bsvd_arch.py:490-499) -----------------------------------------------------
-    def forward(self, input, noise_map=None):
-        # N, F, C, H, W -> (N*F, C, H, W): like the reference, N>1 is one long clip
+    def forward(self, input, noise_map=None, cuts=None):
+        # N, F, C, H, W -> (N*F, C, H, W): like the reference, N>1 is one long clip (``cuts`` index its N*F frames: check_cuts)
         input = self._check_input(input, noise_map)
         N, F, C, H, W = input.shape
         frames = input.reshape(N * F, C, H, W)
+        cuts = check_cuts(cuts, N * F)
         self.last_mode = self._pick_mode(N * F, H, W)
         if self.last_mode == "clip":
             try:
-                out = self.clip_forward(frames)
+                out = self.clip_forward(frames, cuts=cuts) if cuts else self.clip_forward(frames)      # (no cut: the call it always was)
             except torch.cuda.OutOfMemoryError:
                 if self.engine_mode != "auto":
                     raise
@@ -691,7 +744,7 @@ class BSVD(_HipNet):
                 torch.cuda.empty_cache()
                 self.last_mode = "stream"
         if self.last_mode == "stream":
-            out = self.streaming_forward(frames)
+            out = self.streaming_forward(frames, cuts=cuts) if cuts else self.streaming_forward(frames)
         return out.reshape(N, F, out.shape[1], H, W)
 
     def _pick_mode(self, frames, H, W):

@@ -29,6 +29,11 @@ and the PCIe transfers stay picture-sized and the results have the shape and dty
 ``sigma`` is the noise level of the non-blind models' noise map: a float the caller knows, or 'auto' -- every frame's own estimate, computed
 on the compute stream from the converted frame and written into its noise-map plane (``frame_io.estimate_sigma``; ``sigma_gain`` scales
 it).  The host sees it only afterwards, as ``LiveStream.last_sigma``: 4 bytes that come down with the frame.
+
+``cuts`` is what the pipelines know about scene cuts: None (nothing: the footage is one scene, as before) or 'auto' -- every frame is scored
+against the one before it on the device (``frame_io.scene_scores`` / ``scene_cuts``; ``cut_threshold``) and a frame that scores as a scene
+start is fed with ``cut=True``: no temporal-fusion conv mixes the two scenes, nothing is flushed, latency is unchanged.  A caller who knows
+the cuts says so per frame instead (``LiveStream.feed(frame, cut=True)``).  Nothing is known about the score on real footage.
 """
 import collections
 
@@ -36,8 +41,9 @@ import numpy as np
 import torch
 
 from . import _lib
-from .frame_io import (_check_gain, _sigma_mode, _yuv_desc, _yuv_surface, frames_to_input, network_size, output_to_frames, output_to_yuv, output_to_yuv420,
-                       yuv420_frame_bytes, yuv420_picture_bytes, yuv420_to_input, yuv_to_input)
+from .frame_io import (CUT_THRESHOLD, _check_gain, _sigma_mode, _yuv_desc, _yuv_surface, check_cut_threshold, cut_scores, frames_to_input, network_size,
+                       output_to_frames, output_to_yuv, output_to_yuv420, scene_cuts, scene_scores, yuv420_frame_bytes, yuv420_picture_bytes, yuv420_to_input,
+                       yuv_to_input)
 
 Colour = collections.namedtuple("Colour", "matrix full_range chroma row_pitch width", defaults=("bt709", False, "linear", None, None))
 Colour.__doc__ = """How a YUV surface is to be read and written: matrix 'bt601' | 'bt709' | 'bt2020', full_range (False = limited / "TV"
@@ -195,6 +201,13 @@ def _pixel_format(pix_fmt, colour, pad=None, frame_shape=None):
     raise ValueError("pix_fmt %r: one of 'rgb24', 'nv12', 'p010', %s" % (pix_fmt, ", ".join(repr(n) for n in sorted(_lib.YUV_FORMATS))))
 
 
+def _check_cuts_mode(cuts, cut_threshold, what):
+    """the pipelines' ``cuts``: None or 'auto' -> (auto?, threshold).  Before anything touches a device."""
+    if cuts is not None and not (isinstance(cuts, str) and cuts == "auto"):
+        raise ValueError("%s: cuts must be None or 'auto' (known cuts: LiveStream.feed(frame, cut=True), BSVD.forward(cuts=[...])), got %r" % (what, cuts))
+    return cuts is not None, check_cut_threshold(cut_threshold)
+
+
 def _check_sigma(model, sigma, sigma_gain, what):
     """the pipelines' ``sigma``: None, a float or 'auto' -- which needs a noise-map channel to write into.  Before anything touches a device."""
     if isinstance(sigma, str) or sigma is None or not hasattr(sigma, "__len__"):
@@ -241,11 +254,18 @@ class ClipPipeline:
     pix_fmt 'yuv420p' | 'yuv420p10le' | 'uyvy422' | 'yuyv422' | 'nv16' | 'p210le' | 'yuv422p' | 'yuv422p10le' | 'yuv444p' | 'yuv444p10le'
     with frame_shape=(H, W): clips are [T, n] arrays of the tight frames' samples (uint8, uint16 for 10 bit), as ffmpeg's rawvideo.
     sigma='auto' (non-blind models): every frame's noise-map plane holds that frame's own estimate, times sigma_gain, computed on the
-    device (``frame_io.estimate_sigma``: what is known about it, and that YUV sources with subsampled chroma read low)."""
+    device (``frame_io.estimate_sigma``: what is known about it, and that YUV sources with subsampled chroma read low).
+    cuts='auto': the scene starts of every clip are detected on the device (``frame_io.scene_cuts`` at ``cut_threshold``; its docstring says
+    what is known about the rule -- nothing on real footage -- and its blind spot: a cut one or two frames after another scores low) and
+    handed to the model's forward, which runs every scene as a clip of its own.  The detection reads T integers back before the forward is
+    enqueued: the host waits for the clip's upload and conversion there.  ``last_cuts``: the cuts of the most recent clip submitted."""
 
-    def __init__(self, model, sigma=None, depth=2, pix_fmt="rgb24", colour=None, pad=None, frame_shape=None, sigma_gain=1.0):
+    def __init__(self, model, sigma=None, depth=2, pix_fmt="rgb24", colour=None, pad=None, frame_shape=None, sigma_gain=1.0, cuts=None,
+                 cut_threshold=CUT_THRESHOLD):
         if depth < 1:
             raise ValueError("depth must be >= 1")
+        self.auto_cuts, self.cut_threshold = _check_cuts_mode(cuts, cut_threshold, "ClipPipeline")
+        self.last_cuts = None
         self.sigma_gain = _check_sigma(model, sigma, sigma_gain, "ClipPipeline")
         self.fmt = _pixel_format(pix_fmt, colour, pad, frame_shape)
         self.model, self.sigma = model, sigma
@@ -282,10 +302,14 @@ class ClipPipeline:
                 self.comp.wait_event(slot.uploaded)
                 x = self.fmt.to_input(slot.dev_in, geom, self.sigma, self.sigma_gain)
                 T, _, H, W = x.shape
+                kw = {}
+                if self.auto_cuts:
+                    self.last_cuts = scene_cuts(x, self.cut_threshold, picture=(geom.h, geom.w))
+                    kw = dict(cuts=self.last_cuts)
                 if self.model._pick_mode(T, H, W) == "clip":
-                    y = self.model.clip_forward(x)
+                    y = self.model.clip_forward(x, **kw)
                 else:
-                    y = self.model.streaming_forward(x)
+                    y = self.model.streaming_forward(x, **kw)
                 slot.dev_out = self.fmt.to_output(y.float(), geom)  # held by the slot until its download completed
                 slot.computed.record()
             with torch.cuda.stream(self.down):
@@ -345,14 +369,29 @@ class LiveStream:
     what they are with a float.  ``last_sigma``: the estimate (a float, [0,1] units) of the most recent input step ``feed`` has already
     waited for -- i.e. of the frame fed ``depth - 1`` calls ago --, None before that; it comes down on the download stream into the slot's
     pinned memory beside the frame and is never read earlier.  Nothing is known about the estimate on real footage, and YUV sources with
-    subsampled chroma read low (``sigma_gain``)."""
+    subsampled chroma read low (``sigma_gain``).
+
+    Scene cuts.  ``feed(frame, cut=True)`` says that ``frame`` starts a new scene: no temporal-fusion conv mixes it with the frames before it
+    (each side sees zeros for the other, as at a stream's ends), nothing is flushed and no feed returns None because of it.  The steps a cut
+    passes through have launch plans of their own: batched launches at the first sighting, captured when the same ring phase recurs.
+    cuts='auto' finds the cuts itself (``cut=True`` is refused then): the conversion, the two detector kernels (``frame_io.scene_scores``
+    against the previous frame's grid, kept on the device) and an 8-byte copy run on the upload stream behind the frame's copy, and the host
+    waits for them before it plans the step -- the step before is already enqueued, so ``depth >= 2`` keeps its overlap.  A frame whose score
+    (``frame_io.scene_cuts``' rule, carried from frame to frame) reaches ``cut_threshold`` starts a scene.  ``last_cut_score`` /
+    ``last_cut``: score and decision of the most recent frame fed.  ``flush()`` forgets the previous frame.  With cuts=None the stream order
+    is what it always was.  Nothing is known about the rule on real footage, the default threshold has met none, and a cut one or two
+    frames after another cut scores low (``frame_io.scene_cuts``)."""
 
     def __init__(self, model, sigma=None, depth=2, overlap_blocks=None, frame_shape=None, pix_fmt="rgb24", colour=None, pad=None,
-                 sigma_gain=1.0):
+                 sigma_gain=1.0, cuts=None, cut_threshold=CUT_THRESHOLD):
         """frame_shape: optional (H, W) of the frames to come (the picture, also with ``pad``) -- the overlap decision (and with it
         ``latency``) is then final at construction instead of at the first feed."""
         if depth < 1:
             raise ValueError("depth must be >= 1")
+        self.auto_cuts, self.cut_threshold = _check_cuts_mode(cuts, cut_threshold, "LiveStream")
+        self.last_cut_score, self.last_cut = None, False
+        self._grids = self._sad = self._pin_sad = None       # cuts='auto': two alternating grid buffers, the step's sum on the device and pinned
+        self._have_prev, self._prev_mafd, self._n_scored = False, 0.0, 0
         self.sigma_gain = _check_sigma(model, sigma, sigma_gain, "LiveStream")
         self.auto_sigma = isinstance(sigma, str)
         self.last_sigma = None
@@ -417,6 +456,35 @@ class LiveStream:
                 s.pin_sigma = torch.zeros(1, dtype=torch.float32).pin_memory()
                 s.dev_sigma = torch.empty(1, dtype=torch.float32, device=self.device)
             self.slots.append(s)
+        if self.auto_cuts:
+            gh, gw = geom.h // 16, geom.w // 16
+            self._grids = torch.zeros((2, 1, gh, gw), dtype=torch.int32, device=self.device)
+            self._sad = torch.zeros(1, dtype=torch.int64, device=self.device)
+            self._pin_sad = torch.zeros(1, dtype=torch.int64).pin_memory()
+            self._scored = torch.cuda.Event()
+            self._forget_scene()
+
+    def _forget_scene(self):
+        self._have_prev, self._prev_mafd = False, 0.0
+
+    def _detect(self, slot):
+        """cuts='auto', on the upload stream behind the frame's copy: conversion, grid, difference against the previous frame's grid, 8 bytes
+        to pinned memory; the host waits for them and decides.  -> (the network input, handed on to the compute stream; cut?)"""
+        x = self.fmt.to_input(slot.dev_in, self.geom, self.sigma, self.sigma_gain)
+        x.record_stream(self.comp)
+        cur = self._grids[self._n_scored % 2]
+        prev = self._grids[(self._n_scored + 1) % 2][0] if self._have_prev else None
+        scene_scores(x, picture=(self.geom.h, self.geom.w), prev=prev, out=(self._sad, cur))
+        self._pin_sad.copy_(self._sad, non_blocking=True)
+        self._scored.record()
+        slot.uploaded.record()
+        self._scored.synchronize()
+        score, mafd = cut_scores([int(self._pin_sad[0])], cur.shape[1] * cur.shape[2], self._prev_mafd)
+        self._n_scored += 1
+        self._have_prev, self._prev_mafd = True, mafd[0]
+        self.last_cut_score = score[0]
+        self.last_cut = score[0] >= self.cut_threshold
+        return x, self.last_cut
 
     def _pop(self):
         """oldest in-flight step -> its uint8 frame, or None if that step emitted nothing (pipeline fill)"""
@@ -426,25 +494,30 @@ class LiveStream:
             self.last_sigma = float(slot.pin_sigma[0])
         return slot.pin_out.numpy().copy().view(self.fmt.dtype).reshape(self.shape) if has_out else None
 
-    def _step(self, frame_u8, last=False):
+    def _step(self, frame_u8, last=False, cut=False):
         if frame_u8 is not None:
             self._decide_overlap(self.geom.net_h, self.geom.net_w)
         slot = self.slots[self.count % len(self.slots)]
         self.count += 1
         with torch.cuda.device(self.device):
+            x = None
             if frame_u8 is not None:
                 slot.pin_in.numpy()[...] = frame_u8.view(np.uint8).reshape(self.geom.staging)
                 with torch.cuda.stream(self.up):
                     slot.dev_in[0].copy_(slot.pin_in, non_blocking=True)
-                    slot.uploaded.record()
+                    if self.auto_cuts:
+                        x, cut = self._detect(slot)
+                    else:
+                        slot.uploaded.record()
             with torch.cuda.stream(self.comp):
-                x = None
                 if frame_u8 is not None:
                     self.comp.wait_event(slot.uploaded)
-                    x = self.fmt.to_input(slot.dev_in, self.geom, self.sigma, self.sigma_gain)
+                    if x is None:
+                        x = self.fmt.to_input(slot.dev_in, self.geom, self.sigma, self.sigma_gain)
                     if self.auto_sigma:
                         slot.dev_sigma.copy_(x[0, -1, 0, :1])          # the plane holds the estimate: one element of it, device to device
-                y = self.model.feed_overlapped(x, last=last) if self.overlap else self.model.feedin_one_element(x)
+                kw = dict(cut=True) if cut else {}
+                y = self.model.feed_overlapped(x, last=last, **kw) if self.overlap else self.model.feedin_one_element(x, **kw)
                 if y is not None:
                     slot.dev_out = self.fmt.to_output(y.float(), self.geom)   # held by the slot until its download completed
                 slot.computed.record()
@@ -463,7 +536,10 @@ class LiveStream:
             if r is not None:
                 outs.append(r)
 
-    def feed(self, frame_u8):
+    def feed(self, frame_u8, cut=False):
+        """cut=True: this frame starts a new scene (refused with cuts='auto', which decides that itself)"""
+        if cut and self.auto_cuts:
+            raise ValueError("LiveStream(cuts='auto') finds the cuts itself: feed(frame, cut=True) is for streams constructed with cuts=None")
         frame_u8 = np.ascontiguousarray(frame_u8)
         geom = self.fmt.geometry(frame_u8, clip=False)
         if self.shape != frame_u8.shape:
@@ -471,7 +547,7 @@ class LiveStream:
                 raise ValueError("frame size changed mid-stream; flush() first")
             self._reopen_overlap()                    # the rings of another frame size may or may not fit
             self._alloc(frame_u8.shape, geom)
-        self._step(frame_u8)                          # step k is in flight ...
+        self._step(frame_u8, cut=bool(cut))           # step k is in flight ...
         outs = []
         self._drain(self.depth - 1, outs)             # ... while step k - (depth-1) is waited for and handed out
         return outs[0] if outs else None
@@ -489,5 +565,6 @@ class LiveStream:
             self._step(None, last=True)
         self._drain(0, outs)
         self.model.reset()
+        self._forget_scene()
         self._reopen_overlap()                        # the next stream decides again (free HBM may have changed)
         return outs

@@ -126,20 +126,36 @@ class _TsmStage:
     frame (chunk) before it (its channels [fold:2fold] are what ShiftConv reads; None = zeros at stream start).
     Like the reference, ``past`` survives a flush and is only cleared by reset()."""
 
-    def __init__(self, spec):
+    def __init__(self, spec, *, cuts=None):
         self.spec = spec
         self.mid = None
         self.past = None
         self.past_valid = False
+        # scene cuts: ``cuts`` is the stream's shared set of input indices that start a scene (None: the stream has none).  Every stage
+        # sees every frame (chunk) once, in order, so it counts its own non-None inputs and looks the index up.
+        self.cuts = cuts
+        self.n_seen = 0
+        self.mid_cut = False
 
     def reset(self):
         self.mid = None
         self.past = None
         self.past_valid = False
+        self.n_seen = 0
+        self.mid_cut = False
+
+    def _starts_scene(self, nxt):
+        """does the input ``nxt`` start a scene?  (counts it)"""
+        if nxt is None:
+            return False
+        i = self.n_seen
+        self.n_seen = i + 1
+        return bool(self.cuts) and i in self.cuts
 
     def feed(self, ex, nxt):
+        nxt_cut = self._starts_scene(nxt)
         if self.mid is None:
-            self.mid = nxt
+            self.mid, self.mid_cut = nxt, nxt_cut
             if nxt is not None and not self.past_valid:
                 self.past, self.past_valid = None, True     # zeros
             return None
@@ -148,10 +164,11 @@ class _TsmStage:
         # a step may carry a chunk of several consecutive frames ([n,H,W,C], stream_plan's chunked streaming_forward):
         # inside the chunk the kernel reads frames t-1 / t+1 itself; the halos are the previous chunk's LAST frame and
         # the next chunk's FIRST frame
-        hp = None if self.past is None else Halo(self.past if self.past.shape[0] == 1 else self.past[-1:], cpad, sp.fold)
-        hn = None if nxt is None else Halo(nxt, cpad, 0)
+        # a scene cut is a clip end on both sides: the scene's first frame (chunk) reads zeros for t-1, its last one zeros for t+1
+        hp = None if self.past is None or self.mid_cut else Halo(self.past if self.past.shape[0] == 1 else self.past[-1:], cpad, sp.fold)
+        hn = None if nxt is None or nxt_cut else Halo(nxt, cpad, 0)
         y = ex.conv(sp, cur, halo_prev=hp, halo_next=hn)
-        self.past, self.mid = cur, nxt
+        self.past, self.mid, self.mid_cut = cur, nxt, nxt_cut
         return y
 
 
@@ -173,9 +190,9 @@ class _SkipFifo:
 
 
 class _DenBlockStream:
-    def __init__(self, S):
+    def __init__(self, S, *, cuts=None):
         self.S = S
-        self.stage = {n: _TsmStage(S[n]) for n in S if S[n].tsm}
+        self.stage = {n: _TsmStage(S[n], cuts=cuts) for n in S if S[n].tsm}
         self.skip_in, self.skip_x0, self.skip_x1 = _SkipFifo(), _SkipFifo(), _SkipFifo()
 
     def reset(self):       # DenBlock.reset only resets the BiBufferConvs (bsvd_arch.py:352-356)
@@ -215,21 +232,58 @@ class _DenBlockStream:
         return _outc(ex, S, w, base, eps, ecs, y_planar)
 
 
+class _CutSet:
+    """The scene starts of one stream that are still inside the pipeline: ``pending`` holds input indices (counted from the last
+    reset) and is the set every _TsmStage of the stream looks its own input count up in."""
+
+    def __init__(self):
+        self.pending = set()
+        self.n_in = 0
+
+    def clear(self):
+        self.pending.clear()
+        self.n_in = 0
+
+    def note(self, x, cut):
+        """called once per step with the step's input, before the stages see it"""
+        if x is None:
+            if cut:
+                raise ValueError("cut=True needs a frame: a flush step (x=None) starts no scene")
+            return
+        if cut:
+            self.pending.add(self.n_in)
+        self.n_in += 1
+
+    def prune(self, last_block):
+        """forgets the entries the last stage of the pipeline has passed (it keeps its pending frame's flag itself)"""
+        if self.pending:
+            seen = last_block.stage["u1c2"].n_seen
+            for i in [i for i in self.pending if i < seen]:
+                self.pending.discard(i)
+
+
 class StreamPipeline:
     """feedin_one_element on device buffers: x is a [1,H,W,cin_pad] NHWC tensor or None (flush)."""
 
     def __init__(self, net):
-        self.t1 = _DenBlockStream(net.temp1)
-        self.t2 = _DenBlockStream(net.temp2)
+        self.cuts = _CutSet()
+        self.t1 = _DenBlockStream(net.temp1, cuts=self.cuts.pending)
+        self.t2 = _DenBlockStream(net.temp2, cuts=self.cuts.pending)
         self.shift_num = net.shift_num
 
     def reset(self):
         self.t1.reset()
         self.t2.reset()
+        self.cuts.clear()
 
     def clear(self):
         self.t1.clear()
         self.t2.clear()
+        self.cuts.clear()
 
-    def feed(self, ex, x, x_planar=False, y_planar=None):
-        return self.t2.feed(ex, self.t1.feed(ex, x, x_planar=x_planar), y_planar=y_planar)
+    def feed(self, ex, x, x_planar=False, y_planar=None, *, cut=False):
+        """cut=True: x starts a new scene -- no temporal-fusion conv mixes it (or anything after it) with the frames before it"""
+        self.cuts.note(x, cut)
+        y = self.t2.feed(ex, self.t1.feed(ex, x, x_planar=x_planar), y_planar=y_planar)
+        self.cuts.prune(self.t2)
+        return y

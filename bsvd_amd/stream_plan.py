@@ -32,7 +32,7 @@ from collections import OrderedDict, namedtuple
 import torch
 
 from .netspec import out_hwc
-from .schedule import _DenBlockStream, _fused_head, _fused_pair
+from .schedule import _CutSet, _DenBlockStream, _fused_head, _fused_pair
 
 RING_PERIOD = 10            # every ring depth divides it -> the steady-state signature has period 10
 _DEPTHS = (1, 2, 5, 10)
@@ -181,8 +181,9 @@ class StreamEngine:
         for name, sp, shape, depth in _ring_layout(net, H, W, n):
             if sp.key not in fused_away:
                 ring(sp.key, shape, depth, out_v(sp) if out_v else 0)
-        self.t1 = _DenBlockStream(net.temp1)
-        self.t2 = _DenBlockStream(net.temp2)
+        self.cuts = _CutSet()       # scene starts still inside the pipeline (schedule._TsmStage looks them up)
+        self.t1 = _DenBlockStream(net.temp1, cuts=self.cuts.pending)
+        self.t2 = _DenBlockStream(net.temp2, cuts=self.cuts.pending)
         self.r1 = _Recorder(self)
         self.r2 = _Recorder(self)
         self.n_in = 0
@@ -235,6 +236,7 @@ class StreamEngine:
         """DenBlock.reset (bsvd_arch.py:352-356): only the BiBufferConv state."""
         self.t1.reset()
         self.t2.reset()
+        self.cuts.clear()
 
     def clear(self):
         """New stream: buffers, skip FIFOs and ring positions (so that pipeline-fill plans repeat from clip to clip)."""
@@ -242,6 +244,7 @@ class StreamEngine:
         self.t2.clear()
         self.r1.reset()
         self.r2.reset()
+        self.cuts.clear()
         self.n_in = 0
         self._lag = None
         self._mode = None           # 'feed' | 'lagged': the two step protocols must not be mixed inside one stream
@@ -379,22 +382,27 @@ class StreamEngine:
                                "streaming_forward); reset() between them" % (self._mode, mode))
 
     # ---- the two entry points ------------------------------------------------------------------
-    def feed(self, x, y_planar):
+    def feed(self, x, y_planar, *, cut=False):
         """One ``feedin_one_element`` step: both DenBlocks of this step, in order.  Returns a VIEW of the exit ring slot
-        (valid until the next-but-one step; callers copy it) or None."""
+        (valid until the next-but-one step; callers copy it) or None.  ``cut``: x starts a new scene (a chunk must not span one):
+        the steps it passes through have launch plans of their own (a halo address of 0 where the neighbour is the other scene)."""
         self._enter("feed")
+        self.cuts.note(x, cut)
         self.stats["steps"] += 1
         xin = self._stage_input(x)
         y1, s1, p1 = self._plan(self.t1, self.r1, xin, True, None)
         y2, s2, p2 = self._plan(self.t2, self.r2, y1, False, y_planar)
+        self.cuts.prune(self.t2)
         self._issue((s1, s2), (p1, p2), ())
         return y2
 
-    def feed_lagged(self, x, y_planar, last=False):
+    def feed_lagged(self, x, y_planar, last=False, *, cut=False):
         """``streaming_forward`` step k: DenBlock 1 of step k and DenBlock 2 of step k-1 as two independent chains (one graph
         with two branches).  Returns DenBlock 2's result of step k-1 (a ring view; None for k = 0).  ``last``: only drain the
-        lagging DenBlock-2 step (no DenBlock-1 work)."""
+        lagging DenBlock-2 step (no DenBlock-1 work).  ``cut``: x starts a new scene; DenBlock 2 meets the same input index one step
+        later (its stages count their own inputs), so nothing is handed over with the frame."""
         self._enter("lagged")
+        self.cuts.note(None if last else x, cut)
         self.stats["steps"] += 1
         had_lag, lag = self._lag is not None, (self._lag[0] if self._lag is not None else None)
         plans_a, plans_b, sa, sb, y2 = (), (), (), (), None
@@ -408,5 +416,6 @@ class StreamEngine:
         if had_lag:
             y2, sb, pb = self._plan(self.t2, self.r2, lag, False, y_planar, shared_chip=True)
             plans_b = (pb,)
+            self.cuts.prune(self.t2)
         self._issue(("lag", sa, sb), plans_b, plans_a)
         return y2

@@ -523,6 +523,35 @@ int bsvd_fill_sigma_plane(float *x, int32_t frames, int32_t channels, int32_t Hp
                           void *stream);
 
 /*
+ * What a scene-cut detector needs from a frame, computed on the device.  Each temporal-fusion conv mixes a frame with its two neighbours; a
+ * caller who knows where a scene starts passes halo_prev = NULL / halo_next = NULL there (a clip end in mid-stream).  These two entry points
+ * serve the caller who does not know: they reduce the planar fp32 tensor the *_to_planar entry points build -- so the result does not depend
+ * on the pixel format -- to one integer per frame pair; the decision (a threshold on it) is the host's.  Added without a new
+ * BSVD_ABI_VERSION: discover the two entry points by symbol (dlsym), like the sigma entry points above.
+ *
+ * Exactly (tests/scene_model.py reproduces both results bit for bit):
+ *   input   x [frames][>= 3][Hp][Wp] fp32, frames `frame_stride` FLOATS apart (>= 3 * Hp * Wp), rows Wp apart.  The picture is the top-left
+ *           H x W of each plane (0 <= H <= Hp, 0 <= W <= Wp); only its full 16 x 16 blocks count: GH = H / 16, GW = W / 16.
+ *   value   q = clamp(rint(255 v), 0, 255) per plane value, halves to even, NaN -> 0; L = qR + 2 qG + qB per pixel (0 .. 1020).
+ *   grid    grid[t][by][bx] (int32, [frames][GH * GW]) = the sum of L over block (by, bx): 0 .. 261120.  (256 pixels a block: white noise
+ *           is averaged down by 16.)
+ *   sad     sad[t] (uint64) = sum over the blocks of |grid[t][b] - grid[t-1][b]|; for t = 0, prev_grid [GH * GW] stands in for grid[-1],
+ *           and prev_grid == NULL gives sad[0] = 0.
+ * Integer sums only: neither result depends on the launch shape.
+ *
+ * bsvd_scene_grid: rows move as float4 when x is 16-byte aligned and Wp and frame_stride are multiples of 4, as scalars otherwise.
+ *   GH * GW == 0 is valid: nothing is written and nothing launched (grid may be NULL then).  Returns -3, naming the argument in
+ *   bsvd_last_error(), for: a NULL or misaligned pointer; frames outside 1 .. 65535; H or W negative; Hp or Wp not positive; Hp < H or
+ *   Wp < W; frame_stride below 3 * Hp * Wp.  All of it without a device.
+ * bsvd_scene_diff: zeroes sad[frames] itself, on the stream.  blocks = GH * GW; blocks == 0 is valid and leaves every sum 0 without a
+ *   kernel.  -3 for: frames outside 1 .. 65535; blocks negative; sad NULL or not 8-byte aligned; grid NULL with blocks > 0; grid or
+ *   prev_grid not 4-byte aligned.
+ */
+int bsvd_scene_grid(const float *x, int32_t frames, int32_t H, int32_t W, int32_t Hp, int32_t Wp, int64_t frame_stride, int32_t *grid,
+                    void *stream);
+int bsvd_scene_diff(const int32_t *grid, const int32_t *prev_grid, int32_t frames, int32_t blocks, uint64_t *sad, void *stream);
+
+/*
  * Frame-window sharding: gathers the channel slice [c0, c0+n) of one NHWC frame into
  * a compact [H*W][n] buffer -- the message a rank sends to its temporal neighbour
  * (first frame, c0 = 0 -> the left neighbour's halo_next; last frame, c0 = fold -> the right

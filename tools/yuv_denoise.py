@@ -10,6 +10,9 @@ steady_frames_per_s (wall clock, reads and writes included) over the steady stat
     python tools/yuv_denoise.py IN OUT --size 1920x1080 --sigma auto [--sigma-gain 1.0]      the noise level of every frame estimated on the
                                 device (LiveStream(sigma='auto')); the JSON line then carries last_sigma, in 8-bit code units.  Untested on
                                 real footage; with subsampled chroma the estimate reads low, which --sigma-gain corrects
+    python tools/yuv_denoise.py IN OUT --size 1920x1080 --sigma 30 --cuts auto [--cut-threshold 10]      scene cuts detected on the device
+                                (LiveStream(cuts='auto')): no frame is mixed with a frame of another scene; the JSON line then carries the
+                                frame numbers found.  Untested on real footage; a cut one or two frames after another cut scores low
 
     ffmpeg -i in.mp4 -pix_fmt yuv420p -f rawvideo - | python tools/yuv_denoise.py - - --size 1920x1080 --sigma 30 | ffmpeg -f rawvideo ...
                                                                                   (--pix-fmt defaults to yuv420p, ffmpeg's own default)
@@ -49,6 +52,8 @@ def main(argv=None):
     ap.add_argument("--pix-fmt", default="yuv420p", choices=["nv12", "p010"] + sorted(_lib.YUV_FORMATS))
     ap.add_argument("--sigma", type=parse_sigma, required=True, help="noise std in 8-bit code units (e.g. 30), or auto: estimated per frame on the device")
     ap.add_argument("--sigma-gain", type=float, default=1.0, help="factor on the estimate of --sigma auto")
+    ap.add_argument("--cuts", default="none", choices=["none", "auto"], help="auto: scene cuts detected per frame on the device")
+    ap.add_argument("--cut-threshold", type=float, default=frame_io.CUT_THRESHOLD, help="score at which --cuts auto declares a scene start")
     ap.add_argument("--matrix", default="bt709", choices=["bt601", "bt709", "bt2020"])
     ap.add_argument("--full-range", action="store_true")
     ap.add_argument("--chroma", default="linear", choices=["nearest", "linear"])
@@ -72,7 +77,9 @@ def main(argv=None):
     m = bsvd_amd.BSVD(chns=[64, 128, 256], mid_ch=64, norm="none", act="relu6", interm_ch=64, pretrain_ckpt=a.ckpt,
                       precision=a.precision).to(torch.device("cuda", 0)).eval()
     live = LiveStream(m, sigma=a.sigma, sigma_gain=a.sigma_gain, depth=a.depth, frame_shape=(H, W), pix_fmt=a.pix_fmt,
-                      colour={"matrix": a.matrix, "full_range": a.full_range, "chroma": a.chroma}, pad=pad)
+                      colour={"matrix": a.matrix, "full_range": a.full_range, "chroma": a.chroma}, pad=pad,
+                      cuts="auto" if a.cuts == "auto" else None, cut_threshold=a.cut_threshold)
+    found = []
     fin = sys.stdin.buffer if a.input == "-" else open(a.input, "rb")
     fout = sys.stdout.buffer if a.output == "-" else open(a.output, "wb")
     n_in = n_out = 0
@@ -83,6 +90,8 @@ def main(argv=None):
         t1 = time.perf_counter()
         r = live.feed(frame)
         ms.append((time.perf_counter() - t1) * 1e3)
+        if live.last_cut:
+            found.append(n_in)
         n_in += 1
         if r is not None:
             fout.write(r.tobytes())
@@ -105,6 +114,9 @@ def main(argv=None):
     if a.sigma == "auto":
         res["sigma_gain"] = a.sigma_gain
         res["last_sigma"] = None if live.last_sigma is None else live.last_sigma * 255.0
+    if a.cuts == "auto":
+        res["cut_threshold"] = a.cut_threshold
+        res["cuts"] = found
     print(json.dumps(res), file=sys.stderr if a.output == "-" else sys.stdout, flush=True)
     return res
 
