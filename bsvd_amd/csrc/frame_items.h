@@ -1,10 +1,11 @@
-// frame_items.h -- the frame I/O kernels' work on ONE item, as plain __host__ __device__ functions: the sample groups of frame_yuv.hip
-// (load_codes / store_codes) and the item bodies of the pad / crop entry points (include/bsvd_hip.h: bsvd_u8_to_planar_pad,
-// bsvd_planar_to_u8_crop, bsvd_yuv420_to_planar_pad, bsvd_planar_to_yuv420_crop).  The kernels are grid-stride loops around these bodies;
-// a host program can run the same bodies over exact-size heap buffers under AddressSanitizer (tools/debug/frame_pad_bounds.hip), which
-// sees the reads a GPU run cannot show: the tail of a half item, pitch padding, the bytes behind the last row of the last frame.
+// frame_items.h -- the frame I/O kernels' work on ONE item, as plain __host__ __device__ functions: the item bodies of the uint8 pad / crop
+// entry points (include/bsvd_hip.h: bsvd_u8_to_planar_pad, bsvd_planar_to_u8_crop), and what they share with the YUV bodies of
+// frame_surface_items.h and with frame_sigma_items.h: the item -> address arithmetic, the mirror images of the pad region and the
+// constants of the colour conversion.  The kernels are grid-stride loops around these bodies; a host program can run the same bodies over
+// exact-size heap buffers under AddressSanitizer (tools/debug/frame_pad_bounds.hip, tools/debug/yuv_surface_bounds.hip), which sees the
+// reads a GPU run cannot show: the tail of a part item, pitch padding, the bytes behind the last row of the last frame.
 //
-// Pad rule (one for all four): the picture is H x W, the network's tensor Hp x Wp with Hp >= H, Wp >= W, pad on the right and bottom only,
+// Pad rule (one for all entry points): the picture is H x W, the network's tensor Hp x Wp with Hp >= H, Wp >= W, pad on the right and bottom only,
 // padded element (r, c) = converted picture element (refl_H(r), refl_W(c)), refl_N(i) = i below N, else 2 (N - 1) - i (torch's 'reflect').
 // On the way in, the lane that owns a picture element writes it AND its mirror images (at most one row image, one column image and the
 // corner they span): every destination element has exactly one writer, and a pad element holds the bits of its source by construction.
@@ -17,31 +18,6 @@
 #define BSVD_HD __host__ __device__ __forceinline__
 
 namespace bsvd {
-
-template <int PIX> struct Pix;
-template <> struct Pix<BSVD_PIX_NV12> { using S = uint8_t;  static constexpr int SHIFT = 0; };
-template <> struct Pix<BSVD_PIX_P010> { using S = uint16_t; static constexpr int SHIFT = 6; };   // 10-bit code in the high bits of the word
-
-// N consecutive samples of a surface row.  A surface promises no more than its sample's own alignment (pitch and base are the caller's),
-// hence the memcpy: one load / store of the group's width, legal at any sample-aligned address.
-template <int PIX, int N>
-BSVD_HD void load_codes(const uint8_t *p, float *out)
-{
-    typename Pix<PIX>::S v[N];
-    __builtin_memcpy(v, __builtin_assume_aligned(p, sizeof(v[0])), sizeof(v));
-#pragma unroll
-    for (int k = 0; k < N; ++k) out[k] = (float)(v[k] >> Pix<PIX>::SHIFT);
-}
-
-// scaled values -> legal codes (clamp, round half to even like planar_to_u8_kernel) -> N samples in one store
-template <int PIX, int N = 4>
-BSVD_HD void store_codes(uint8_t *p, const float *val, float lo, float hi)
-{
-    typename Pix<PIX>::S v[N];
-#pragma unroll
-    for (int k = 0; k < N; ++k) v[k] = (typename Pix<PIX>::S)((unsigned)rintf(fminf(fmaxf(val[k], lo), hi)) << Pix<PIX>::SHIFT);
-    __builtin_memcpy(__builtin_assume_aligned(p, sizeof(v[0])), v, sizeof(v));
-}
 
 // decode: codes -> (Y - y_off) * y_mul, (C - c_off) * c_mul -> R = y + r_cr cr, G = y - g_cr cr - g_cb cb, B = y + b_cb cb.  NOT clamped.
 struct YuvDecode { float y_off, y_mul, c_off, c_mul, r_cr, g_cr, g_cb, b_cb; };
@@ -208,158 +184,6 @@ BSVD_HD void planar_to_u8_crop_item(const float *src, uint8_t *dst, const U8Geom
                 else for (int q = 0; q < it.n; ++q) o[q] = b[q];
             }
         }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// YUV 4:2:0 <-> planar fp32 with pad / crop.  The item of frame_yuv.hip, 4 columns x 2 rows with the one chroma row under them; W % 4 == 2
-// leaves a HALF item at the right edge (2 luma samples per row, one CbCr pair), H / 2 may be odd.  Hp is even and Wp a multiple of 4, so
-// every picture item owns float4-aligned positions of the planes.
-struct YuvPadGeom { int H, W, Hp, Wp, cc; int64_t pitch, fstride; float const_val; };
-
-// N = 4: a whole item; N = 2: the half item.  Straight-line in either: every load of the item is issued before the first is needed.
-template <int PIX, int LINEAR, int N>
-BSVD_HD void yuv420_to_planar_pad_body(const uint8_t *src, float *dst, const YuvPadGeom &g, const YuvDecode &k, const PadItem &it)
-{
-    constexpr int SB = (int)sizeof(typename Pix<PIX>::S);
-    const int hh = g.H >> 1, j = it.row >> 1;
-    const int64_t plane = (int64_t)g.Hp * g.Wp;
-    const uint8_t *py = src + it.f * g.fstride + (int64_t)it.row * g.pitch + it.x0 * SB;
-    const uint8_t *pc = src + it.f * g.fstride + (int64_t)g.H * g.pitch + it.x0 * SB;    // + row * pitch: the item's CbCr pairs of a chroma row
-    float Y[2][4] = {}, cb[2][4], cr[2][4];
-    load_codes<PIX, N>(py, Y[0]);
-    load_codes<PIX, N>(py + g.pitch, Y[1]);
-    if (!LINEAR) {
-        float c[4];                                              // Cb0 Cr0 Cb1 Cr1
-        load_codes<PIX, N>(pc + (int64_t)j * g.pitch, c);
-        if (N == 2) { c[2] = c[0]; c[3] = c[1]; }
-#pragma unroll
-        for (int r = 0; r < 2; ++r) {
-            cb[r][0] = cb[r][1] = c[0]; cb[r][2] = cb[r][3] = c[2];
-            cr[r][0] = cr[r][1] = c[1]; cr[r][2] = cr[r][3] = c[3];
-        }
-    } else {
-        // chroma sample (i, j) sits at luma (2i, 2j + 0.5): rows j - 1, j, j + 1 and the pair right of the item's, clamped at the PICTURE's edges
-        const int rows[3] = {j > 0 ? j - 1 : 0, j, j + 1 < hh ? j + 1 : hh - 1};
-        const int xn = (it.x0 + 4 < g.W ? it.x0 + 4 : g.W - 2) - it.x0;
-        float a[3][6];                                           // Cb0 Cr0 Cb1 Cr1 Cb2 Cr2 of each row
-#pragma unroll
-        for (int r = 0; r < 3; ++r) {
-            const uint8_t *p = pc + (int64_t)rows[r] * g.pitch;
-            load_codes<PIX, N>(p, a[r]);
-            if (N == 4) {
-                load_codes<PIX, 2>(p + xn * SB, a[r] + 4);
-            } else {                                             // the half item's one pair is the row's last: its right neighbour is itself
-                a[r][2] = a[r][4] = a[r][0];
-                a[r][3] = a[r][5] = a[r][1];
-            }
-        }
-        // vertical first, then horizontal; dyadic weights on <= 10-bit integers: exact in fp32
-#pragma unroll
-        for (int r = 0; r < 2; ++r) {
-            float v[6];
-#pragma unroll
-            for (int q = 0; q < 6; ++q) v[q] = r == 0 ? 0.25f * a[0][q] + 0.75f * a[1][q] : 0.75f * a[1][q] + 0.25f * a[2][q];
-            cb[r][0] = v[0]; cb[r][1] = 0.5f * (v[0] + v[2]); cb[r][2] = v[2]; cb[r][3] = 0.5f * (v[2] + v[4]);
-            cr[r][0] = v[1]; cr[r][1] = 0.5f * (v[1] + v[3]); cr[r][2] = v[3]; cr[r][3] = 0.5f * (v[3] + v[5]);
-        }
-    }
-    float *d = dst + it.f * (3 + g.cc) * plane;
-    const float kc[4] = {g.const_val, g.const_val, g.const_val, g.const_val};
-    float rgb[2][3][4];
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const float y = (Y[r][q] - k.y_off) * k.y_mul;
-            const float u = (cb[r][q] - k.c_off) * k.c_mul, v = (cr[r][q] - k.c_off) * k.c_mul;
-            rgb[r][0][q] = fmaf(k.r_cr, v, y);
-            rgb[r][1][q] = fmaf(-k.g_cb, u, fmaf(-k.g_cr, v, y));
-            rgb[r][2][q] = fmaf(k.b_cb, u, y);
-        }
-        float *own = d + (int64_t)(it.row + r) * g.Wp + it.x0;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) put_own(own + c * plane, N, rgb[r][c], 1);
-        for (int c = 0; c < g.cc; ++c) put_own(own + (3 + c) * plane, N, kc, 1);
-    }
-    // the images: only items at the right and bottom edge own any
-    const Images im0 = images_of(it.row, it.x0, N, g.H, g.W, g.Hp, g.Wp), im1 = images_of(it.row + 1, it.x0, N, g.H, g.W, g.Hp, g.Wp);
-    if (im0.any() || im1.any()) {
-#pragma unroll
-        for (int r = 0; r < 2; ++r) {
-            const Images &im = r ? im1 : im0;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) put_images(d + c * plane, im, it.row + r, it.x0, N, rgb[r][c], g.W, g.Wp, 1);
-            for (int c = 0; c < g.cc; ++c) put_images(d + (3 + c) * plane, im, it.row + r, it.x0, N, kc, g.W, g.Wp, 1);
-        }
-    }
-}
-
-template <int PIX, int LINEAR>
-BSVD_HD void yuv420_to_planar_pad_item(const uint8_t *src, float *dst, const YuvPadGeom &g, const YuvDecode &k, int64_t i)
-{
-    const PadItem it = pad_item_of(i, g.H >> 1, g.W, 2);
-    if (it.n == 4) yuv420_to_planar_pad_body<PIX, LINEAR, 4>(src, dst, g, k, it);
-    else yuv420_to_planar_pad_body<PIX, LINEAR, 2>(src, dst, g, k, it);
-}
-
-// src is the network's [frames][3][Hp][Wp]; only its picture rows and columns reach a sample.  A half item's float4 still lies inside its
-// row of src (Wp is a multiple of 4 above W); the two pad values it carries end in no stored code.
-template <int PIX, int LINEAR>
-BSVD_HD void planar_to_yuv420_crop_item(const float *src, uint8_t *dst, const YuvPadGeom &g, const YuvEncode &k, int64_t i)
-{
-    constexpr int SB = (int)sizeof(typename Pix<PIX>::S);
-    const PadItem it = pad_item_of(i, g.H >> 1, g.W, 2);
-    const int64_t plane = (int64_t)g.Hp * g.Wp;
-    const float *s = src + it.f * 3 * plane + (int64_t)it.row * g.Wp + it.x0;
-    float yv[2][4], db[5] = {}, dr[5] = {};   // db / dr: mean over the two rows of B - Y', R - Y' at columns x0 - 1 (edge-clamped) .. x0 + 3
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-        const float *row = s + (int64_t)r * g.Wp;
-        const float4 R = *reinterpret_cast<const float4 *>(row);
-        const float4 G = *reinterpret_cast<const float4 *>(row + plane);
-        const float4 B = *reinterpret_cast<const float4 *>(row + 2 * plane);
-        const float pr[4] = {R.x, R.y, R.z, R.w}, pg[4] = {G.x, G.y, G.z, G.w}, pb[4] = {B.x, B.y, B.z, B.w};
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const float cr_ = clamp01(pr[q]), cg = clamp01(pg[q]), cb_ = clamp01(pb[q]);
-            const float y = fmaf(k.kb, cb_, fmaf(k.kg, cg, k.kr * cr_));
-            yv[r][q] = fmaf(y, k.y_mul, k.y_off);
-            db[q + 1] += 0.5f * (cb_ - y);
-            dr[q + 1] += 0.5f * (cr_ - y);
-        }
-        if (LINEAR && it.x0 > 0) {                               // the column left of the item: tap 2i - 1 of its first chroma sample
-            const float cr_ = clamp01(row[-1]), cg = clamp01(row[plane - 1]), cb_ = clamp01(row[2 * plane - 1]);
-            const float y = fmaf(k.kb, cb_, fmaf(k.kg, cg, k.kr * cr_));
-            db[0] += 0.5f * (cb_ - y);
-            dr[0] += 0.5f * (cr_ - y);
-        }
-    }
-    if (LINEAR && it.x0 == 0) { db[0] = db[1]; dr[0] = dr[1]; }   // ... clamped at the frame's left edge
-    float c[4];                                                  // Cb0 Cr0 Cb1 Cr1
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-        float mb, mr;
-        if (LINEAR) {                                            // [1 2 1] / 4 over columns 2i - 1, 2i, 2i + 1: picture columns, all three
-            mb = 0.25f * (db[2 * p] + db[2 * p + 2]) + 0.5f * db[2 * p + 1];
-            mr = 0.25f * (dr[2 * p] + dr[2 * p + 2]) + 0.5f * dr[2 * p + 1];
-        } else {                                                 // mean of the 2 x 2 block
-            mb = 0.5f * (db[2 * p + 1] + db[2 * p + 2]);
-            mr = 0.5f * (dr[2 * p + 1] + dr[2 * p + 2]);
-        }
-        c[2 * p] = fmaf(mb, k.cb_mul, k.c_off);
-        c[2 * p + 1] = fmaf(mr, k.cr_mul, k.c_off);
-    }
-    uint8_t *py = dst + it.f * g.fstride + (int64_t)it.row * g.pitch + it.x0 * SB;
-    uint8_t *pc = dst + it.f * g.fstride + (int64_t)(g.H + (it.row >> 1)) * g.pitch + it.x0 * SB;
-    if (it.n == 4) {
-        store_codes<PIX, 4>(py, yv[0], k.y_lo, k.y_hi);
-        store_codes<PIX, 4>(py + g.pitch, yv[1], k.y_lo, k.y_hi);
-        store_codes<PIX, 4>(pc, c, k.c_lo, k.c_hi);
-    } else {
-        store_codes<PIX, 2>(py, yv[0], k.y_lo, k.y_hi);
-        store_codes<PIX, 2>(py + g.pitch, yv[1], k.y_lo, k.y_hi);
-        store_codes<PIX, 2>(pc, c, k.c_lo, k.c_hi);
     }
 }
 

@@ -1,11 +1,12 @@
-// frame_surface_items.h -- the item bodies of the general YUV surface entry points (include/bsvd_hip.h: bsvd_yuv_to_planar,
-// bsvd_planar_to_yuv and their _pad / _crop forms), as plain __host__ __device__ functions like those of frame_items.h: the kernels of
-// frame_yuv_surface.hip are grid-stride loops around them, and tools/debug/yuv_surface_bounds.hip runs the same bodies over exact-size heap
-// buffers under AddressSanitizer.
+// frame_surface_items.h -- the item bodies of the YUV entry points (include/bsvd_hip.h: bsvd_yuv420_to_planar, bsvd_planar_to_yuv420,
+// bsvd_yuv_to_planar, bsvd_planar_to_yuv and their _pad / _crop forms), as plain __host__ __device__ functions like those of
+// frame_items.h: the kernels of frame_yuv.hip are grid-stride loops around them, and tools/debug/yuv_surface_bounds.hip runs the same
+// bodies over exact-size heap buffers under AddressSanitizer.
 //
 // A surface format is three compile-time facts: the subsampling (4:2:0, 4:2:2, 4:4:4), the layout (three planes; Y + interleaved CbCr;
 // packed Cb Y0 Cr Y1; packed Y0 Cb Y1 Cr) and the sample rule (8 bit; 10 bit in the high bits of a 16-bit word; 10 bit in the low bits).
-// The work shape is that of frame_yuv.hip -- the fp32 side decides it: an ITEM is 4 columns of one picture row (4:2:2, 4:4:4) or of a row
+// Both kernels are bandwidth-bound and the fp32 side carries 8 to 16 times the bytes of the YUV side, so the fp32 side decides the layout
+// of work over lanes: an ITEM is 4 columns of one picture row (4:2:2, 4:4:4) or of a row
 // pair with the one chroma row under it (4:2:0), consecutive lanes take consecutive items of a row, a lane moves one float4 per plane row.
 // On the surface side the item's samples are one group per plane and row -- 4 Y, 2 (or 4) Cb, 2 (or 4) Cr, or the 8 bytes of two packed
 // pixel pairs -- each read or written once, as a whole, by this lane alone.  A row that W % 4 leaves short ends in a part item of 2 columns
@@ -32,7 +33,8 @@ template <int SUB_, int LAY_, int SMP_> struct SurfFmt {
 // planes: 0 = Y (or the packed plane), 1 = Cb or CbCr, 2 = Cr.  off / pitch in bytes, resolved by the host (no zeros left).
 struct SurfGeom { int H, W, Hp, Wp, cc; float const_val; int64_t fstride, off[3], pitch[3]; };
 
-// N consecutive samples of a row; as load_codes / store_codes (frame_items.h), with the sample rule of the format
+// N consecutive samples of a row, with the sample rule of the format.  A surface promises no more than its sample's own alignment (pitch
+// and base are the caller's), hence the memcpy: one load / store of the group's width, legal at any sample-aligned address.
 template <int SMP, int N>
 BSVD_HD void load_smp(const uint8_t *p, float *out)
 {
@@ -126,7 +128,7 @@ BSVD_HD void store_packed(uint8_t *fr, const SurfGeom &g, const YuvEncode &k, in
 // ---------------------------------------------------------------------------------------------
 // decode.  N picture columns from (it.row, x0): 4 = a whole item, 2 / 1 = the groups of a part item (1 with 4:4:4 only).  Chroma filters
 // clamp at the PICTURE's edges; the mirror images of the pad region are copies of the converted values (frame_items.h, put_images).
-// 4:2:0: the arithmetic of yuv420_to_planar_pad_body, operation for operation.  4:2:2: its horizontal half.  4:4:4: none.
+// 4:2:0: vertical filter, then horizontal.  4:2:2: the horizontal half.  4:4:4: none.
 template <class F, int LINEAR, int N>
 BSVD_HD void yuv_to_planar_body(const uint8_t *src, float *dst, const SurfGeom &g, const YuvDecode &k, int64_t f, int row, int x0)
 {
@@ -230,8 +232,8 @@ BSVD_HD void yuv_to_planar_item(const uint8_t *src, float *dst, const SurfGeom &
 
 // ---------------------------------------------------------------------------------------------
 // encode.  src is the network's [frames][3][Hp][Wp]; only its picture rows and columns reach a sample.  A part item's float4 still lies
-// inside its row of src (Wp is a multiple of 4 at or above W); the pad values it carries end in no stored code.  4:2:0: the arithmetic of
-// planar_to_yuv420_crop_item.  4:2:2: the same without the mean over two rows.  4:4:4: Cb and Cr of every pixel.
+// inside its row of src (Wp is a multiple of 4 at or above W); the pad values it carries end in no stored code.  4:2:0: chroma from the
+// mean over the item's two rows.  4:2:2: the same without that mean.  4:4:4: Cb and Cr of every pixel.
 template <class F, int LINEAR>
 BSVD_HD void planar_to_yuv_item(const float *src, uint8_t *dst, const SurfGeom &g, const YuvEncode &k, int64_t i)
 {

@@ -333,15 +333,16 @@ def yuv420_picture_bytes(H, W, pix_fmt, row_pitch=None):
     return _yuv_desc(H, W, pix_fmt, "bt709", False, "linear", row_pitch, picture=True)[1]
 
 
-def _yuv_buffer(buf, T, nbytes, pix_fmt, what):
-    """a surface buffer [T, >= frame_bytes] -> its frame stride in bytes"""
+def _surface_buffer(buf, T, nbytes, sixteen, what, callers="10-bit", frames="10-bit"):
+    """a surface buffer [T, >= frame_bytes] -> its frame stride in bytes.  sixteen: 16-bit samples; callers / frames: how the two
+    messages about them name the format ("P010" / "p010" for the 4:2:0 functions)"""
     if buf.dtype != torch.uint8 or not buf.is_cuda or buf.dim() != 2 or not buf.is_contiguous():
-        raise ValueError("%s: expected a contiguous uint8 device tensor [T, frame_bytes] (P010 callers view their uint16 as bytes)" % what)
+        raise ValueError("%s: expected a contiguous uint8 device tensor [T, frame_bytes] (%s callers view their uint16 as bytes)" % (what, callers))
     if (T is not None and buf.shape[0] != T) or buf.shape[0] < 1 or buf.shape[1] < nbytes:
         raise ValueError("%s: shape %s, expected [%s, %d] (or longer rows: frames row-length bytes apart)"
                          % (what, tuple(buf.shape), "T" if T is None else T, nbytes))
-    if pix_fmt == "p010" and buf.shape[1] % 2:
-        raise ValueError("%s: p010 frames must be an even number of bytes apart, got %d" % (what, buf.shape[1]))
+    if sixteen and buf.shape[1] % 2:
+        raise ValueError("%s: %s frames must be an even number of bytes apart, got %d" % (what, frames, buf.shape[1]))
     return buf.shape[1]
 
 
@@ -361,7 +362,7 @@ def yuv420_to_input(buf, H, W, pix_fmt="nv12", matrix="bt709", full_range=False,
         return _with_sigma(yuv420_to_input(buf, H, W, pix_fmt, matrix, full_range, chroma, 0.0, row_pitch, pad_to), mode, (int(H), int(W)), gain)
     desc, nbytes = _yuv_desc(H, W, pix_fmt, matrix, full_range, chroma, row_pitch, picture=pad_to is not None)
     lib = require_hip()
-    desc.frame_stride = _yuv_buffer(buf, None, nbytes, pix_fmt, "yuv420_to_input")
+    desc.frame_stride = _surface_buffer(buf, None, nbytes, pix_fmt == "p010", "yuv420_to_input", "P010", "p010")
     T = buf.shape[0]
     extra = 0 if sigma is None else 1
     if pad_to is not None:
@@ -397,7 +398,7 @@ def output_to_yuv420(y, pix_fmt="nv12", matrix="bt709", full_range=False, chroma
         out = (torch.zeros if row_pitch else torch.empty)((T, nbytes), dtype=torch.uint8, device=y.device)
     elif out.device != y.device:
         raise ValueError("output_to_yuv420: out is on %s, y on %s" % (out.device, y.device))
-    desc.frame_stride = _yuv_buffer(out, T, nbytes, pix_fmt, "output_to_yuv420(out=)")
+    desc.frame_stride = _surface_buffer(out, T, nbytes, pix_fmt == "p010", "output_to_yuv420(out=)", "P010", "p010")
     with torch.cuda.device(y.device):
         if crop_to is not None:
             _lib.check(lib.bsvd_planar_to_yuv420_crop(y.data_ptr(), out.data_ptr(), T, Hp, Wp, H, W, ctypes.byref(desc), _stream()),
@@ -459,18 +460,6 @@ def yuv_frame_bytes(H, W, pix_fmt, pitches=None, offsets=None):
     row of each plane, None / 0 = tight; ``offsets``: byte offset of each plane from the frame start, None / 0 for planes 1 and 2 =
     directly behind the plane before.  Any picture size the format can carry (``pad_to`` / ``crop_to``)."""
     return _yuv_surface(H, W, pix_fmt, "bt709", False, "linear", pitches, offsets, picture=True)[1]
-
-
-def _surface_buffer(buf, T, nbytes, sixteen, what):
-    """a surface buffer [T, >= frame_bytes] -> its frame stride in bytes"""
-    if buf.dtype != torch.uint8 or not buf.is_cuda or buf.dim() != 2 or not buf.is_contiguous():
-        raise ValueError("%s: expected a contiguous uint8 device tensor [T, frame_bytes] (10-bit callers view their uint16 as bytes)" % what)
-    if (T is not None and buf.shape[0] != T) or buf.shape[0] < 1 or buf.shape[1] < nbytes:
-        raise ValueError("%s: shape %s, expected [%s, %d] (or longer rows: frames row-length bytes apart)"
-                         % (what, tuple(buf.shape), "T" if T is None else T, nbytes))
-    if sixteen and buf.shape[1] % 2:
-        raise ValueError("%s: 10-bit frames must be an even number of bytes apart, got %d" % (what, buf.shape[1]))
-    return buf.shape[1]
 
 
 def yuv_to_input(buf, H, W, pix_fmt="yuv420p", matrix="bt709", full_range=False, chroma="linear", sigma=None, pitches=None, pad_to=None,

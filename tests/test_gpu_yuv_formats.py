@@ -1,4 +1,4 @@
-"""The planar, 4:2:2 and 4:4:4 YUV surfaces on the device (bsvd_amd/csrc/frame_yuv_surface.hip through frame_io.yuv_to_input /
+"""The planar, 4:2:2 and 4:4:4 YUV surfaces on the device (bsvd_amd/csrc/frame_yuv.hip through frame_io.yuv_to_input /
 output_to_yuv and the pipelines' pix_fmt): bit for bit against the NV12 / P010 kernels where the formats say the same thing, against the
 independent numpy model tests/yuv_surface_model.py elsewhere, and the memory contract.  T = 2.  Pictures: 4x4 is one item with both edge
 clamps in one chroma sample, 8x12 an odd item count per row, 12x20 and 36x52 several rows of items with every neighbour case; the pad /
@@ -21,6 +21,7 @@ pytestmark = pytest.mark.gpu
 T = 2
 SIZES = [(4, 4), (8, 12), (12, 20), (36, 52)]
 PAD_PICTURE = {420: (6, 10), 422: (5, 10), 444: (5, 7)}
+PAD_420 = [((6, 10), (8, 12)), ((10, 14), (16, 24))]      # picture, tensor: 4:2:0 against NV12 / P010 through pad and crop
 NAMES = sorted(S.FORMATS)
 COLOUR = list(itertools.product(["bt601", "bt709", "bt2020"], [False, True], ["nearest", "linear"]))
 GUARD = 66          # bytes in front of a surface inside its allocation: surfaces promise no more than their sample's alignment
@@ -112,7 +113,9 @@ def _encode420(x, pix_fmt, **kw):
 @pytest.mark.parametrize("pix_fmt,semi", [("yuv420p", "nv12"), ("yuv420p10le", "p010")])
 def test_planar_420_is_the_semi_planar_kernel_bit_for_bit(pix_fmt, semi):
     """yuv420p decodes to exactly the tensor bsvd_yuv420_to_planar gives for the same samples as NV12, and encodes to exactly its codes, for
-    every matrix x range x chroma; likewise yuv420p10le and P010.  The ignored bits of the two 10-bit rules hold different junk."""
+    every matrix x range x chroma; likewise yuv420p10le and P010.  The ignored bits of the two 10-bit rules hold different junk.  The same
+    through the pad and crop entry points, at pictures that end their rows in a half item and pad both ways, by less and by more than one
+    item: one kernel serves both formats, so this holds its semi-planar loads and stores against its planar ones."""
     bits = S.FORMATS[pix_fmt].bits
     rs = np.random.RandomState(5)
     for (H, W), (matrix, full_range, chroma) in itertools.product(SIZES, COLOUR):
@@ -127,6 +130,18 @@ def test_planar_420_is_the_semi_planar_kernel_bit_for_bit(pix_fmt, semi):
             surf, _ = _encode(x, S.frame_bytes(H, W, pix_fmt), pix_fmt=pix_fmt, **kw)
             y2, cb2, cr2, ignored = S.unpack(surf, H, W, pix_fmt)
             assert np.array_equal(y1, y2) and np.array_equal(cb1, cb2) and np.array_equal(cr1, cr2) and ignored == 0, (H, W, kw, kind)
+    for ((H, W), pad), (matrix, full_range, chroma) in itertools.product(PAD_420, COLOUR):
+        kw = dict(matrix=matrix, full_range=full_range, chroma=chroma)
+        Y, Cb, Cr = _codes(bits, 420, H, W)
+        want = _decode420(M.pack(Y, Cb, Cr, semi, low_bits=rs.randint(0, 64, (T, H * 3 // 2, W))), H, W, pix_fmt=semi, sigma=SIGMA, pad_to=pad, **kw)
+        got = _decode(S.pack(Y, Cb, Cr, pix_fmt, junk=rs), H, W, pix_fmt=pix_fmt, sigma=SIGMA, pad_to=pad, **kw)
+        assert got.shape == (T, 4) + pad and np.array_equal(_bits(got), _bits(want)), (H, W, pad, kw)
+        for kind in ("uniform", "limits"):
+            x = _rgb(pad[0], pad[1], kind)
+            y1, cb1, cr1, _ = M.unpack(_encode420(x, semi, crop_to=(H, W), **kw), H, W, semi)
+            surf, _ = _encode(x, S.frame_bytes(H, W, pix_fmt), pix_fmt=pix_fmt, crop_to=(H, W), **kw)
+            y2, cb2, cr2, ignored = S.unpack(surf, H, W, pix_fmt)
+            assert np.array_equal(y1, y2) and np.array_equal(cb1, cb2) and np.array_equal(cr1, cr2) and ignored == 0, (H, W, pad, kw, kind)
 
 
 @pytest.mark.parametrize("bits", [8, 10])

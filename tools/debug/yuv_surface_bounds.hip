@@ -1,10 +1,11 @@
-// yuv_surface_bounds.hip -- runs the item bodies of the general YUV surface kernels (bsvd_amd/csrc/frame_surface_items.h) on the HOST, over
-// heap buffers of exactly the bytes the ABI promises, under AddressSanitizer, in the manner of frame_pad_bounds.hip: every byte of a
+// yuv_surface_bounds.hip -- runs the item bodies of the YUV kernels (bsvd_amd/csrc/frame_surface_items.h), all twelve formats, on the HOST,
+// over heap buffers of exactly the bytes the ABI promises, under AddressSanitizer, in the manner of frame_pad_bounds.hip: every byte of a
 // surface that is not a sample -- pitch padding, the bytes between planes and frames, the bytes behind the last sample of the plane that
-// ends last -- is outside the allocation or poisoned, so a read or write there stops the program.  It also checks what needs no model:
-// every destination element written, pad elements bit-equal to their mirror source, non-sample bytes untouched, NaN in the pad region of
-// the fp32 tensor reaching no sample, the ignored bits of 10-bit words reaching no value, and yuv420p / yuv420p10le against the NV12 /
-// P010 bodies of frame_items.h on the same samples, bit for bit.  Host code only: no kernel is launched and no device is needed.
+// ends last -- is outside the allocation or poisoned, so a read or write there stops the program.  nv12 and p010 run with the geometry
+// bsvd_yuv420_* gives them (one pitch, CbCr directly behind Y), the ten others with a pitch, an offset and a gap per plane.  It also checks
+// what needs no model: every destination element written, pad elements bit-equal to their mirror source, non-sample bytes untouched, NaN
+// in the pad region of the fp32 tensor reaching no sample, the ignored bits of 10-bit words reaching no value, and yuv420p / yuv420p10le
+// against nv12 / p010 on the same samples, bit for bit.  Host code only: no kernel is launched and no device is needed.
 //
 //   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -Xarch_host -fsanitize=address -Iinclude -Ibsvd_amd/csrc \
 //         tools/debug/yuv_surface_bounds.hip -o build/yuv_surface_bounds && build/yuv_surface_bounds
@@ -64,6 +65,20 @@ static SurfGeom geom_of(int H, int W, int Hp, int Wp, int cc, int pitched)
     return g;
 }
 
+// NV12 / P010 as bsvd_yuv420_* describe them: one pitch for both planes, the CbCr plane directly behind the H rows of Y; pitched: rows padded
+// to the next multiple of 64 bytes and 64 more, frames 128 bytes of slack apart
+template <class F>
+static SurfGeom geom_nv12(int H, int W, int Hp, int Wp, int cc, int pitched)
+{
+    const int64_t pitch = pitched ? ((int64_t)W * F::SB + 63) / 64 * 64 + 64 : (int64_t)W * F::SB;
+    SurfGeom g = {};
+    g.H = H; g.W = W; g.Hp = Hp; g.Wp = Wp; g.cc = cc; g.const_val = 0.125f;
+    g.pitch[0] = g.pitch[1] = pitch;
+    g.off[1] = H * pitch;
+    g.fstride = pitch * H * 3 / 2 + (pitched ? 128 : 0);
+    return g;
+}
+
 // a surface of exactly its bytes: it ends at the last sample of the plane that ends last; with `poison` every byte that is no sample is poisoned
 struct Surface { uint8_t *p; int64_t bytes; std::vector<uint8_t> is_sample; };
 template <class F>
@@ -89,15 +104,18 @@ static Surface surface(int T, int H, int W, const SurfGeom &g, bool poison)
 }
 static void release(Surface &s) { __asan_unpoison_memory_region(s.p, s.bytes); free(s.p); }
 
+using FNV12 = SurfFmt<BSVD_SUB_420, BSVD_LAYOUT_SEMIPLANAR, SMP_U8>;
+using FP010 = SurfFmt<BSVD_SUB_420, BSVD_LAYOUT_SEMIPLANAR, SMP_HIGH10>;
+
 static const YuvDecode kDec8 = {16.f, 1.f / 219, 128.f, 1.f / 224, 1.5748f, 0.4681f, 0.1873f, 1.8556f};
 static const YuvDecode kDec10 = {64.f, 1.f / 876, 512.f, 1.f / 896, 1.5748f, 0.4681f, 0.1873f, 1.8556f};
 static const YuvEncode kEnc8 = {0.2126f, 0.7152f, 0.0722f, 219.f, 16.f, 120.7f, 142.2f, 128.f, 16.f, 235.f, 16.f, 240.f};
 static const YuvEncode kEnc10 = {0.2126f, 0.7152f, 0.0722f, 876.f, 64.f, 482.9f, 568.9f, 512.f, 64.f, 940.f, 64.f, 960.f};
 
 template <class F, int LINEAR>
-static void surf_case(const char *name, int T, int H, int W, int Hp, int Wp, int pitched)
+static void surf_case(const char *name, int T, const SurfGeom &g)
 {
-    const SurfGeom g = geom_of<F>(H, W, Hp, Wp, 1, pitched);
+    const int H = g.H, W = g.W, Hp = g.Hp, Wp = g.Wp;
     const int64_t plane = (int64_t)Hp * Wp, items = (int64_t)T * surf_item_rows<F>(H) * items_per_row(W);
     const YuvDecode kd = F::SB == 2 ? kDec10 : kDec8;
     const YuvEncode ke = F::SB == 2 ? kEnc10 : kEnc8;
@@ -149,14 +167,14 @@ static void surf_case(const char *name, int T, int H, int W, int Hp, int Wp, int
     release(o1); release(o2); free(y); free(dst); free(dst2);
 }
 
-// yuv420p / yuv420p10le against the NV12 / P010 item bodies on the same samples: the same floats in, the same codes out
-template <class F, int PIX, int LINEAR>
-static void against_yuv420(const char *name, int T, int H, int W, int Hp, int Wp)
+// yuv420p / yuv420p10le against nv12 / p010 (FS) on the same samples: the same floats in, the same codes out -- the planar loads and stores
+// against the semi-planar ones
+template <class F, class FS, int LINEAR>
+static void against_semi_planar(const char *name, int T, int H, int W, int Hp, int Wp)
 {
     using S = typename F::S;
-    const SurfGeom g = geom_of<F>(H, W, Hp, Wp, 0, 0);
-    const int64_t pitch = (int64_t)W * F::SB, fstride = pitch * H * 3 / 2, plane = (int64_t)Hp * Wp;
-    const YuvPadGeom g420 = {H, W, Hp, Wp, 0, pitch, fstride, 0.f};
+    const SurfGeom g = geom_of<F>(H, W, Hp, Wp, 0, 0), gs = geom_nv12<FS>(H, W, Hp, Wp, 0, 0);
+    const int64_t fstride = gs.fstride, plane = (int64_t)Hp * Wp;
     const int64_t items = (int64_t)T * (H / 2) * items_per_row(W), n = (int64_t)T * fstride / F::SB;
     const YuvDecode kd = F::SB == 2 ? kDec10 : kDec8;
     const YuvEncode ke = F::SB == 2 ? kEnc10 : kEnc8;
@@ -175,15 +193,15 @@ static void against_yuv420(const char *name, int T, int H, int W, int Hp, int Wp
     float *a = alloc_planes((int64_t)T * 3 * plane, true), *b = alloc_planes((int64_t)T * 3 * plane, true);
     for (int64_t i = 0; i < items; ++i) {
         yuv_to_planar_item<F, LINEAR>((const uint8_t *)planar.data(), a, g, kd, i);
-        yuv420_to_planar_pad_item<PIX, LINEAR>((const uint8_t *)semi.data(), b, g420, kd, i);
+        yuv_to_planar_item<FS, LINEAR>((const uint8_t *)semi.data(), b, gs, kd, i);
     }
-    EXPECT(memcmp(a, b, (size_t)T * 3 * plane * 4) == 0, "%s lin%d %dx%d->%dx%d: decode differs from the 4:2:0 body", name, LINEAR, H, W, Hp, Wp);
+    EXPECT(memcmp(a, b, (size_t)T * 3 * plane * 4) == 0, "%s lin%d %dx%d->%dx%d: decode differs from the semi-planar format's", name, LINEAR, H, W, Hp, Wp);
     float *y = alloc_planes((int64_t)T * 3 * plane, false);
     for (int64_t i = 0; i < (int64_t)T * 3 * plane; ++i) y[i] = (float)((int)(rnd() % 1400) - 200) / 1000.f;      // out of gamut on both sides
     std::vector<S> op(n), os(n);
     for (int64_t i = 0; i < items; ++i) {
         planar_to_yuv_item<F, LINEAR>(y, (uint8_t *)op.data(), g, ke, i);
-        planar_to_yuv420_crop_item<PIX, LINEAR>(y, (uint8_t *)os.data(), g420, ke, i);
+        planar_to_yuv_item<FS, LINEAR>(y, (uint8_t *)os.data(), gs, ke, i);
     }
     int64_t bad = 0;
     for (int f = 0; f < T; ++f) {
@@ -196,17 +214,18 @@ static void against_yuv420(const char *name, int T, int H, int W, int Hp, int Wp
                     bad += (F::SB == 2 ? v << 6 : v) != q[(int64_t)H * W + r * W + 2 * x + c];
                 }
     }
-    EXPECT(bad == 0, "%s lin%d %dx%d<-%dx%d: %lld codes differ from the 4:2:0 body", name, LINEAR, H, W, Hp, Wp, (long long)bad);
+    EXPECT(bad == 0, "%s lin%d %dx%d<-%dx%d: %lld codes differ from the semi-planar format's", name, LINEAR, H, W, Hp, Wp, (long long)bad);
     free(a); free(b); free(y);
 }
 
-template <class F>
+template <class F, bool NV12 = false>
 static void both(const char *name, const int (*sizes)[4], int n)
 {
     for (int i = 0; i < n; ++i)
         for (int pitched = 0; pitched < 2; ++pitched) {
-            surf_case<F, 0>(name, 2, sizes[i][0], sizes[i][1], sizes[i][2], sizes[i][3], pitched);
-            if (F::SUB != BSVD_SUB_444) surf_case<F, 1>(name, 2, sizes[i][0], sizes[i][1], sizes[i][2], sizes[i][3], pitched);
+            const SurfGeom g = (NV12 ? geom_nv12<F> : geom_of<F>)(sizes[i][0], sizes[i][1], sizes[i][2], sizes[i][3], 1, pitched);
+            surf_case<F, 0>(name, 2, g);
+            if (F::SUB != BSVD_SUB_444) surf_case<F, 1>(name, 2, g);
         }
 }
 
@@ -226,11 +245,17 @@ int main()
     both<SurfFmt<BSVD_SUB_422, BSVD_LAYOUT_PLANAR, SMP_LOW10>>("yuv422p10le", s422, 9);
     both<SurfFmt<BSVD_SUB_444, BSVD_LAYOUT_PLANAR, SMP_U8>>("yuv444p", s444, 11);
     both<SurfFmt<BSVD_SUB_444, BSVD_LAYOUT_PLANAR, SMP_LOW10>>("yuv444p10le", s444, 11);
+    // nv12 / p010 with the geometry of bsvd_yuv420_*: the sizes above and those the pad / crop bodies were first written against
+    const int snv[][4] = {{8, 12, 12, 16}, {34, 52, 36, 52}, {10, 14, 16, 24}};
+    both<FNV12, true>("nv12", s420, 9);
+    both<FNV12, true>("nv12", snv, 3);
+    both<FP010, true>("p010", s420, 9);
+    both<FP010, true>("p010", snv, 3);
     for (const auto &s : s420) {
-        against_yuv420<SurfFmt<BSVD_SUB_420, BSVD_LAYOUT_PLANAR, SMP_U8>, BSVD_PIX_NV12, 0>("yuv420p", 2, s[0], s[1], s[2], s[3]);
-        against_yuv420<SurfFmt<BSVD_SUB_420, BSVD_LAYOUT_PLANAR, SMP_U8>, BSVD_PIX_NV12, 1>("yuv420p", 2, s[0], s[1], s[2], s[3]);
-        against_yuv420<SurfFmt<BSVD_SUB_420, BSVD_LAYOUT_PLANAR, SMP_LOW10>, BSVD_PIX_P010, 0>("yuv420p10le", 2, s[0], s[1], s[2], s[3]);
-        against_yuv420<SurfFmt<BSVD_SUB_420, BSVD_LAYOUT_PLANAR, SMP_LOW10>, BSVD_PIX_P010, 1>("yuv420p10le", 2, s[0], s[1], s[2], s[3]);
+        against_semi_planar<SurfFmt<BSVD_SUB_420, BSVD_LAYOUT_PLANAR, SMP_U8>, FNV12, 0>("yuv420p", 2, s[0], s[1], s[2], s[3]);
+        against_semi_planar<SurfFmt<BSVD_SUB_420, BSVD_LAYOUT_PLANAR, SMP_U8>, FNV12, 1>("yuv420p", 2, s[0], s[1], s[2], s[3]);
+        against_semi_planar<SurfFmt<BSVD_SUB_420, BSVD_LAYOUT_PLANAR, SMP_LOW10>, FP010, 0>("yuv420p10le", 2, s[0], s[1], s[2], s[3]);
+        against_semi_planar<SurfFmt<BSVD_SUB_420, BSVD_LAYOUT_PLANAR, SMP_LOW10>, FP010, 1>("yuv420p10le", 2, s[0], s[1], s[2], s[3]);
     }
     printf("yuv_surface_bounds: %d failure(s)\n", failures);
     return failures ? 1 : 0;
