@@ -26,7 +26,8 @@ EXPORTS = ("bsvd_abi_version", "bsvd_conv_args_size", "bsvd_build_info", "bsvd_l
            "bsvd_planar_to_yuv420_crop",
            "bsvd_yuv_frame_bytes", "bsvd_yuv_to_planar", "bsvd_planar_to_yuv", "bsvd_yuv_to_planar_pad", "bsvd_planar_to_yuv_crop",
            "bsvd_sigma_workspace_bytes", "bsvd_estimate_sigma", "bsvd_fill_sigma_plane",
-           "bsvd_scene_grid", "bsvd_scene_diff")
+           "bsvd_scene_grid", "bsvd_scene_diff",
+           "bsvd_rgb_frame_bytes", "bsvd_rgb_to_planar", "bsvd_planar_to_rgb")
 PIX_FMT = {"nv12": 0, "p010": 1}
 MATRIX = {"bt601": 0, "bt709": 1, "bt2020": 2}
 CHROMA = {"nearest": 0, "linear": 1}
@@ -45,6 +46,31 @@ YUV_FORMATS = {
     "yuv422p": (SUB_422, LAYOUT_PLANAR, 8, 0), "yuv422p10le": (SUB_422, LAYOUT_PLANAR, 10, 0),
     "yuv444p": (SUB_444, LAYOUT_PLANAR, 8, 0), "yuv444p10le": (SUB_444, LAYOUT_PLANAR, 10, 0),
 }
+RGB_PACKED, RGB_PACKED_X2_10, RGB_PLANAR = 0, 1, 2
+FOURTH_NONE, FOURTH_ALPHA, FOURTH_FILLER = 0, 1, 2
+
+
+def _rgb_formats():
+    """the surfaces of bsvd_rgb_to_planar / bsvd_planar_to_rgb, by ffmpeg's names: (layout, components, bits, pos of R G B fourth, fourth)"""
+    t = {}
+    for name in ("rgb24", "bgr24", "rgba", "bgra", "argb", "abgr", "rgb0", "bgr0", "0rgb", "0bgr"):
+        order = name[:-2] if name.endswith("24") else name
+        fourth = FOURTH_ALPHA if "a" in order else FOURTH_FILLER if "0" in order else FOURTH_NONE
+        pos = tuple(order.index(c) for c in "rgb") + ((order.index("a" if fourth == FOURTH_ALPHA else "0"),) if fourth else (0,))
+        t[name] = (RGB_PACKED, len(order), 8, pos, fourth)
+    t["rgb48le"] = (RGB_PACKED, 3, 16, (0, 1, 2, 0), FOURTH_NONE)
+    t["bgr48le"] = (RGB_PACKED, 3, 16, (2, 1, 0, 0), FOURTH_NONE)
+    t["rgba64le"] = (RGB_PACKED, 4, 16, (0, 1, 2, 3), FOURTH_ALPHA)
+    t["bgra64le"] = (RGB_PACKED, 4, 16, (2, 1, 0, 3), FOURTH_ALPHA)
+    t["x2rgb10le"] = (RGB_PACKED_X2_10, 3, 10, (2, 1, 0, 0), FOURTH_NONE)      # (msb) 2 X | R | G | B (lsb): B is field 0
+    t["x2bgr10le"] = (RGB_PACKED_X2_10, 3, 10, (0, 1, 2, 0), FOURTH_NONE)
+    for bits, suffix in ((8, ""), (10, "10le"), (12, "12le"), (16, "16le")):       # plane order G, B, R, (A)
+        t["gbrp" + suffix] = (RGB_PLANAR, 3, bits, (2, 0, 1, 0), FOURTH_NONE)
+        t["gbrap" + suffix] = (RGB_PLANAR, 4, bits, (2, 0, 1, 3), FOURTH_ALPHA)
+    return t
+
+
+RGB_FORMATS = _rgb_formats()
 
 
 class BsvdConvArgs(ctypes.Structure):
@@ -100,6 +126,13 @@ class BsvdYuvSurface(ctypes.Structure):
                 ("matrix", ctypes.c_int32), ("full_range", ctypes.c_int32), ("chroma", ctypes.c_int32), ("reserved0", ctypes.c_int32),
                 ("pitch", ctypes.c_int32 * 3), ("reserved1", ctypes.c_int32), ("offset", ctypes.c_int64 * 3),
                 ("frame_stride", ctypes.c_int64), ("reserved2", ctypes.c_int64)]
+
+
+class BsvdRgbSurface(ctypes.Structure):
+    """Mirror of ``struct BsvdRgbSurface`` (include/bsvd_hip.h)."""
+    _fields_ = [("layout", ctypes.c_int32), ("components", ctypes.c_int32), ("bits", ctypes.c_int32), ("pos", ctypes.c_int32 * 4),
+                ("fourth", ctypes.c_int32), ("full_range", ctypes.c_int32), ("pitch", ctypes.c_int32 * 4), ("reserved0", ctypes.c_int32),
+                ("offset", ctypes.c_int64 * 4), ("frame_stride", ctypes.c_int64), ("reserved", ctypes.c_int64)]
 
 
 class BsvdLibraryError(RuntimeError):
@@ -209,6 +242,13 @@ def load():
     lib.bsvd_scene_grid.argtypes = [vp, i32, i32, i32, i32, i32, i64, vp, vp]
     lib.bsvd_scene_diff.restype = ctypes.c_int
     lib.bsvd_scene_diff.argtypes = [vp, vp, i32, i32, vp, vp]
+    rgb = ctypes.POINTER(BsvdRgbSurface)
+    lib.bsvd_rgb_frame_bytes.restype = i64
+    lib.bsvd_rgb_frame_bytes.argtypes = [i32, i32, rgb]
+    lib.bsvd_rgb_to_planar.restype = ctypes.c_int
+    lib.bsvd_rgb_to_planar.argtypes = [vp, vp, i32, i32, i32, i32, i32, rgb, vp, i32, f32, vp]
+    lib.bsvd_planar_to_rgb.restype = ctypes.c_int
+    lib.bsvd_planar_to_rgb.argtypes = [vp, vp, i32, i32, i32, i32, i32, rgb, vp, vp]
     lib.bsvd_workspace_bytes.restype = i64
     lib.bsvd_workspace_bytes.argtypes = [ctypes.POINTER(BsvdConvArgs)]
     if lib.bsvd_abi_version() != ABI_VERSION:

@@ -9,6 +9,11 @@ pixel over PCIe instead of RGB24's 3, and no colour conversion on the host).  An
 planar 4:2:0, 4:2:2 (packed, semi-planar, planar) and planar 4:4:4, 8 and 10 bit, by ffmpeg's names (``_lib.YUV_FORMATS``):
 ``yuv_to_input`` / ``output_to_yuv`` (bsvd_yuv_to_planar / bsvd_planar_to_yuv), with a pitch and an offset per plane.
 
+RGB as callers hold it who do not come through a video decoder (``_lib.RGB_FORMATS``, ffmpeg's names): packed 8 and 16 bit in any component
+order with alpha or a filler, x2rgb10le / x2bgr10le, planar gbrp / gbrap at 8 to 16 bits -- ``rgb_to_input`` / ``output_to_rgb``
+(bsvd_rgb_to_planar / bsvd_planar_to_rgb).  Alpha never meets the arithmetic: it comes out of ``rgb_to_input(return_alpha=True)`` as a
+plane of codes and goes back in through ``output_to_rgb(alpha=)``.
+
 Any picture size: the network needs H and W to be multiples of 4, and the reference's callers reflect-pad the fp32 tensor on the right and
 bottom and crop the result (``denoise.pad_to_multiple_of_4`` / ``crop_padding`` here).  ``pad_to=(Hp, Wp)`` on the way in and
 ``crop_to=(H, W)`` on the way out do both inside the conversion kernels (bsvd_*_pad / bsvd_*_crop): the frames stay picture-sized uint8 /
@@ -520,4 +525,138 @@ def output_to_yuv(y, pix_fmt="yuv420p", matrix="bt709", full_range=False, chroma
         else:
             _lib.check(lib.bsvd_planar_to_yuv(y.data_ptr(), out.data_ptr(), T, H, W, ctypes.byref(surf), _stream()),
                        "bsvd_planar_to_yuv")
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------
+# RGB surfaces (include/bsvd_hip.h, BsvdRgbSurface): the names of _lib.RGB_FORMATS, ffmpeg's
+
+def _quad(v, what, planes):
+    """pitches / offsets: None, or up to ``planes`` non-negative ints (None or 0 = tight / directly behind the plane before)"""
+    if v is None:
+        return (0, 0, 0, 0)
+    try:
+        v = [int(x or 0) for x in v]
+    except TypeError:
+        raise ValueError("%s: expected a sequence of up to %d ints, got %r" % (what, planes, v)) from None
+    if len(v) > planes or any(x < 0 for x in v):
+        raise ValueError("%s %r: the layout has %d plane(s); values must not be negative" % (what, v, planes))
+    return tuple(v) + (0,) * (4 - len(v))
+
+
+def rgb_planes(pix_fmt):
+    """planes of an RGB surface format: 1 (packed) or 3 / 4 (gbrp* / gbrap*)"""
+    if pix_fmt not in _lib.RGB_FORMATS:
+        raise ValueError("pix_fmt %r: one of %s" % (pix_fmt, ", ".join(sorted(_lib.RGB_FORMATS))))
+    layout, components = _lib.RGB_FORMATS[pix_fmt][:2]
+    return components if layout == _lib.RGB_PLANAR else 1
+
+
+def rgb_has_alpha(pix_fmt):
+    rgb_planes(pix_fmt)
+    return _lib.RGB_FORMATS[pix_fmt][4] == _lib.FOURTH_ALPHA
+
+
+def rgb_sample_dtype(pix_fmt):
+    """torch dtype of a sample's container (and of the alpha side plane): uint8, or uint16 for the formats above 8 bits"""
+    rgb_planes(pix_fmt)
+    return torch.uint8 if _lib.RGB_FORMATS[pix_fmt][2] == 8 else torch.uint16
+
+
+def _rgb_surface(H, W, pix_fmt, full_range, pitches, offsets, picture):
+    """-> (BsvdRgbSurface, frame_bytes); ValueError for a name or a size the library would refuse.  picture: a surface for pad_to / crop_to,
+    whose H and W need not be multiples of 4"""
+    planes = rgb_planes(pix_fmt)
+    layout, components, bits, pos, fourth = _lib.RGB_FORMATS[pix_fmt]
+    surf = _lib.BsvdRgbSurface(layout=layout, components=components, bits=bits, fourth=fourth, full_range=1 if full_range else 0)
+    surf.pos[:] = pos
+    surf.pitch[:] = _quad(pitches, "pitches", planes)
+    surf.offset[:] = _quad(offsets, "offsets", planes)
+    H, W = int(H), int(W)
+    if not picture and (H <= 0 or W <= 0 or H % 4 or W % 4):
+        raise ValueError("%s frame %d x %d: H and W must be positive multiples of 4 (or use pad_to / crop_to)" % (pix_fmt, H, W))
+    lib = _lib.load()
+    nbytes = lib.bsvd_rgb_frame_bytes(H, W, ctypes.byref(surf))
+    if nbytes < 0:
+        raise ValueError("%s frame %d x %d with pitches %s, offsets %s: %s" % (pix_fmt, H, W, pitches, offsets, lib.bsvd_last_error().decode()
+                                                                               if H > 0 and W > 0 else "H and W must be positive"))
+    return surf, nbytes
+
+
+def rgb_frame_bytes(H, W, pix_fmt, pitches=None, offsets=None):
+    """Bytes of one frame of an RGB surface (``_lib.RGB_FORMATS``): the end of its last plane.  ``pitches``: bytes per row of each plane,
+    None / 0 = tight; ``offsets``: byte offset of each plane from the frame start, None / 0 for a later plane = directly behind the plane
+    before.  Any picture size."""
+    return _rgb_surface(H, W, pix_fmt, True, pitches, offsets, picture=True)[1]
+
+
+def _alpha_plane(alpha, T, H, W, pix_fmt, device, what):
+    if (not isinstance(alpha, torch.Tensor) or alpha.dtype != rgb_sample_dtype(pix_fmt) or tuple(alpha.shape) != (T, H, W)
+            or alpha.device != device or not alpha.is_contiguous()):
+        raise ValueError("%s: expected a contiguous %s tensor [%d,%d,%d] on %s" % (what, rgb_sample_dtype(pix_fmt), T, H, W, device))
+    return alpha
+
+
+def rgb_to_input(buf, H, W, pix_fmt, full_range=True, sigma=None, pitches=None, offsets=None, pad_to=None, sigma_gain=1.0, return_alpha=False):
+    """buf: uint8 device tensor [T, frame_bytes] of RGB surfaces (``rgb_frame_bytes``; rows longer than one frame are frames that far
+    apart; 16-bit callers view their uint16 as bytes) -> fp32 [T,3(+1),H,W] in R, G, B order, the tensor ``frames_to_input`` builds; with
+    ``sigma`` the noise-map channel is appended.  pix_fmt: one of ``_lib.RGB_FORMATS`` (packed 8 / 16 bit in any component order with alpha
+    or a filler, x2rgb10le / x2bgr10le, planar gbrp / gbrap at 8, 10, 12, 16 bits).  full_range (the default): code / (2^bits - 1); False:
+    (code - 16 s) / (219 s).  NOT clamped.  ``pitches`` / ``offsets``: see ``rgb_frame_bytes``.  ``pad_to=(Hp, Wp)``: any picture size,
+    reflect-padded on the right and bottom after conversion.  ``sigma='auto'`` / a sequence / a device tensor [T] and ``sigma_gain``: as for
+    ``frames_to_input``.  ``return_alpha`` (formats with alpha): True -> (x, alpha), alpha the frames' alpha codes as they are, a device
+    tensor [T,H,W] (uint8, uint16 above 8 bits), picture-sized also with ``pad_to``; a tensor of that shape: written into and returned."""
+    if return_alpha is not False and not rgb_has_alpha(pix_fmt):
+        raise ValueError("rgb_to_input(return_alpha=): pix_fmt %r carries no alpha" % (pix_fmt,))
+    mode = _sigma_mode(sigma, buf.shape[0] if isinstance(buf, torch.Tensor) and buf.dim() == 2 else None)
+    if mode[0] != "const":
+        gain = _check_gain(sigma_gain)
+        r = rgb_to_input(buf, H, W, pix_fmt, full_range, 0.0, pitches, offsets, pad_to, 1.0, return_alpha)
+        x = _with_sigma(r[0] if return_alpha is not False else r, mode, (int(H), int(W)), gain)
+        return (x, r[1]) if return_alpha is not False else x
+    surf, nbytes = _rgb_surface(H, W, pix_fmt, full_range, pitches, offsets, picture=pad_to is not None)
+    H, W = int(H), int(W)
+    Hp, Wp = (H, W) if pad_to is None else _pair(pad_to, "pad_to")
+    lib = require_hip()
+    surf.frame_stride = _surface_buffer(buf, None, nbytes, surf.bits > 8, "rgb_to_input", "16-bit", "16-bit")
+    T = buf.shape[0]
+    alpha = None
+    if return_alpha is True:
+        alpha = torch.empty((T, H, W), dtype=rgb_sample_dtype(pix_fmt), device=buf.device)
+    elif return_alpha is not False:
+        alpha = _alpha_plane(return_alpha, T, H, W, pix_fmt, buf.device, "rgb_to_input(return_alpha=)")
+    extra = 0 if sigma is None else 1
+    y = torch.empty((T, 3 + extra, max(Hp, 0), max(Wp, 0)), dtype=torch.float32, device=buf.device)
+    with torch.cuda.device(buf.device):
+        _lib.check(lib.bsvd_rgb_to_planar(buf.data_ptr(), y.data_ptr(), T, H, W, Hp, Wp, ctypes.byref(surf),
+                                          None if alpha is None else alpha.data_ptr(), extra, float(sigma or 0.0), _stream()), "bsvd_rgb_to_planar")
+    return y if alpha is None else (y, alpha)
+
+
+def output_to_rgb(y, pix_fmt, full_range=True, pitches=None, offsets=None, out=None, crop_to=None, alpha=None):
+    """y: fp32 device tensor [T,3,H,W] (R, G, B) -> uint8 [T, frame_bytes] RGB surfaces: clamp [0,1], scale (+ 16 s at limited range), round
+    half to even.  A filler sample is written as all ones.  ``alpha`` (formats with alpha): the codes to write, a device tensor [T,H,W]
+    (uint8, uint16 above 8 bits; picture-sized also with ``crop_to``) -- what ``rgb_to_input(return_alpha=True)`` gave; None: the maximum
+    code, opaque.  ``out``: the caller's buffer [T, >= frame_bytes] -- pitch padding, the bytes between planes and between frames are left
+    as they were; without it the result's padding is zero.  ``crop_to=(H, W)``: the surfaces of ``y[..., :H, :W]``."""
+    if alpha is not None and not rgb_has_alpha(pix_fmt):
+        raise ValueError("output_to_rgb(alpha=): pix_fmt %r carries no alpha" % (pix_fmt,))
+    rgb_planes(pix_fmt)
+    if not isinstance(y, torch.Tensor) or y.dtype != torch.float32 or not y.is_cuda or y.dim() != 4 or y.shape[1] != 3:
+        raise ValueError("expected a float32 device tensor [T,3,H,W]")
+    T, _, Hp, Wp = y.shape
+    H, W = (Hp, Wp) if crop_to is None else _pair(crop_to, "crop_to")
+    surf, nbytes = _rgb_surface(H, W, pix_fmt, full_range, pitches, offsets, picture=crop_to is not None)
+    lib = require_hip()
+    y = y.contiguous()
+    if alpha is not None:
+        _alpha_plane(alpha, T, H, W, pix_fmt, y.device, "output_to_rgb(alpha=)")
+    if out is None:
+        out = (torch.zeros if pitches or offsets else torch.empty)((T, nbytes), dtype=torch.uint8, device=y.device)
+    elif out.device != y.device:
+        raise ValueError("output_to_rgb: out is on %s, y on %s" % (out.device, y.device))
+    surf.frame_stride = _surface_buffer(out, T, nbytes, surf.bits > 8, "output_to_rgb(out=)", "16-bit", "16-bit")
+    with torch.cuda.device(y.device):
+        _lib.check(lib.bsvd_planar_to_rgb(y.data_ptr(), out.data_ptr(), T, Hp, Wp, H, W, ctypes.byref(surf),
+                                          None if alpha is None else alpha.data_ptr(), _stream()), "bsvd_planar_to_rgb")
     return out

@@ -18,7 +18,13 @@ then the H/2 rows of interleaved CbCr; 1.5 (NV12) or 3 (P010) bytes per pixel ea
 ``bsvd_yuv420_to_planar`` / ``bsvd_planar_to_yuv420`` where the uint8 kernels run for 'rgb24'.  The planar, 4:2:2 and 4:4:4 surfaces
 ('yuv420p', 'yuv420p10le', 'uyvy422', 'yuyv422', 'nv16', 'p210le', 'yuv422p', 'yuv422p10le', 'yuv444p', 'yuv444p10le'; ffmpeg's names)
 cross as 1-D arrays of the tight frame's samples -- what ``ffmpeg -f rawvideo`` emits --, with ``frame_shape=(H, W)`` given at
-construction, converted by ``bsvd_yuv_to_planar`` / ``bsvd_planar_to_yuv``.
+construction, converted by ``bsvd_yuv_to_planar`` / ``bsvd_planar_to_yuv``.  The RGB surfaces of ``_lib.RGB_FORMATS`` besides 'rgb24'
+('bgr24', 'rgba', 'bgra', 'argb', 'abgr', 'rgb0', 'bgr0', '0rgb', '0bgr', 'rgb48le', 'bgr48le', 'rgba64le', 'bgra64le', 'x2rgb10le',
+'x2bgr10le', 'gbrp', 'gbrp10le', 'gbrp12le', 'gbrp16le', 'gbrap', 'gbrap10le', 'gbrap12le', 'gbrap16le') cross as self-describing
+arrays -- packed [H,W,3|4] uint8 / uint16, [H,W] uint32 for the x2 words, planar [P,H,W] -- or as 1-D arrays of the tight frame's
+samples with ``frame_shape``, converted by ``bsvd_rgb_to_planar`` / ``bsvd_planar_to_rgb``; ``colour`` may carry ``full_range`` only
+(default True).  A format with alpha returns every frame with the alpha codes it came with, bit for bit: they wait on the device while
+the frame is inside the network.
 
 ``pad`` selects what happens to a picture whose H or W is no multiple of 4 (the network has two 2x scales): None (the default) refuses
 it; 'reflect' takes any size -- even H and W for the 4:2:0 surfaces -- and does what the reference's callers do around the model
@@ -42,8 +48,8 @@ import torch
 
 from . import _lib
 from .frame_io import (CUT_THRESHOLD, _check_gain, _sigma_mode, _yuv_desc, _yuv_surface, check_cut_threshold, cut_scores, frames_to_input, network_size,
-                       output_to_frames, output_to_yuv, output_to_yuv420, scene_cuts, scene_scores, yuv420_frame_bytes, yuv420_picture_bytes, yuv420_to_input,
-                       yuv_to_input)
+                       output_to_frames, output_to_rgb, output_to_yuv, output_to_yuv420, rgb_frame_bytes, rgb_to_input, scene_cuts, scene_scores,
+                       yuv420_frame_bytes, yuv420_picture_bytes, yuv420_to_input, yuv_to_input)
 
 Colour = collections.namedtuple("Colour", "matrix full_range chroma row_pitch width", defaults=("bt709", False, "linear", None, None))
 Colour.__doc__ = """How a YUV surface is to be read and written: matrix 'bt601' | 'bt709' | 'bt2020', full_range (False = limited / "TV"
@@ -188,6 +194,104 @@ class _YuvSurface:
         return output_to_yuv(y, crop_to=(geom.h, geom.w) if self.pad else None, **self.kw)
 
 
+class _RgbSurface:
+    """the RGB surfaces of _lib.RGB_FORMATS but 'rgb24': self-describing arrays -- packed [H,W,3|4] uint8 / uint16, x2rgb10le / x2bgr10le
+    [H,W] uint32, planar [P,H,W] -- or, with frame_shape=(H, W), 1-D arrays of the tight frame's samples (``ffmpeg -f rawvideo``'s bytes);
+    staged as the tight surface's bytes, converted by bsvd_rgb_to_planar / bsvd_planar_to_rgb.  A format with alpha hands the frames' alpha
+    codes from ``to_input`` to ``to_output`` as a device plane beside the tensor (``alpha=``): the pipelines keep it with its frame."""
+
+    def __init__(self, pix_fmt, colour, pad=None, frame_shape=None):
+        self.pad = _check_pad(pad)
+        if colour is None:
+            colour = {}
+        if not isinstance(colour, dict) or set(colour) - {"full_range"}:
+            raise ValueError("colour: pix_fmt %r is RGB: a dict that may carry 'full_range' only (default True), got %r" % (pix_fmt, colour))
+        self.pix_fmt, self.full_range = pix_fmt, bool(colour.get("full_range", True))
+        layout, self.components, bits, _, fourth = _lib.RGB_FORMATS[pix_fmt]
+        self.x2, self.planar = layout == _lib.RGB_PACKED_X2_10, layout == _lib.RGB_PLANAR
+        self.has_alpha = fourth == _lib.FOURTH_ALPHA
+        self.dtype = np.dtype(np.uint32 if self.x2 else np.uint16 if bits > 8 else np.uint8)
+        self.per_pixel = 1 if self.x2 else self.components            # array elements per pixel
+        self.hw = None
+        if frame_shape is not None:
+            try:
+                self.hw = (int(frame_shape[0]), int(frame_shape[1]))
+            except (TypeError, ValueError, IndexError):
+                raise ValueError("frame_shape: expected (H, W), got %r" % (frame_shape,)) from None
+            self._size(*self.hw)                                      # a size the format cannot carry fails here, not at the first frame
+
+    def _size(self, h, w):
+        what = "%s %d x %d" % (self.pix_fmt, h, w)
+        if self.pad:
+            if h < 2 or w < 2:
+                raise ValueError("expected frames of at least 2 x 2, got %d x %d" % (h, w))
+            net = _padded_size(h, w, what)
+        elif h <= 0 or w <= 0 or h % 4 or w % 4:
+            raise ValueError("%s: H and W must be positive multiples of 4 (pad first: denoise.pad_to_multiple_of_4; or pad='reflect')" % what)
+        else:
+            net = (h, w)
+        return net, rgb_frame_bytes(h, w, self.pix_fmt)
+
+    def natural_shape(self, h, w):
+        return (h, w) if self.x2 else (self.components, h, w) if self.planar else (h, w, self.components)
+
+    def geometry(self, a, clip):
+        shape = tuple(a.shape[1:]) if clip and a.ndim >= 1 else tuple(a.shape)
+        hw = None
+        if a.dtype == self.dtype and not (clip and a.ndim < 2):
+            if len(shape) == 1:
+                if self.hw is None:
+                    raise ValueError("pix_fmt %r: a 1-D frame of samples does not say its picture size: give frame_shape=(H, W)" % (self.pix_fmt,))
+                if shape[0] == self.hw[0] * self.hw[1] * self.per_pixel:
+                    hw = self.hw
+            elif self.x2 and len(shape) == 2:
+                hw = shape
+            elif self.planar and len(shape) == 3 and shape[0] == self.components:
+                hw = shape[1:]
+            elif not self.x2 and not self.planar and len(shape) == 3 and shape[2] == self.components:
+                hw = shape[:2]
+        if hw is None or (self.hw is not None and tuple(hw) != self.hw):
+            raise ValueError("expected %s %s %s%s%s, got %s %s"
+                             % (self.pix_fmt, self.dtype.name, "[T,...] of " if clip else "",
+                                list(self.natural_shape(*(self.hw or ("H", "W")))),
+                                " or the %d samples of the tight frame" % (self.hw[0] * self.hw[1] * self.per_pixel) if self.hw else "",
+                                a.dtype, a.shape))
+        h, w = int(hw[0]), int(hw[1])
+        net, nbytes = self._size(h, w)
+        return _Geometry(h, w, (a.shape[0], nbytes) if clip else (nbytes,), None, *net)
+
+    def to_input(self, dev_in, geom, sigma, sigma_gain=1.0, alpha=None):
+        """alpha (formats with alpha): True -> (x, the frames' alpha plane); a device tensor [T,H,W]: written into"""
+        return rgb_to_input(dev_in, geom.h, geom.w, self.pix_fmt, full_range=self.full_range, sigma=sigma, sigma_gain=sigma_gain,
+                            pad_to=(geom.net_h, geom.net_w) if self.pad else None, return_alpha=False if alpha is None else alpha)
+
+    def to_output(self, y, geom, alpha=None):
+        return output_to_rgb(y, self.pix_fmt, full_range=self.full_range, crop_to=(geom.h, geom.w) if self.pad else None, alpha=alpha)
+
+
+class _AlphaRing:
+    """LiveStream's alpha planes: frame k's alpha codes wait on the device while frame k is inside the network.  ``planes`` picture-sized
+    planes, written in feed order and read in the order the frames come out -- the same order; a plane is written again ``planes`` feeds
+    later, by when the step that read it has been waited for (planes >= latency + depth).  Allocated once with the slots."""
+
+    def __init__(self, planes, h, w, dtype, device):
+        self.buf = torch.empty((planes, 1, h, w), dtype=dtype, device=device)
+        self.fed = self.emitted = 0
+
+    def next_in(self):
+        self.fed += 1
+        return self.buf[(self.fed - 1) % self.buf.shape[0]]
+
+    def next_out(self):
+        if self.emitted >= self.fed:
+            raise RuntimeError("alpha ring: frame %d comes out before it went in" % self.emitted)
+        self.emitted += 1
+        return self.buf[(self.emitted - 1) % self.buf.shape[0]]
+
+    def reset(self):
+        self.fed = self.emitted = 0
+
+
 def _pixel_format(pix_fmt, colour, pad=None, frame_shape=None):
     _check_pad(pad)
     if pix_fmt == "rgb24":
@@ -198,7 +302,9 @@ def _pixel_format(pix_fmt, colour, pad=None, frame_shape=None):
         return _Yuv420(pix_fmt, colour, pad)
     if pix_fmt in _lib.YUV_FORMATS:
         return _YuvSurface(pix_fmt, colour, pad, frame_shape)
-    raise ValueError("pix_fmt %r: one of 'rgb24', 'nv12', 'p010', %s" % (pix_fmt, ", ".join(repr(n) for n in sorted(_lib.YUV_FORMATS))))
+    if isinstance(pix_fmt, str) and pix_fmt in _lib.RGB_FORMATS:
+        return _RgbSurface(pix_fmt, colour, pad, frame_shape)
+    raise ValueError("pix_fmt %r: one of 'rgb24', 'nv12', 'p010', %s" % (pix_fmt, ", ".join(repr(n) for n in sorted(set(_lib.YUV_FORMATS) | set(_lib.RGB_FORMATS) - {"rgb24"}))))
 
 
 def _check_cuts_mode(cuts, cut_threshold, what):
@@ -229,6 +335,7 @@ class _Slot:
         self.downloaded = torch.cuda.Event()
         self.ticket = None          # the in-flight clip occupying this slot
         self.dev_sigma = self.pin_sigma = None      # LiveStream(sigma='auto'): the step's estimate, 4 bytes beside the frame
+        self.dev_alpha = None                       # ClipPipeline, formats with alpha: the clip's alpha plane [T,H,W], held like dev_out
 
 
 class _Ticket:
@@ -255,6 +362,9 @@ class ClipPipeline:
     with frame_shape=(H, W): clips are [T, n] arrays of the tight frames' samples (uint8, uint16 for 10 bit), as ffmpeg's rawvideo.
     sigma='auto' (non-blind models): every frame's noise-map plane holds that frame's own estimate, times sigma_gain, computed on the
     device (``frame_io.estimate_sigma``: what is known about it, and that YUV sources with subsampled chroma read low).
+    pix_fmt one of the RGB names of the module docstring ('bgra', 'rgba64le', 'gbrp10le', ...): clips are [T,...] arrays of self-describing
+    frames (or [T, n] tight samples with frame_shape), colour={'full_range': bool}; the clip's alpha codes stay on the device beside the
+    clip and come back with their frames.
     cuts='auto': the scene starts of every clip are detected on the device (``frame_io.scene_cuts`` at ``cut_threshold``; its docstring says
     what is known about the rule -- nothing on real footage -- and its blind spot: a cut one or two frames after another scores low) and
     handed to the model's forward, which runs every scene as a clip of its own.  The detection reads T integers back before the forward is
@@ -268,6 +378,7 @@ class ClipPipeline:
         self.last_cuts = None
         self.sigma_gain = _check_sigma(model, sigma, sigma_gain, "ClipPipeline")
         self.fmt = _pixel_format(pix_fmt, colour, pad, frame_shape)
+        self.alpha = getattr(self.fmt, "has_alpha", False)       # the clip's alpha codes ride beside the clip, [T,H,W] on the device
         self.model, self.sigma = model, sigma
         self.device = model._device()
         if self.device.type != "cuda":
@@ -300,7 +411,10 @@ class ClipPipeline:
                 slot.uploaded.record()
             with torch.cuda.stream(self.comp):
                 self.comp.wait_event(slot.uploaded)
-                x = self.fmt.to_input(slot.dev_in, geom, self.sigma, self.sigma_gain)
+                if self.alpha:
+                    x, slot.dev_alpha = self.fmt.to_input(slot.dev_in, geom, self.sigma, self.sigma_gain, alpha=True)
+                else:
+                    x = self.fmt.to_input(slot.dev_in, geom, self.sigma, self.sigma_gain)
                 T, _, H, W = x.shape
                 kw = {}
                 if self.auto_cuts:
@@ -310,7 +424,8 @@ class ClipPipeline:
                     y = self.model.clip_forward(x, **kw)
                 else:
                     y = self.model.streaming_forward(x, **kw)
-                slot.dev_out = self.fmt.to_output(y.float(), geom)  # held by the slot until its download completed
+                # held by the slot until its download completed
+                slot.dev_out = self.fmt.to_output(y.float(), geom, alpha=slot.dev_alpha) if self.alpha else self.fmt.to_output(y.float(), geom)
                 slot.computed.record()
             with torch.cuda.stream(self.down):
                 self.down.wait_event(slot.computed)
@@ -361,6 +476,12 @@ class LiveStream:
     planar, 4:2:2 and 4:4:4 surfaces; ``frame_shape`` is required): feed takes and returns 1-D arrays of the tight frame's samples
     (uint8, uint16 for 10 bit) -- the bytes ``ffmpeg -f rawvideo`` emits --, converted by ``bsvd_yuv_to_planar`` / ``bsvd_planar_to_yuv``.
 
+    pix_fmt one of the RGB names of the module docstring ('bgr24', 'bgra', 'rgba64le', 'x2rgb10le', 'gbrp10le', ...): feed takes and returns
+    self-describing arrays ([H,W,3|4], [H,W] uint32, [P,H,W]) or, with ``frame_shape``, 1-D tight samples, converted by
+    ``bsvd_rgb_to_planar`` / ``bsvd_planar_to_rgb``.  Alpha rides with its frame: the frame returned for source frame k carries frame k's
+    alpha codes bit for bit, ``latency`` feeds later, through ``cut=True`` and ``flush()`` -- a ring of ``latency + depth`` picture-sized
+    planes on the device, allocated with the slots, filled by the decode and consumed in order by the encode; nothing is allocated per feed.
+
     pad None | 'reflect': 'reflect' takes frames of any size (even H and W for YUV): reflect-padded to the next multiples of 4 and cropped
     again on the device, same latency, frames back in the fed shape.
 
@@ -396,6 +517,7 @@ class LiveStream:
         self.auto_sigma = isinstance(sigma, str)
         self.last_sigma = None
         self.fmt = _pixel_format(pix_fmt, colour, pad, frame_shape)
+        self._alpha = None                                    # formats with alpha: the ring of alpha planes (_AlphaRing), allocated with the slots
         self.model, self.sigma, self.depth = model, sigma, depth
         self._overlap_wanted = (depth >= 2) if overlap_blocks is None else bool(overlap_blocks)
         self._overlap_explicit = overlap_blocks is not None
@@ -456,6 +578,8 @@ class LiveStream:
                 s.pin_sigma = torch.zeros(1, dtype=torch.float32).pin_memory()
                 s.dev_sigma = torch.empty(1, dtype=torch.float32, device=self.device)
             self.slots.append(s)
+        if getattr(self.fmt, "has_alpha", False):
+            self._alpha = _AlphaRing(self.latency + self.depth, geom.h, geom.w, getattr(torch, self.fmt.dtype.name), self.device)
         if self.auto_cuts:
             gh, gw = geom.h // 16, geom.w // 16
             self._grids = torch.zeros((2, 1, gh, gw), dtype=torch.int32, device=self.device)
@@ -470,7 +594,7 @@ class LiveStream:
     def _detect(self, slot):
         """cuts='auto', on the upload stream behind the frame's copy: conversion, grid, difference against the previous frame's grid, 8 bytes
         to pinned memory; the host waits for them and decides.  -> (the network input, handed on to the compute stream; cut?)"""
-        x = self.fmt.to_input(slot.dev_in, self.geom, self.sigma, self.sigma_gain)
+        x = self._to_input(slot)
         x.record_stream(self.comp)
         cur = self._grids[self._n_scored % 2]
         prev = self._grids[(self._n_scored + 1) % 2][0] if self._have_prev else None
@@ -485,6 +609,18 @@ class LiveStream:
         self.last_cut_score = score[0]
         self.last_cut = score[0] >= self.cut_threshold
         return x, self.last_cut
+
+    def _to_input(self, slot):
+        """the slot's frame -> the network input; a format with alpha leaves the frame's alpha codes in the ring's next plane"""
+        if self._alpha is None:
+            return self.fmt.to_input(slot.dev_in, self.geom, self.sigma, self.sigma_gain)
+        return self.fmt.to_input(slot.dev_in, self.geom, self.sigma, self.sigma_gain, alpha=self._alpha.next_in())[0]
+
+    def _to_output(self, y):
+        """what a step emitted -> the surface; frames come out in the order they went in, and so do their alpha planes"""
+        if self._alpha is None:
+            return self.fmt.to_output(y.float(), self.geom)
+        return self.fmt.to_output(y.float(), self.geom, alpha=self._alpha.next_out())
 
     def _pop(self):
         """oldest in-flight step -> its uint8 frame, or None if that step emitted nothing (pipeline fill)"""
@@ -513,13 +649,13 @@ class LiveStream:
                 if frame_u8 is not None:
                     self.comp.wait_event(slot.uploaded)
                     if x is None:
-                        x = self.fmt.to_input(slot.dev_in, self.geom, self.sigma, self.sigma_gain)
+                        x = self._to_input(slot)
                     if self.auto_sigma:
                         slot.dev_sigma.copy_(x[0, -1, 0, :1])          # the plane holds the estimate: one element of it, device to device
                 kw = dict(cut=True) if cut else {}
                 y = self.model.feed_overlapped(x, last=last, **kw) if self.overlap else self.model.feedin_one_element(x, **kw)
                 if y is not None:
-                    slot.dev_out = self.fmt.to_output(y.float(), self.geom)   # held by the slot until its download completed
+                    slot.dev_out = self._to_output(y)             # held by the slot until its download completed
                 slot.computed.record()
             with torch.cuda.stream(self.down):
                 self.down.wait_event(slot.computed)
@@ -566,5 +702,7 @@ class LiveStream:
         self._drain(0, outs)
         self.model.reset()
         self._forget_scene()
+        if self._alpha is not None:
+            self._alpha.reset()
         self._reopen_overlap()                        # the next stream decides again (free HBM may have changed)
         return outs

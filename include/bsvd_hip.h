@@ -483,6 +483,79 @@ int bsvd_planar_to_yuv_crop(const float *src, void *dst, int32_t frames, int32_t
                             const BsvdYuvSurface *surface, void *stream);
 
 /*
+ * RGB surfaces: what callers hold who do not come through a video decoder -- OpenCV (bgr24), screen / window capture and GL / Vulkan
+ * read-back (bgra, rgba, bgr0, pitched), 16-bit image sequences and mastering formats (rgb48le, gbrp10le .. gbrp16le, gbrap*), DRM / VAAPI
+ * capture (x2rgb10le).  bsvd_u8_to_planar / bsvd_planar_to_u8 and their _pad / _crop forms are unchanged; these three take a BsvdRgbSurface.
+ * Added without a new BSVD_ABI_VERSION: discover the three entry points by symbol (dlsym), like the YUV entry points above.
+ *
+ * A surface is a layout, a component count, a sample width and the place of each component:
+ *   BSVD_RGB_PACKED        one plane of pixels; a pixel is `components` (3 or 4) samples, each one byte (bits = 8) or one little-endian
+ *                          16-bit word with the code in the LOW `bits` bits (bits = 10, 12, 16; the high bits ignored in, zero out).
+ *                          pos[c] = index of the sample of component c inside the pixel.
+ *   BSVD_RGB_PACKED_X2_10  one plane of 32-bit little-endian words, three 10-bit fields and two unused top bits (ignored in, ones out):
+ *                          field i is bits [10 i, 10 i + 10); pos[c] = the field of component c.  components = 3, bits = 10, fourth = 0.
+ *                          x2rgb10le ((msb) 2 X | R | G | B (lsb)) is pos = {2, 1, 0}, x2bgr10le pos = {0, 1, 2}.
+ *   BSVD_RGB_PLANAR        `components` (3 or 4) planes of W x H samples (one byte, or a 16-bit word as above); pos[c] = the plane of
+ *                          component c.  ffmpeg's gbrp* is pos = {2, 0, 1}, gbrap* pos = {2, 0, 1, 3}.
+ * Components: 0 = R, 1 = G, 2 = B, 3 = the fourth sample, which `fourth` names: 1 = alpha, 2 = a filler (rgb0, bgr0, 0rgb, 0bgr);
+ * components = 3 goes with fourth = 0 and pos[3] = 0.  pos[0 .. components - 1] is a permutation of 0 .. components - 1.
+ * Plane i has pitch[i] BYTES per row (0 = tight) and starts offset[i] bytes from the frame's first byte (offset[0] as given; 0 for a later
+ * plane = directly behind the last row of the plane before, pitch included); frames are frame_stride bytes apart (0 = tight: the end of
+ * the plane that ends last).  A plane occupies [offset, offset + pitch * H); planes must not share bytes.  pitch / offset of planes the
+ * layout does not have must be 0.  With 16-bit samples pitch, offset, frame_stride and the surface pointer are multiples of 2, with
+ * BSVD_RGB_PACKED_X2_10 of 4.
+ *
+ * Sizes: H x W is the picture (what the surface has), Hp x Wp the planar tensor.  Hp == H and Wp == W is the plain case; otherwise the
+ * rules of bsvd_u8_to_planar_pad / bsvd_planar_to_u8_crop hold word for word: in, "convert at picture size, then reflect-pad" on the right
+ * and bottom, the pad below the dimension; out, "take src[..., :H, :W], then convert".  Any Hp, Wp and any alignment (float4 on the fp32
+ * side when Wp % 4 == 0 and the tensor is 16-byte aligned, scalars otherwise; the same bits either way).
+ *
+ * Arithmetic, in fp32, no contraction, with s = 2^(bits - 8), for each of R, G, B alike:
+ *   in   full_range = 1:  v = (float)code / (float)(2^bits - 1)         (what bsvd_u8_to_planar does at 8 bits)
+ *        full_range = 0:  v = ((float)code - 16 s) / (219 s)
+ *        one subtraction (of 0 at full range) and one IEEE division.  NOT clamped: codes outside the legal range give v outside [0,1].
+ *   out  c = rintf(fminf(fmaxf(v, 0), 1) * m + a), m = 2^bits - 1, a = 0 (full) or m = 219 s, a = 16 s (limited): one multiplication,
+ *        one addition, round half to even; then clamped to [0, 2^bits - 1] or [16 s, 235 s].  At 8 bits full range: bsvd_planar_to_u8's.
+ *   At full range every code of 8, 10, 12 and 16 bits comes back as itself; at limited range every legal code does and the others
+ *   land on the nearest legal end.
+ * dst of bsvd_rgb_to_planar is [frames][3 + const_channels][Hp][Wp], planes R, G, B, then the constant channels (constant over the whole
+ * plane); src of bsvd_planar_to_rgb is [frames][3][Hp][Wp].
+ * The fourth sample.  A filler is ignored on input and written as all ones on output (255, 2^bits - 1).  Alpha never meets the arithmetic:
+ * with alpha_out != NULL the decode also writes the alpha codes, masked to `bits`, into a tight picture-sized side plane [frames][H][W]
+ * of the container type (uint8_t or uint16_t), never padded; alpha_out == NULL ignores alpha.  The encode takes the alpha codes from
+ * alpha_in (the same side plane, masked to `bits`), or writes the maximum code when alpha_in is NULL.
+ * No byte outside a surface's samples is read or written -- pitch padding, the bytes between planes and frames, and on input the ignored
+ * bits of a word are all outside --, and every sample, every element of the fp32 tensor and of alpha_out is written exactly once.
+ * All return -3, naming the argument in bsvd_last_error(), without a device, for: a NULL src, dst or surface; frames <= 0; H or W <= 0;
+ * Hp < H or Wp < W; a pad of a whole dimension or more; an unknown layout; components other than 3 / 4; bits other than 8 / 10 / 12 / 16
+ * or not served by the layout; fourth outside 0 .. 2 or at odds with components; full_range other than 0 / 1; pos not a permutation;
+ * a reserved field != 0; a pitch below the plane's row; a negative offset; pitch / offset set for a plane the layout lacks; planes
+ * sharing bytes; frame_stride below one frame; a pitch, offset, frame_stride or surface / alpha pointer off the sample's alignment; a
+ * planar pointer that is not 4-byte aligned; alpha_out / alpha_in given for a surface without alpha; const_channels < 0.
+ * bsvd_rgb_frame_bytes: the bytes of one frame, tight or pitched; -1 on bad arguments.
+ */
+enum { BSVD_RGB_PACKED = 0, BSVD_RGB_PACKED_X2_10 = 1, BSVD_RGB_PLANAR = 2 };
+enum { BSVD_RGB_FOURTH_NONE = 0, BSVD_RGB_FOURTH_ALPHA = 1, BSVD_RGB_FOURTH_FILLER = 2 };
+typedef struct BsvdRgbSurface {
+    int32_t layout;
+    int32_t components;        /* 3 or 4: samples per pixel (PACKED) / planes (PLANAR); 3 with PACKED_X2_10 */
+    int32_t bits;              /* 8 | 10 | 12 | 16; 10 with PACKED_X2_10 */
+    int32_t pos[4];            /* where R, G, B and the fourth sample sit */
+    int32_t fourth;            /* BSVD_RGB_FOURTH_* */
+    int32_t full_range;        /* 1 = codes span [0, 2^bits - 1], 0 = [16 s, 235 s] */
+    int32_t pitch[4];          /* bytes per row of plane i; 0 = tight */
+    int32_t reserved0;         /* must be 0 */
+    int64_t offset[4];         /* bytes from the frame's first byte to plane i; 0 for planes 1 .. 3 = directly behind the plane before */
+    int64_t frame_stride;      /* bytes; 0 = tight */
+    int64_t reserved;          /* must be 0 */
+} BsvdRgbSurface;              /* 104 bytes */
+int64_t bsvd_rgb_frame_bytes(int32_t H, int32_t W, const BsvdRgbSurface *surface);
+int bsvd_rgb_to_planar(const void *src, float *dst, int32_t frames, int32_t H, int32_t W, int32_t Hp, int32_t Wp,
+                       const BsvdRgbSurface *surface, void *alpha_out, int32_t const_channels, float const_value, void *stream);
+int bsvd_planar_to_rgb(const float *src, void *dst, int32_t frames, int32_t Hp, int32_t Wp, int32_t H, int32_t W,
+                       const BsvdRgbSurface *surface, const void *alpha_in, void *stream);
+
+/*
  * The noise level of a frame, estimated on the device.  bsvd_c64 is non-blind: its fourth input channel is the noise map, which the
  * reference fills with a constant the caller knows (temp_denoise's sigma map, validation_seq_infer.py:19-21).  A camera, SDI or ffmpeg
  * feed comes without one.  These entry points stand in for that constant: bsvd_estimate_sigma computes one sigma per frame from the planar

@@ -2,7 +2,9 @@
 """Denoises a raw YUV stream -- NV12 or P010 frames, or planar / 4:2:2 / 4:4:4 ones (yuv420p, yuv420p10le, uyvy422, yuyv422, nv16,
 p210le, yuv422p, yuv422p10le, yuv444p, yuv444p10le), as any `-f rawvideo` producer pipes them -- through
 bsvd_amd.pipeline.LiveStream(pix_fmt=...): surfaces over PCIe, colour conversion on the device, one graph-replayed pipeline step per
-frame.  Prints one JSON line: frames, frames_per_s (whole run, host to host, file I/O and pipeline fill included), ms_per_feed p50 / p99 and
+frame.  The same for raw RGB streams (the file name is older than they are): --pix-fmt bgr24, rgba, bgra, argb, abgr, rgb0, bgr0, 0rgb, 0bgr,
+rgb48le, bgr48le, rgba64le, bgra64le, x2rgb10le, x2bgr10le, gbrp, gbrp10le / 12le / 16le, gbrap, gbrap10le / 12le / 16le (rgb24: tools/live_stream.py); full
+range unless --limited-range; any size; the alpha of a frame comes out with that frame, bit for bit.  Prints one JSON line: frames, frames_per_s (whole run, host to host, file I/O and pipeline fill included), ms_per_feed p50 / p99 and
 steady_frames_per_s (wall clock, reads and writes included) over the steady state, the second half of the feeds.
 
     python tools/yuv_denoise.py IN OUT --size 1920x1080 --pix-fmt nv12 --sigma 30 [--matrix bt709] [--full-range] [--chroma linear]
@@ -49,26 +51,31 @@ def main(argv=None):
     ap.add_argument("input")
     ap.add_argument("output")
     ap.add_argument("--size", required=True, help="WxH of the pictures, e.g. 1920x1080")
-    ap.add_argument("--pix-fmt", default="yuv420p", choices=["nv12", "p010"] + sorted(_lib.YUV_FORMATS))
+    ap.add_argument("--pix-fmt", default="yuv420p", choices=["nv12", "p010"] + sorted(_lib.YUV_FORMATS) + sorted(set(_lib.RGB_FORMATS) - {'rgb24'}))
     ap.add_argument("--sigma", type=parse_sigma, required=True, help="noise std in 8-bit code units (e.g. 30), or auto: estimated per frame on the device")
     ap.add_argument("--sigma-gain", type=float, default=1.0, help="factor on the estimate of --sigma auto")
     ap.add_argument("--cuts", default="none", choices=["none", "auto"], help="auto: scene cuts detected per frame on the device")
     ap.add_argument("--cut-threshold", type=float, default=frame_io.CUT_THRESHOLD, help="score at which --cuts auto declares a scene start")
     ap.add_argument("--matrix", default="bt709", choices=["bt601", "bt709", "bt2020"])
     ap.add_argument("--full-range", action="store_true")
+    ap.add_argument("--limited-range", action="store_true", help="RGB formats: codes span [16 s, 235 s] instead of the full range")
     ap.add_argument("--chroma", default="linear", choices=["nearest", "linear"])
     ap.add_argument("--depth", type=int, default=2)
     ap.add_argument("--ckpt", default=None)
     ap.add_argument("--precision", default="f16x3")
     a = ap.parse_args(argv)
     W, H = map(int, a.size.lower().split("x"))
-    surface = a.pix_fmt in _lib.YUV_FORMATS              # the 1-D frames of the planar / 4:2:2 / 4:4:4 formats
-    sub, bits = (_lib.YUV_FORMATS[a.pix_fmt][0], _lib.YUV_FORMATS[a.pix_fmt][2]) if surface else (_lib.SUB_420, 8 if a.pix_fmt == "nv12" else 10)
+    rgb = a.pix_fmt in _lib.RGB_FORMATS                  # the RGB formats: 1-D frames too
+    surface = a.pix_fmt in _lib.YUV_FORMATS or rgb       # the 1-D frames of the planar / 4:2:2 / 4:4:4 formats
+    if rgb:
+        sub, bits = _lib.SUB_444, 32 if _lib.RGB_FORMATS[a.pix_fmt][0] == _lib.RGB_PACKED_X2_10 else _lib.RGB_FORMATS[a.pix_fmt][2]
+    else:
+        sub, bits = (_lib.YUV_FORMATS[a.pix_fmt][0], _lib.YUV_FORMATS[a.pix_fmt][2]) if surface else (_lib.SUB_420, 8 if a.pix_fmt == "nv12" else 10)
     if W <= 2 or H <= 2 or (W % 2 and sub != _lib.SUB_444) or (H % 2 and sub == _lib.SUB_420):
         ap.error("--size %s: at least 3x3; the width must be even for 4:2:0 and 4:2:2, the height for 4:2:0" % a.size)
     pad = "reflect" if W % 4 or H % 4 else None
-    dtype = np.dtype(np.uint8 if bits == 8 else "<u2")
-    nbytes = frame_io.yuv_frame_bytes(H, W, a.pix_fmt) if surface else W * H * 3 // 2 * dtype.itemsize
+    dtype = np.dtype(np.uint8 if bits == 8 else "<u4" if bits == 32 else "<u2")
+    nbytes = frame_io.rgb_frame_bytes(H, W, a.pix_fmt) if rgb else frame_io.yuv_frame_bytes(H, W, a.pix_fmt) if surface else W * H * 3 // 2 * dtype.itemsize
 
     import torch
     import bsvd_amd
@@ -77,7 +84,7 @@ def main(argv=None):
     m = bsvd_amd.BSVD(chns=[64, 128, 256], mid_ch=64, norm="none", act="relu6", interm_ch=64, pretrain_ckpt=a.ckpt,
                       precision=a.precision).to(torch.device("cuda", 0)).eval()
     live = LiveStream(m, sigma=a.sigma, sigma_gain=a.sigma_gain, depth=a.depth, frame_shape=(H, W), pix_fmt=a.pix_fmt,
-                      colour={"matrix": a.matrix, "full_range": a.full_range, "chroma": a.chroma}, pad=pad,
+                      colour={"full_range": not a.limited_range} if rgb else {"matrix": a.matrix, "full_range": a.full_range, "chroma": a.chroma}, pad=pad,
                       cuts="auto" if a.cuts == "auto" else None, cut_threshold=a.cut_threshold)
     found = []
     fin = sys.stdin.buffer if a.input == "-" else open(a.input, "rb")
