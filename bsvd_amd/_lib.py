@@ -27,10 +27,15 @@ EXPORTS = ("bsvd_abi_version", "bsvd_conv_args_size", "bsvd_build_info", "bsvd_l
            "bsvd_yuv_frame_bytes", "bsvd_yuv_to_planar", "bsvd_planar_to_yuv", "bsvd_yuv_to_planar_pad", "bsvd_planar_to_yuv_crop",
            "bsvd_sigma_workspace_bytes", "bsvd_estimate_sigma", "bsvd_fill_sigma_plane",
            "bsvd_scene_grid", "bsvd_scene_diff",
-           "bsvd_rgb_frame_bytes", "bsvd_rgb_to_planar", "bsvd_planar_to_rgb")
+           "bsvd_rgb_frame_bytes", "bsvd_rgb_to_planar", "bsvd_planar_to_rgb",
+           "bsvd_blend_planar", "bsvd_planar_to_yuv420_crop_d", "bsvd_planar_to_yuv_crop_d", "bsvd_planar_to_rgb_d")
 PIX_FMT = {"nv12": 0, "p010": 1}
 MATRIX = {"bt601": 0, "bt709": 1, "bt2020": 2}
 CHROMA = {"nearest": 0, "linear": 1}
+DITHER = {None: 0, "ordered": 1, "random": 2}           # BSVD_DITHER_*
+DITHER_NONE, DITHER_ORDERED, DITHER_RANDOM = 0, 1, 2
+# Kr, Kg, Kb of the matrices, as the encoders make them (frame_yuv.hip): Kg = 1 - Kr - Kb in double
+LUMA_WEIGHTS = {name: (kr, 1.0 - kr - kb, kb) for name, (kr, kb) in (("bt601", (0.299, 0.114)), ("bt709", (0.2126, 0.0722)), ("bt2020", (0.2627, 0.0593)))}
 SUB_420, SUB_422, SUB_444 = 0, 1, 2
 LAYOUT_PLANAR, LAYOUT_SEMIPLANAR, LAYOUT_UYVY, LAYOUT_YUYV = 0, 1, 2, 3
 SIGMA_BINS = 4096             # bins of bsvd_estimate_sigma's histogram: 1 / 4096 of |r| each
@@ -133,6 +138,11 @@ class BsvdRgbSurface(ctypes.Structure):
     _fields_ = [("layout", ctypes.c_int32), ("components", ctypes.c_int32), ("bits", ctypes.c_int32), ("pos", ctypes.c_int32 * 4),
                 ("fourth", ctypes.c_int32), ("full_range", ctypes.c_int32), ("pitch", ctypes.c_int32 * 4), ("reserved0", ctypes.c_int32),
                 ("offset", ctypes.c_int64 * 4), ("frame_stride", ctypes.c_int64), ("reserved", ctypes.c_int64)]
+
+
+class BsvdDither(ctypes.Structure):
+    """Mirror of ``struct BsvdDither`` (include/bsvd_hip.h)."""
+    _fields_ = [("mode", ctypes.c_int32), ("seed", ctypes.c_uint32), ("frame0", ctypes.c_int64), ("reserved", ctypes.c_int64)]
 
 
 class BsvdLibraryError(RuntimeError):
@@ -249,6 +259,15 @@ def load():
     lib.bsvd_rgb_to_planar.argtypes = [vp, vp, i32, i32, i32, i32, i32, rgb, vp, i32, f32, vp]
     lib.bsvd_planar_to_rgb.restype = ctypes.c_int
     lib.bsvd_planar_to_rgb.argtypes = [vp, vp, i32, i32, i32, i32, i32, rgb, vp, vp]
+    dith = ctypes.POINTER(BsvdDither)
+    lib.bsvd_blend_planar.restype = ctypes.c_int
+    lib.bsvd_blend_planar.argtypes = [vp, i64, vp, i64, i32, i32, i32, f32, f32, ctypes.POINTER(f32), vp]
+    lib.bsvd_planar_to_yuv420_crop_d.restype = ctypes.c_int
+    lib.bsvd_planar_to_yuv420_crop_d.argtypes = [vp, vp, i32, i32, i32, i32, i32, ctypes.POINTER(BsvdYuvDesc), dith, vp]
+    lib.bsvd_planar_to_yuv_crop_d.restype = ctypes.c_int
+    lib.bsvd_planar_to_yuv_crop_d.argtypes = [vp, vp, i32, i32, i32, i32, i32, surf, dith, vp]
+    lib.bsvd_planar_to_rgb_d.restype = ctypes.c_int
+    lib.bsvd_planar_to_rgb_d.argtypes = [vp, vp, i32, i32, i32, i32, i32, rgb, vp, dith, vp]
     lib.bsvd_workspace_bytes.restype = i64
     lib.bsvd_workspace_bytes.argtypes = [ctypes.POINTER(BsvdConvArgs)]
     if lib.bsvd_abi_version() != ABI_VERSION:

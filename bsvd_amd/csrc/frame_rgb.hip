@@ -17,16 +17,16 @@ __global__ __launch_bounds__(256) void rgb_to_planar_kernel(const uint8_t *__res
 }
 
 template <class F>
-__global__ __launch_bounds__(256) void planar_to_rgb_kernel(const float *__restrict__ src, uint8_t *__restrict__ dst, const void *__restrict__ alpha, RgbGeom g, RgbEncode k, int64_t items)
+__global__ __launch_bounds__(256) void planar_to_rgb_kernel(const float *__restrict__ src, uint8_t *__restrict__ dst, const void *__restrict__ alpha, RgbGeom g, RgbEncode k, Dither di, int64_t items)
 {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < items; i += (int64_t)gridDim.x * blockDim.x)
-        planar_to_rgb_item<F>(src, dst, alpha, g, k, i);
+        planar_to_rgb_item<F>(src, dst, alpha, g, k, di, i);
 }
 
 // ---------------------------------------------------------------------------------------------
 // host side: the table, validation (no device needed), constants, dispatch
 using DecodeKernel = void (*)(const uint8_t *, float *, void *, RgbGeom, RgbDecode, int64_t);
-using EncodeKernel = void (*)(const float *, uint8_t *, const void *, RgbGeom, RgbEncode, int64_t);
+using EncodeKernel = void (*)(const float *, uint8_t *, const void *, RgbGeom, RgbEncode, Dither, int64_t);
 // [packed 0 | planar 1][sample bytes - 1][slots - 3], then the x2 word
 #define BSVD_RGB_TABLE(K) {{{K<RgbFmt<BSVD_RGB_PACKED, 1, 3>>, K<RgbFmt<BSVD_RGB_PACKED, 1, 4>>}, {K<RgbFmt<BSVD_RGB_PACKED, 2, 3>>, K<RgbFmt<BSVD_RGB_PACKED, 2, 4>>}}, \
                            {{K<RgbFmt<BSVD_RGB_PLANAR, 1, 3>>, K<RgbFmt<BSVD_RGB_PLANAR, 1, 4>>}, {K<RgbFmt<BSVD_RGB_PLANAR, 2, 3>>, K<RgbFmt<BSVD_RGB_PLANAR, 2, 4>>}}}
@@ -169,13 +169,16 @@ int bsvd_rgb_to_planar(const void *src, float *dst, int32_t frames, int32_t H, i
     return launch_sweep(kern, items, stream, (const uint8_t *)src, dst, alpha_out, p.g, k, items);
 }
 
-int bsvd_planar_to_rgb(const float *src, void *dst, int32_t frames, int32_t Hp, int32_t Wp, int32_t H, int32_t W, const BsvdRgbSurface *surface,
-                       const void *alpha_in, void *stream)
+// dither == NULL: off (bsvd_planar_to_rgb)
+static int encode_rgb(const char *fn, const float *src, void *dst, int32_t frames, int32_t Hp, int32_t Wp, int32_t H, int32_t W, const BsvdRgbSurface *surface,
+                      const void *alpha_in, const BsvdDither *dither, void *stream)
 {
     RgbPlan p;
     int64_t items = 0;
-    const int rc = rgb_check({"bsvd_planar_to_rgb", dst, "dst", src, "src", alpha_in, "alpha_in", frames, H, W, Hp, Wp}, surface, &p, &items);
+    const int rc = rgb_check({fn, dst, "dst", src, "src", alpha_in, "alpha_in", frames, H, W, Hp, Wp}, surface, &p, &items);
     if (rc) return rc;
+    Dither di;
+    if (dither_check(fn, dither, &di)) return -3;
     const float s = (float)(1 << (p.bits - 8)), top = (float)((1u << p.bits) - 1);
     RgbEncode k;
     k.mul = p.full_range ? top : 219.f * s;
@@ -184,7 +187,20 @@ int bsvd_planar_to_rgb(const float *src, void *dst, int32_t frames, int32_t Hp, 
     k.hi = p.full_range ? top : 235.f * s;
     k.fill = p.g.mask;
     const EncodeKernel kern = surface->layout == BSVD_RGB_PACKED_X2_10 ? kEncodeX2 : kEncode[table_row(surface)][p.bits > 8][surface->components - 3];
-    return launch_sweep(kern, items, stream, src, (uint8_t *)dst, alpha_in, p.g, k, items);
+    return launch_sweep(kern, items, stream, src, (uint8_t *)dst, alpha_in, p.g, k, di, items);
+}
+
+int bsvd_planar_to_rgb(const float *src, void *dst, int32_t frames, int32_t Hp, int32_t Wp, int32_t H, int32_t W, const BsvdRgbSurface *surface,
+                       const void *alpha_in, void *stream)
+{
+    return encode_rgb("bsvd_planar_to_rgb", src, dst, frames, Hp, Wp, H, W, surface, alpha_in, nullptr, stream);
+}
+
+int bsvd_planar_to_rgb_d(const float *src, void *dst, int32_t frames, int32_t Hp, int32_t Wp, int32_t H, int32_t W, const BsvdRgbSurface *surface,
+                         const void *alpha_in, const BsvdDither *dither, void *stream)
+{
+    if (!dither) { set_error("bsvd_planar_to_rgb_d: dither is NULL"); return -3; }
+    return encode_rgb("bsvd_planar_to_rgb_d", src, dst, frames, Hp, Wp, H, W, surface, alpha_in, dither, stream);
 }
 
 }  // extern "C"

@@ -17,6 +17,7 @@
 #pragma once
 #include <type_traits>
 #include "frame_items.h"
+#include "frame_finish_items.h"
 
 namespace bsvd {
 
@@ -166,9 +167,13 @@ BSVD_HD void rgb_to_planar_item(const uint8_t *src, float *dst, void *alpha, con
 
 BSVD_HD unsigned rgb_code(float v, const RgbEncode &k) { return (unsigned)fminf(fmaxf(rintf(clamp01(v) * k.mul + k.add), k.lo), k.hi); }
 
-// encode: [frames][3][Hp][Wp] -> surface; only picture rows and columns are read.  alpha: the side plane, or NULL (the fourth sample is k.fill)
+// ... with the dither value d (frame_finish_items.h) joining the scaled value right before rintf: clamp(rintf(t + d), lo, hi)
+BSVD_HD unsigned rgb_code_d(float v, const RgbEncode &k, float d) { return (unsigned)fminf(fmaxf(rintf(clamp01(v) * k.mul + k.add + d), k.lo), k.hi); }
+
+// encode: [frames][3][Hp][Wp] -> surface; only picture rows and columns are read.  alpha: the side plane, or NULL (the fourth sample is k.fill).
+// Dither touches R, G and B on the picture's grid, never the fourth sample; with di.mode == BSVD_DITHER_NONE the codes are rgb_code's.
 template <class F>
-BSVD_HD void planar_to_rgb_item(const float *src, uint8_t *dst, const void *alpha, const RgbGeom &g, const RgbEncode &k, int64_t i)
+BSVD_HD void planar_to_rgb_item(const float *src, uint8_t *dst, const void *alpha, const RgbGeom &g, const RgbEncode &k, const Dither &di, int64_t i)
 {
     using A = typename F::A;
     const PadItem it = pad_item_of(i, g.H, g.W, 1);
@@ -187,8 +192,15 @@ BSVD_HD void planar_to_rgb_item(const float *src, uint8_t *dst, const void *alph
 #pragma unroll
                 for (int q = 0; q < 4; ++q) if (q < it.n) v[q] = s[c * plane + q];
             }
+            if (di.mode != BSVD_DITHER_NONE) {
+                float d[4] = {0.f, 0.f, 0.f, 0.f};
+                dither_add<4>(di, it.f, c, it.row, it.x0, d);
 #pragma unroll
-            for (int q = 0; q < 4; ++q) code[j][q] = rgb_code(v[q], k);
+                for (int q = 0; q < 4; ++q) code[j][q] = rgb_code_d(v[q], k, d[q]);
+            } else {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) code[j][q] = rgb_code(v[q], k);
+            }
         } else if constexpr (F::SLOTS == 4) {
             A a[4] = {(A)k.fill, (A)k.fill, (A)k.fill, (A)k.fill};
             if (alpha) {
@@ -204,6 +216,13 @@ BSVD_HD void planar_to_rgb_item(const float *src, uint8_t *dst, const void *alph
         }
     }
     store_codes<F>(dst + it.f * g.fstride, g, it, code);
+}
+
+// dither off: the body as its callers of before the finish stage name it
+template <class F>
+BSVD_HD void planar_to_rgb_item(const float *src, uint8_t *dst, const void *alpha, const RgbGeom &g, const RgbEncode &k, int64_t i)
+{
+    planar_to_rgb_item<F>(src, dst, alpha, g, k, Dither{BSVD_DITHER_NONE, 0u, 0}, i);
 }
 
 }  // namespace bsvd

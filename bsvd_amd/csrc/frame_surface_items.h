@@ -13,6 +13,7 @@
 // (W is even with subsampled chroma) or of 1..3 (4:4:4), which moves as groups of 2 and 1.
 #pragma once
 #include "frame_items.h"
+#include "frame_finish_items.h"
 
 namespace bsvd {
 
@@ -234,8 +235,10 @@ BSVD_HD void yuv_to_planar_item(const uint8_t *src, float *dst, const SurfGeom &
 // encode.  src is the network's [frames][3][Hp][Wp]; only its picture rows and columns reach a sample.  A part item's float4 still lies
 // inside its row of src (Wp is a multiple of 4 at or above W); the pad values it carries end in no stored code.  4:2:0: chroma from the
 // mean over the item's two rows.  4:2:2: the same without that mean.  4:4:4: Cb and Cr of every pixel.
+// Dither (frame_finish_items.h): d joins a scaled value right before the store's clamp and rintf -- rint(clamp(t + d, lo, hi)) --, luma and
+// 4:4:4 chroma on the picture's grid, subsampled chroma on the chroma grid; with di.mode == BSVD_DITHER_NONE no value is touched.
 template <class F, int LINEAR>
-BSVD_HD void planar_to_yuv_item(const float *src, uint8_t *dst, const SurfGeom &g, const YuvEncode &k, int64_t i)
+BSVD_HD void planar_to_yuv_item(const float *src, uint8_t *dst, const SurfGeom &g, const YuvEncode &k, const Dither &di, int64_t i)
 {
     constexpr int R = F::ROWS;
     constexpr float WGT = R == 2 ? 0.5f : 1.0f;
@@ -266,10 +269,18 @@ BSVD_HD void planar_to_yuv_item(const float *src, uint8_t *dst, const SurfGeom &
         }
     }
     uint8_t *fr = dst + it.f * g.fstride;
+    if (di.mode != BSVD_DITHER_NONE) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) dither_add<4>(di, it.f, 0, it.row + r, it.x0, yv[r]);
+    }
     if constexpr (F::SUB == BSVD_SUB_444) {
         float cb[4], cr[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) { cb[q] = fmaf(db[q + 1], k.cb_mul, k.c_off); cr[q] = fmaf(dr[q + 1], k.cr_mul, k.c_off); }
+        if (di.mode != BSVD_DITHER_NONE) {
+            dither_add<4>(di, it.f, 1, it.row, it.x0, cb);
+            dither_add<4>(di, it.f, 2, it.row, it.x0, cr);
+        }
         if (it.n == 4) {
             store_luma<F, 4>(fr, g, k, it.row, it.x0, yv[0]);
             store_chroma<F, 4>(fr, g, k, it.row, it.x0, cb, cr);
@@ -295,6 +306,10 @@ BSVD_HD void planar_to_yuv_item(const float *src, uint8_t *dst, const SurfGeom &
             cr[p] = fmaf(mr, k.cr_mul, k.c_off);
         }
         const int ci = it.x0 >> 1, crow = F::SUB == BSVD_SUB_420 ? it.row >> 1 : it.row;
+        if (di.mode != BSVD_DITHER_NONE) {
+            dither_add<2>(di, it.f, 1, crow, ci, cb);
+            dither_add<2>(di, it.f, 2, crow, ci, cr);
+        }
         if constexpr (F::PACKED) {
             if (it.n == 4) store_packed<F, 4>(fr, g, k, it.row, it.x0, yv[0], cb, cr);
             else store_packed<F, 2>(fr, g, k, it.row, it.x0, yv[0], cb, cr);
@@ -308,6 +323,13 @@ BSVD_HD void planar_to_yuv_item(const float *src, uint8_t *dst, const SurfGeom &
             store_chroma<F, 1>(fr, g, k, crow, ci, cb, cr);
         }
     }
+}
+
+// dither off: the body as its callers of before the finish stage name it
+template <class F, int LINEAR>
+BSVD_HD void planar_to_yuv_item(const float *src, uint8_t *dst, const SurfGeom &g, const YuvEncode &k, int64_t i)
+{
+    planar_to_yuv_item<F, LINEAR>(src, dst, g, k, Dither{BSVD_DITHER_NONE, 0u, 0}, i);
 }
 
 }  // namespace bsvd

@@ -19,10 +19,10 @@ __global__ __launch_bounds__(256) void yuv_to_planar_kernel(const uint8_t *__res
 }
 
 template <class F, int LINEAR>
-__global__ __launch_bounds__(256) void planar_to_yuv_kernel(const float *__restrict__ src, uint8_t *__restrict__ dst, SurfGeom g, YuvEncode k, int64_t items)
+__global__ __launch_bounds__(256) void planar_to_yuv_kernel(const float *__restrict__ src, uint8_t *__restrict__ dst, SurfGeom g, YuvEncode k, Dither di, int64_t items)
 {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < items; i += (int64_t)gridDim.x * blockDim.x)
-        planar_to_yuv_item<F, LINEAR>(src, dst, g, k, i);
+        planar_to_yuv_item<F, LINEAR>(src, dst, g, k, di, i);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -44,7 +44,7 @@ enum { FMT_NV12 = 10, N_FORMATS = 12 };
 static_assert(BSVD_PIX_NV12 == 0 && BSVD_PIX_P010 == 1, "FMT_NV12 + pix_fmt indexes the last two table rows");
 
 using DecodeKernel = void (*)(const uint8_t *, float *, SurfGeom, YuvDecode, int64_t);
-using EncodeKernel = void (*)(const float *, uint8_t *, SurfGeom, YuvEncode, int64_t);
+using EncodeKernel = void (*)(const float *, uint8_t *, SurfGeom, YuvEncode, Dither, int64_t);
 // [format][chroma]; 4:4:4 has no filter: one kernel for both values
 #define BSVD_FMT_ROW(K, F) {K<F, 0>, K<F, 1>}
 #define BSVD_FMT_ROW444(K, F) {K<F, 0>, K<F, 0>}
@@ -151,9 +151,12 @@ static int launch_decode(const char *fn, SurfPlan &p, const void *src, float *ds
     return launch_sweep(kDecode[p.fmt][p.chroma], p.items, stream, (const uint8_t *)src, dst, p.g, decode_constants(p.bits, p.matrix, p.full_range), p.items);
 }
 
-static int launch_encode(const SurfPlan &p, const float *src, void *dst, void *stream)
+// dither == NULL: off (the entry points without a BsvdDither).  Checked after the call's other arguments.
+static int launch_encode(const char *fn, const SurfPlan &p, const float *src, void *dst, const BsvdDither *dither, void *stream)
 {
-    return launch_sweep(kEncode[p.fmt][p.chroma], p.items, stream, src, (uint8_t *)dst, p.g, encode_constants(p.bits, p.matrix, p.full_range), p.items);
+    Dither di;
+    if (dither_check(fn, dither, &di)) return -3;
+    return launch_sweep(kEncode[p.fmt][p.chroma], p.items, stream, src, (uint8_t *)dst, p.g, encode_constants(p.bits, p.matrix, p.full_range), di, p.items);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -260,11 +263,11 @@ static int decode(const char *fn, const void *src, float *dst, int32_t frames, i
 }
 
 static int encode(const char *fn, const float *src, void *dst, int32_t frames, int32_t H, int32_t W, int pad, int32_t Hp, int32_t Wp,
-                  const BsvdYuvSurface *s, void *stream)
+                  const BsvdYuvSurface *s, const BsvdDither *dither, void *stream)
 {
     SurfPlan p;
     const int rc = yuv_surface_check({fn, dst, "dst", src, "src", frames, H, W, pad, Hp, Wp}, s, &p);
-    return rc ? rc : launch_encode(p, src, dst, stream);
+    return rc ? rc : launch_encode(fn, p, src, dst, dither, stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -326,11 +329,11 @@ static int decode420(const char *fn, const void *src, float *dst, int32_t frames
 }
 
 static int encode420(const char *fn, const float *src, void *dst, int32_t frames, int32_t H, int32_t W, int pad, int32_t Hp, int32_t Wp,
-                     const BsvdYuvDesc *d, void *stream)
+                     const BsvdYuvDesc *d, const BsvdDither *dither, void *stream)
 {
     SurfPlan p;
     const int rc = yuv420_check({fn, dst, "dst", src, "src", frames, H, W, pad, Hp, Wp}, d, &p);
-    return rc ? rc : launch_encode(p, src, dst, stream);
+    return rc ? rc : launch_encode(fn, p, src, dst, dither, stream);
 }
 
 }  // namespace bsvd
@@ -355,7 +358,7 @@ int bsvd_yuv_to_planar(const void *src, float *dst, int32_t frames, int32_t H, i
 
 int bsvd_planar_to_yuv(const float *src, void *dst, int32_t frames, int32_t H, int32_t W, const BsvdYuvSurface *surface, void *stream)
 {
-    return encode("bsvd_planar_to_yuv", src, dst, frames, H, W, 0, 0, 0, surface, stream);
+    return encode("bsvd_planar_to_yuv", src, dst, frames, H, W, 0, 0, 0, surface, nullptr, stream);
 }
 
 int bsvd_yuv_to_planar_pad(const void *src, float *dst, int32_t frames, int32_t H, int32_t W, int32_t Hp, int32_t Wp, const BsvdYuvSurface *surface,
@@ -367,7 +370,14 @@ int bsvd_yuv_to_planar_pad(const void *src, float *dst, int32_t frames, int32_t 
 int bsvd_planar_to_yuv_crop(const float *src, void *dst, int32_t frames, int32_t Hp, int32_t Wp, int32_t H, int32_t W, const BsvdYuvSurface *surface,
                             void *stream)
 {
-    return encode("bsvd_planar_to_yuv_crop", src, dst, frames, H, W, 1, Hp, Wp, surface, stream);
+    return encode("bsvd_planar_to_yuv_crop", src, dst, frames, H, W, 1, Hp, Wp, surface, nullptr, stream);
+}
+
+int bsvd_planar_to_yuv_crop_d(const float *src, void *dst, int32_t frames, int32_t Hp, int32_t Wp, int32_t H, int32_t W, const BsvdYuvSurface *surface,
+                              const BsvdDither *dither, void *stream)
+{
+    if (!dither) { set_error("bsvd_planar_to_yuv_crop_d: dither is NULL"); return -3; }
+    return encode("bsvd_planar_to_yuv_crop_d", src, dst, frames, H, W, 1, Hp, Wp, surface, dither, stream);
 }
 
 int64_t bsvd_yuv420_frame_bytes(int32_t H, int32_t W, int32_t pix_fmt, int32_t row_pitch) { return yuv_bytes(H, W, pix_fmt, row_pitch, 3); }
@@ -381,7 +391,7 @@ int bsvd_yuv420_to_planar(const void *src, float *dst, int32_t frames, int32_t H
 
 int bsvd_planar_to_yuv420(const float *src, void *dst, int32_t frames, int32_t H, int32_t W, const BsvdYuvDesc *desc, void *stream)
 {
-    return encode420("bsvd_planar_to_yuv420", src, dst, frames, H, W, 0, 0, 0, desc, stream);
+    return encode420("bsvd_planar_to_yuv420", src, dst, frames, H, W, 0, 0, 0, desc, nullptr, stream);
 }
 
 int bsvd_yuv420_to_planar_pad(const void *src, float *dst, int32_t frames, int32_t H, int32_t W, int32_t Hp, int32_t Wp, const BsvdYuvDesc *desc,
@@ -393,7 +403,14 @@ int bsvd_yuv420_to_planar_pad(const void *src, float *dst, int32_t frames, int32
 int bsvd_planar_to_yuv420_crop(const float *src, void *dst, int32_t frames, int32_t Hp, int32_t Wp, int32_t H, int32_t W, const BsvdYuvDesc *desc,
                                void *stream)
 {
-    return encode420("bsvd_planar_to_yuv420_crop", src, dst, frames, H, W, 1, Hp, Wp, desc, stream);
+    return encode420("bsvd_planar_to_yuv420_crop", src, dst, frames, H, W, 1, Hp, Wp, desc, nullptr, stream);
+}
+
+int bsvd_planar_to_yuv420_crop_d(const float *src, void *dst, int32_t frames, int32_t Hp, int32_t Wp, int32_t H, int32_t W, const BsvdYuvDesc *desc,
+                                 const BsvdDither *dither, void *stream)
+{
+    if (!dither) { set_error("bsvd_planar_to_yuv420_crop_d: dither is NULL"); return -3; }
+    return encode420("bsvd_planar_to_yuv420_crop_d", src, dst, frames, H, W, 1, Hp, Wp, desc, dither, stream);
 }
 
 }  // extern "C"

@@ -25,7 +25,11 @@ for it), a sequence of per-frame values, or a device tensor [T].
 
 Scene cuts: ``scene_scores`` (a 16 x 16 block grid of 8-bit luma sums per frame and its frame-to-frame difference, on the device, in
 integers) and ``scene_cuts`` (the rule on top, on the host) find the frames that start a new scene, for the ``cuts=`` / ``cut=`` arguments of
-the model's forward functions.  Untested on real footage."""
+the model's forward functions.  Untested on real footage.
+
+The output finish: ``blend_output`` (the denoise strength: the network's result blended with its input, separate luma and chroma amounts,
+in place, with exact ends) and ``dither=`` on ``output_to_yuv420`` / ``output_to_yuv`` / ``output_to_rgb`` (ordered or random dither at the
+quantiser; a whole code is never moved) -- include/bsvd_hip.h, bsvd_blend_planar / BsvdDither.  The defaults call what was called before."""
 import ctypes
 
 import torch
@@ -259,6 +263,84 @@ def scene_cuts(x, threshold=CUT_THRESHOLD, picture=None):
     return [t for t, s in enumerate(score) if s >= threshold]
 
 
+# ---------------------------------------------------------------------------------------------------
+# the output finish: denoise strength and dither (include/bsvd_hip.h, bsvd_blend_planar / BsvdDither)
+
+DITHERS = (None, "ordered", "random")
+
+
+def check_strength(strength):
+    """``strength``: a number or a pair (luma, chroma), each in [0, 1] -> (s_luma, s_chroma) floats; ValueError otherwise"""
+    try:
+        if isinstance(strength, (tuple, list)):
+            sl, sc = strength
+        else:
+            sl = sc = strength
+        sl, sc = float(sl), float(sc)
+    except (TypeError, ValueError):
+        raise ValueError("strength: expected a number or a pair (luma, chroma), got %r" % (strength,)) from None
+    if not (0.0 <= sl <= 1.0 and 0.0 <= sc <= 1.0):
+        raise ValueError("strength %r: 0 <= strength <= 1 (1 = the network's result, 0 = the source), both finite" % (strength,))
+    return sl, sc
+
+
+def check_dither(dither, dither_seed=0, frame0=0):
+    """``dither`` None | 'ordered' | 'random', ``dither_seed`` in [0, 2^32), ``frame0`` >= 0 -> (mode, seed, frame0); ValueError otherwise"""
+    if dither is not None and not (isinstance(dither, str) and dither in DITHERS):
+        raise ValueError("dither %r: None, 'ordered' or 'random'" % (dither,))
+    try:
+        seed, f0 = int(dither_seed), int(frame0)
+    except (TypeError, ValueError):
+        raise ValueError("dither_seed / frame0: expected ints, got %r / %r" % (dither_seed, frame0)) from None
+    if not 0 <= seed < 2 ** 32:
+        raise ValueError("dither_seed %r: 0 <= seed < 2^32" % (dither_seed,))
+    if not 0 <= f0 < 2 ** 62:
+        raise ValueError("frame0 %r: the stream index of the first frame, not negative" % (frame0,))
+    return _lib.DITHER[dither], seed, f0
+
+
+def _dither_struct(dither, dither_seed, frame0):
+    """-> a BsvdDither, or None with dither off (the existing entry point is called then)"""
+    mode, seed, f0 = check_dither(dither, dither_seed, frame0)
+    return _lib.BsvdDither(mode=mode, seed=seed, frame0=f0) if mode else None
+
+
+def _luma_weights(matrix):
+    """``matrix``: a name of ``_lib.MATRIX`` or three weights (Kr, Kg, Kb) in [0, 1] -> a ctypes float[3]"""
+    if isinstance(matrix, str):
+        if matrix not in _lib.LUMA_WEIGHTS:
+            raise ValueError("matrix %r: one of %s, or three weights (Kr, Kg, Kb)" % (matrix, ", ".join(sorted(_lib.LUMA_WEIGHTS))))
+        w = _lib.LUMA_WEIGHTS[matrix]
+    else:
+        try:
+            w = tuple(float(v) for v in matrix)
+        except (TypeError, ValueError):
+            raise ValueError("matrix: a name of %s or three weights (Kr, Kg, Kb), got %r" % (sorted(_lib.LUMA_WEIGHTS), matrix)) from None
+        if len(w) != 3 or not all(0.0 <= v <= 1.0 for v in w):
+            raise ValueError("matrix %r: three weights (Kr, Kg, Kb), each in [0, 1]" % (matrix,))
+    return (ctypes.c_float * 3)(*w)
+
+
+def blend_output(y, x, strength, matrix="bt709"):
+    """The denoise strength, in place on ``y``: y fp32 device tensor [T,3,Hp,Wp] (the network's output), x fp32 [T,3(+1),Hp,Wp] (the input
+    it came from; only its first three planes are read).  ``strength``: a number or (luma, chroma), each in [0, 1]: 1 keeps the network's
+    result, 0 returns the source; chroma mixes R, G and B alike, and luma moves the result along the luma of the removed noise (weights:
+    the Kr, Kg, Kb of ``matrix``, a name or three numbers).  The ends are exact: (1, 1) leaves ``y``'s bits, (0, 0) gives ``x``'s.
+    Returns ``y``.  (include/bsvd_hip.h, bsvd_blend_planar, states the arithmetic.)"""
+    sl, sc = check_strength(strength)
+    w = _luma_weights(matrix)
+    _planes(y, "blend_output(y)")
+    _planes(x, "blend_output(x)")
+    if y.shape[1] != 3 or x.shape[1] < 3 or x.shape[0] != y.shape[0] or x.shape[2:] != y.shape[2:] or x.device != y.device:
+        raise ValueError("blend_output: y [T,3,Hp,Wp] and x [T,3(+1),Hp,Wp] on one device, got %s and %s" % (tuple(y.shape), tuple(x.shape)))
+    lib = require_hip()
+    T, _, Hp, Wp = y.shape
+    with torch.cuda.device(y.device):
+        _lib.check(lib.bsvd_blend_planar(y.data_ptr(), 3 * Hp * Wp, x.data_ptr(), x.shape[1] * Hp * Wp, T, Hp, Wp, sl, sc, w, _stream()),
+                   "bsvd_blend_planar")
+    return y
+
+
 def frames_to_input(frames_u8, sigma=None, hwc=True, pad_to=None, sigma_gain=1.0):
     """frames_u8: uint8 device tensor [T,H,W,3] (hwc) or [T,3,H,W] -> fp32 [T,3(+1),H,W] in [0,1]; with ``sigma`` (noise
     std in [0,1] units, e.g. 30/255) a constant noise-map channel is appended.  ``pad_to=(Hp, Wp)``: the result is [T,3(+1),Hp,Wp],
@@ -384,12 +466,16 @@ def yuv420_to_input(buf, H, W, pix_fmt="nv12", matrix="bt709", full_range=False,
     return y
 
 
-def output_to_yuv420(y, pix_fmt="nv12", matrix="bt709", full_range=False, chroma="linear", row_pitch=None, out=None, crop_to=None):
+def output_to_yuv420(y, pix_fmt="nv12", matrix="bt709", full_range=False, chroma="linear", row_pitch=None, out=None, crop_to=None,
+                     dither=None, dither_seed=0, frame0=0):
     """y: fp32 device tensor [T,3,H,W] RGB -> uint8 [T, frame_bytes] NV12 / P010 frames: clamp [0,1], matrix, chroma downsampling
     ('nearest': mean of the 2x2 block; 'linear': rows averaged, [1 2 1]/4 over columns), scale, clamp to the legal codes, round half
     to even.  ``out``: the caller's buffer [T, >= frame_bytes] to write into -- pitch padding and the bytes between frames are left
     as they were; without it the result's padding is zero.  ``crop_to=(H, W)`` (even): the surfaces, H x W, of ``y[..., :H, :W]``; the
-    rows and columns of ``y`` beyond reach no sample."""
+    rows and columns of ``y`` beyond reach no sample.  ``dither`` None | 'ordered' | 'random': a value in (-0.5, 0.5) code joins every
+    scaled Y, Cb and Cr right before the clamp and the rounding (8 x 8 Bayer, static; or a hash of ``dither_seed``, the frame's stream index
+    ``frame0 + t``, the component and the position) -- a whole code is never moved (include/bsvd_hip.h, BsvdDither)."""
+    dith = _dither_struct(dither, dither_seed, frame0)
     if y.dtype != torch.float32 or not y.is_cuda or y.dim() != 4 or y.shape[1] != 3:
         raise ValueError("expected a float32 device tensor [T,3,H,W]")
     T, _, H, W = y.shape
@@ -405,7 +491,10 @@ def output_to_yuv420(y, pix_fmt="nv12", matrix="bt709", full_range=False, chroma
         raise ValueError("output_to_yuv420: out is on %s, y on %s" % (out.device, y.device))
     desc.frame_stride = _surface_buffer(out, T, nbytes, pix_fmt == "p010", "output_to_yuv420(out=)", "P010", "p010")
     with torch.cuda.device(y.device):
-        if crop_to is not None:
+        if dith is not None:
+            _lib.check(lib.bsvd_planar_to_yuv420_crop_d(y.data_ptr(), out.data_ptr(), T, Hp, Wp, H, W, ctypes.byref(desc), ctypes.byref(dith),
+                                                        _stream()), "bsvd_planar_to_yuv420_crop_d")
+        elif crop_to is not None:
             _lib.check(lib.bsvd_planar_to_yuv420_crop(y.data_ptr(), out.data_ptr(), T, Hp, Wp, H, W, ctypes.byref(desc), _stream()),
                        "bsvd_planar_to_yuv420_crop")
         else:
@@ -499,11 +588,14 @@ def yuv_to_input(buf, H, W, pix_fmt="yuv420p", matrix="bt709", full_range=False,
     return y
 
 
-def output_to_yuv(y, pix_fmt="yuv420p", matrix="bt709", full_range=False, chroma="linear", pitches=None, out=None, crop_to=None, offsets=None):
+def output_to_yuv(y, pix_fmt="yuv420p", matrix="bt709", full_range=False, chroma="linear", pitches=None, out=None, crop_to=None, offsets=None,
+                  dither=None, dither_seed=0, frame0=0):
     """``output_to_yuv420`` for the planar, 4:2:2 and 4:4:4 surfaces: y fp32 device tensor [T,3,H,W] RGB -> uint8 [T, frame_bytes].
     4:2:2 chroma is filtered along the row only ('nearest': mean of the two columns; 'linear': [1 2 1]/4), 4:4:4 not at all.  ``out``: the
     caller's buffer [T, >= frame_bytes] -- pitch padding, the bytes between planes and between frames are left as they were; without it
-    the result's padding is zero.  ``crop_to=(H, W)``: the surfaces of ``y[..., :H, :W]``."""
+    the result's padding is zero.  ``crop_to=(H, W)``: the surfaces of ``y[..., :H, :W]``.  ``dither`` / ``dither_seed`` / ``frame0``: as for
+    ``output_to_yuv420``; subsampled chroma is dithered on the chroma grid."""
+    dith = _dither_struct(dither, dither_seed, frame0)
     if y.dtype != torch.float32 or not y.is_cuda or y.dim() != 4 or y.shape[1] != 3:
         raise ValueError("expected a float32 device tensor [T,3,H,W]")
     T, _, H, W = y.shape
@@ -519,7 +611,10 @@ def output_to_yuv(y, pix_fmt="yuv420p", matrix="bt709", full_range=False, chroma
         raise ValueError("output_to_yuv: out is on %s, y on %s" % (out.device, y.device))
     surf.frame_stride = _surface_buffer(out, T, nbytes, surf.bits > 8, "output_to_yuv(out=)")
     with torch.cuda.device(y.device):
-        if crop_to is not None:
+        if dith is not None:
+            _lib.check(lib.bsvd_planar_to_yuv_crop_d(y.data_ptr(), out.data_ptr(), T, Hp, Wp, H, W, ctypes.byref(surf), ctypes.byref(dith),
+                                                     _stream()), "bsvd_planar_to_yuv_crop_d")
+        elif crop_to is not None:
             _lib.check(lib.bsvd_planar_to_yuv_crop(y.data_ptr(), out.data_ptr(), T, Hp, Wp, H, W, ctypes.byref(surf), _stream()),
                        "bsvd_planar_to_yuv_crop")
         else:
@@ -633,12 +728,15 @@ def rgb_to_input(buf, H, W, pix_fmt, full_range=True, sigma=None, pitches=None, 
     return y if alpha is None else (y, alpha)
 
 
-def output_to_rgb(y, pix_fmt, full_range=True, pitches=None, offsets=None, out=None, crop_to=None, alpha=None):
+def output_to_rgb(y, pix_fmt, full_range=True, pitches=None, offsets=None, out=None, crop_to=None, alpha=None, dither=None, dither_seed=0,
+                  frame0=0):
     """y: fp32 device tensor [T,3,H,W] (R, G, B) -> uint8 [T, frame_bytes] RGB surfaces: clamp [0,1], scale (+ 16 s at limited range), round
     half to even.  A filler sample is written as all ones.  ``alpha`` (formats with alpha): the codes to write, a device tensor [T,H,W]
     (uint8, uint16 above 8 bits; picture-sized also with ``crop_to``) -- what ``rgb_to_input(return_alpha=True)`` gave; None: the maximum
     code, opaque.  ``out``: the caller's buffer [T, >= frame_bytes] -- pitch padding, the bytes between planes and between frames are left
-    as they were; without it the result's padding is zero.  ``crop_to=(H, W)``: the surfaces of ``y[..., :H, :W]``."""
+    as they were; without it the result's padding is zero.  ``crop_to=(H, W)``: the surfaces of ``y[..., :H, :W]``.  ``dither`` /
+    ``dither_seed`` / ``frame0``: as for ``output_to_yuv420``, on R, G and B before the rounding; alpha and fillers are never dithered."""
+    dith = _dither_struct(dither, dither_seed, frame0)
     if alpha is not None and not rgb_has_alpha(pix_fmt):
         raise ValueError("output_to_rgb(alpha=): pix_fmt %r carries no alpha" % (pix_fmt,))
     rgb_planes(pix_fmt)
@@ -657,6 +755,10 @@ def output_to_rgb(y, pix_fmt, full_range=True, pitches=None, offsets=None, out=N
         raise ValueError("output_to_rgb: out is on %s, y on %s" % (out.device, y.device))
     surf.frame_stride = _surface_buffer(out, T, nbytes, surf.bits > 8, "output_to_rgb(out=)", "16-bit", "16-bit")
     with torch.cuda.device(y.device):
-        _lib.check(lib.bsvd_planar_to_rgb(y.data_ptr(), out.data_ptr(), T, Hp, Wp, H, W, ctypes.byref(surf),
-                                          None if alpha is None else alpha.data_ptr(), _stream()), "bsvd_planar_to_rgb")
+        if dith is not None:
+            _lib.check(lib.bsvd_planar_to_rgb_d(y.data_ptr(), out.data_ptr(), T, Hp, Wp, H, W, ctypes.byref(surf),
+                                                None if alpha is None else alpha.data_ptr(), ctypes.byref(dith), _stream()), "bsvd_planar_to_rgb_d")
+        else:
+            _lib.check(lib.bsvd_planar_to_rgb(y.data_ptr(), out.data_ptr(), T, Hp, Wp, H, W, ctypes.byref(surf),
+                                              None if alpha is None else alpha.data_ptr(), _stream()), "bsvd_planar_to_rgb")
     return out

@@ -47,7 +47,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .frame_io import (CUT_THRESHOLD, _check_gain, _sigma_mode, _yuv_desc, _yuv_surface, check_cut_threshold, cut_scores, frames_to_input, network_size,
+from .frame_io import (CUT_THRESHOLD, _check_gain, _luma_weights, _sigma_mode, _yuv_desc, _yuv_surface, blend_output, check_cut_threshold, check_dither,
+                       check_strength, cut_scores, frames_to_input, network_size,
                        output_to_frames, output_to_rgb, output_to_yuv, output_to_yuv420, rgb_frame_bytes, rgb_to_input, scene_cuts, scene_scores,
                        yuv420_frame_bytes, yuv420_picture_bytes, yuv420_to_input, yuv_to_input)
 
@@ -100,8 +101,12 @@ class _Rgb24:
     def to_input(self, dev_in, geom, sigma, sigma_gain=1.0):
         return frames_to_input(dev_in, sigma, pad_to=(geom.net_h, geom.net_w) if self.pad else None, sigma_gain=sigma_gain)
 
-    def to_output(self, y, geom):
-        return output_to_frames(y, crop_to=(geom.h, geom.w) if self.pad else None)
+    def to_output(self, y, geom, **dither):
+        if dither.get("dither") is None:
+            return output_to_frames(y, crop_to=(geom.h, geom.w) if self.pad else None)
+        # dither: the RGB surface kernel, which gives the uint8 kernel's bits with dither off (the uint8 kernels have no dithered form)
+        out = output_to_rgb(y, "rgb24", crop_to=(geom.h, geom.w) if self.pad else None, **dither)
+        return out.view(y.shape[0], geom.h, geom.w, 3)
 
 
 def _as_colour(colour):
@@ -152,8 +157,8 @@ class _Yuv420:
         return yuv420_to_input(dev_in, geom.h, geom.w, sigma=sigma, row_pitch=geom.row_pitch,
                                pad_to=(geom.net_h, geom.net_w) if self.pad else None, sigma_gain=sigma_gain, **self.kw)
 
-    def to_output(self, y, geom):
-        return output_to_yuv420(y, row_pitch=geom.row_pitch, crop_to=(geom.h, geom.w) if self.pad else None, **self.kw)
+    def to_output(self, y, geom, **dither):
+        return output_to_yuv420(y, row_pitch=geom.row_pitch, crop_to=(geom.h, geom.w) if self.pad else None, **self.kw, **dither)
 
 
 class _YuvSurface:
@@ -190,8 +195,8 @@ class _YuvSurface:
         return yuv_to_input(dev_in, geom.h, geom.w, sigma=sigma, pad_to=(geom.net_h, geom.net_w) if self.pad else None,
                             sigma_gain=sigma_gain, **self.kw)
 
-    def to_output(self, y, geom):
-        return output_to_yuv(y, crop_to=(geom.h, geom.w) if self.pad else None, **self.kw)
+    def to_output(self, y, geom, **dither):
+        return output_to_yuv(y, crop_to=(geom.h, geom.w) if self.pad else None, **self.kw, **dither)
 
 
 class _RgbSurface:
@@ -265,8 +270,8 @@ class _RgbSurface:
         return rgb_to_input(dev_in, geom.h, geom.w, self.pix_fmt, full_range=self.full_range, sigma=sigma, sigma_gain=sigma_gain,
                             pad_to=(geom.net_h, geom.net_w) if self.pad else None, return_alpha=False if alpha is None else alpha)
 
-    def to_output(self, y, geom, alpha=None):
-        return output_to_rgb(y, self.pix_fmt, full_range=self.full_range, crop_to=(geom.h, geom.w) if self.pad else None, alpha=alpha)
+    def to_output(self, y, geom, alpha=None, **dither):
+        return output_to_rgb(y, self.pix_fmt, full_range=self.full_range, crop_to=(geom.h, geom.w) if self.pad else None, alpha=alpha, **dither)
 
 
 class _AlphaRing:
@@ -290,6 +295,56 @@ class _AlphaRing:
 
     def reset(self):
         self.fed = self.emitted = 0
+
+
+class _SourceRing:
+    """LiveStream's source frames, for ``strength`` below 1: frame k's three colour planes at network size wait on the device while frame k
+    is inside the network, as the alpha codes do in ``_AlphaRing`` and by the same bookkeeping -- ``frames`` slots (>= latency + depth),
+    written in feed order by the decode's side, read in the same order when the frames come out.  3 fp32 planes per slot, allocated once
+    with the slots.  A slot is [1,3,Hp,Wp]: what ``frame_io.blend_output`` takes as ``x``."""
+
+    def __init__(self, frames, h, w, device):
+        self.buf = torch.empty((frames, 1, 3, h, w), dtype=torch.float32, device=device)
+        self.fed = self.emitted = 0
+
+    def next_in(self):
+        self.fed += 1
+        return self.buf[(self.fed - 1) % self.buf.shape[0]]
+
+    def next_out(self):
+        if self.emitted >= self.fed:
+            raise RuntimeError("source ring: frame %d comes out before it went in" % self.emitted)
+        self.emitted += 1
+        return self.buf[(self.emitted - 1) % self.buf.shape[0]]
+
+    def reset(self):
+        self.fed = self.emitted = 0
+
+
+class _Finish:
+    """the pipelines' output finish: ``strength`` (a number or (luma, chroma)), ``dither`` / ``dither_seed``, the luma weights of the blend
+    (``luma_matrix``: None = the stream's matrix for YUV formats, BT.709 for RGB ones).  Checked before anything touches a device.  With
+    the defaults ``blends`` is False and ``dither_kw`` empty: no kernel, no buffer and no argument more than before."""
+
+    def __init__(self, fmt, strength, dither, dither_seed, luma_matrix):
+        self.strength = check_strength(strength)
+        self.blends = self.strength != (1.0, 1.0)
+        check_dither(dither, dither_seed)
+        self.dither, self.seed = dither, int(dither_seed)
+        colour = getattr(fmt, "colour", None)
+        self.matrix = luma_matrix if luma_matrix is not None else colour.matrix if isinstance(colour, Colour) else "bt709"
+        _luma_weights(self.matrix)
+        self.emitted = 0                   # frames handed to the encoder since construction / the last flush: the dither's stream index
+
+    def blend(self, y, x):
+        return blend_output(y, x, self.strength, self.matrix)
+
+    def dither_kw(self, frames):
+        """the encoder's keywords for the next ``frames`` frames"""
+        if self.dither is None:
+            return {}
+        f0, self.emitted = self.emitted, self.emitted + frames
+        return dict(dither=self.dither, dither_seed=self.seed, frame0=f0)
 
 
 def _pixel_format(pix_fmt, colour, pad=None, frame_shape=None):
@@ -368,16 +423,22 @@ class ClipPipeline:
     cuts='auto': the scene starts of every clip are detected on the device (``frame_io.scene_cuts`` at ``cut_threshold``; its docstring says
     what is known about the rule -- nothing on real footage -- and its blind spot: a cut one or two frames after another scores low) and
     handed to the model's forward, which runs every scene as a clip of its own.  The detection reads T integers back before the forward is
-    enqueued: the host waits for the clip's upload and conversion there.  ``last_cuts``: the cuts of the most recent clip submitted."""
+    enqueued: the host waits for the clip's upload and conversion there.  ``last_cuts``: the cuts of the most recent clip submitted.
+    strength (a number or (luma, chroma), each in [0, 1]; default 1): how much of the denoising to keep -- the network's result is blended
+    with the clip's own input on the device before it is encoded (``frame_io.blend_output``; luma weights: the stream's matrix, BT.709 for
+    RGB formats, or ``luma_matrix``).  dither None | 'ordered' | 'random' with dither_seed: dither at the encoder's quantiser
+    (``frame_io.output_to_*``); the random pattern's frame index counts the frames submitted since construction.  The defaults launch
+    nothing new and give the bytes they gave."""
 
     def __init__(self, model, sigma=None, depth=2, pix_fmt="rgb24", colour=None, pad=None, frame_shape=None, sigma_gain=1.0, cuts=None,
-                 cut_threshold=CUT_THRESHOLD):
+                 cut_threshold=CUT_THRESHOLD, strength=1.0, dither=None, dither_seed=0, luma_matrix=None):
         if depth < 1:
             raise ValueError("depth must be >= 1")
         self.auto_cuts, self.cut_threshold = _check_cuts_mode(cuts, cut_threshold, "ClipPipeline")
         self.last_cuts = None
         self.sigma_gain = _check_sigma(model, sigma, sigma_gain, "ClipPipeline")
         self.fmt = _pixel_format(pix_fmt, colour, pad, frame_shape)
+        self.finish = _Finish(self.fmt, strength, dither, dither_seed, luma_matrix)
         self.alpha = getattr(self.fmt, "has_alpha", False)       # the clip's alpha codes ride beside the clip, [T,H,W] on the device
         self.model, self.sigma = model, sigma
         self.device = model._device()
@@ -424,8 +485,12 @@ class ClipPipeline:
                     y = self.model.clip_forward(x, **kw)
                 else:
                     y = self.model.streaming_forward(x, **kw)
+                y = y.float()
+                if self.finish.blends:
+                    y = self.finish.blend(y.contiguous(), x)
+                kw = self.finish.dither_kw(T)
                 # held by the slot until its download completed
-                slot.dev_out = self.fmt.to_output(y.float(), geom, alpha=slot.dev_alpha) if self.alpha else self.fmt.to_output(y.float(), geom)
+                slot.dev_out = self.fmt.to_output(y, geom, alpha=slot.dev_alpha, **kw) if self.alpha else self.fmt.to_output(y, geom, **kw)
                 slot.computed.record()
             with torch.cuda.stream(self.down):
                 self.down.wait_event(slot.computed)
@@ -501,10 +566,17 @@ class LiveStream:
     (``frame_io.scene_cuts``' rule, carried from frame to frame) reaches ``cut_threshold`` starts a scene.  ``last_cut_score`` /
     ``last_cut``: score and decision of the most recent frame fed.  ``flush()`` forgets the previous frame.  With cuts=None the stream order
     is what it always was.  Nothing is known about the rule on real footage, the default threshold has met none, and a cut one or two
-    frames after another cut scores low (``frame_io.scene_cuts``)."""
+    frames after another cut scores low (``frame_io.scene_cuts``).
+
+    strength (a number or (luma, chroma), each in [0, 1]; default 1) and dither None | 'ordered' | 'random' with dither_seed: the output
+    finish, on the device.  Frame k's source -- its three colour planes at network size -- waits in a ring of ``latency + depth`` slots
+    (3 fp32 planes each: about 0.5 GB at 1080p) and is blended with frame k's result when that emerges ``latency`` feeds later
+    (``frame_io.blend_output``), through ``cut=True`` and ``flush()`` like the alpha ring; the ring exists only when some strength is
+    below 1, and nothing is allocated per feed.  The random dither's frame index counts the frames emitted since construction or the last
+    ``flush()``.  The defaults launch nothing new and give the bytes they gave."""
 
     def __init__(self, model, sigma=None, depth=2, overlap_blocks=None, frame_shape=None, pix_fmt="rgb24", colour=None, pad=None,
-                 sigma_gain=1.0, cuts=None, cut_threshold=CUT_THRESHOLD):
+                 sigma_gain=1.0, cuts=None, cut_threshold=CUT_THRESHOLD, strength=1.0, dither=None, dither_seed=0, luma_matrix=None):
         """frame_shape: optional (H, W) of the frames to come (the picture, also with ``pad``) -- the overlap decision (and with it
         ``latency``) is then final at construction instead of at the first feed."""
         if depth < 1:
@@ -518,6 +590,8 @@ class LiveStream:
         self.last_sigma = None
         self.fmt = _pixel_format(pix_fmt, colour, pad, frame_shape)
         self._alpha = None                                    # formats with alpha: the ring of alpha planes (_AlphaRing), allocated with the slots
+        self.finish = _Finish(self.fmt, strength, dither, dither_seed, luma_matrix)
+        self._source = None                                   # strength < 1: the ring of source frames (_SourceRing), allocated with the slots
         self.model, self.sigma, self.depth = model, sigma, depth
         self._overlap_wanted = (depth >= 2) if overlap_blocks is None else bool(overlap_blocks)
         self._overlap_explicit = overlap_blocks is not None
@@ -580,6 +654,7 @@ class LiveStream:
             self.slots.append(s)
         if getattr(self.fmt, "has_alpha", False):
             self._alpha = _AlphaRing(self.latency + self.depth, geom.h, geom.w, getattr(torch, self.fmt.dtype.name), self.device)
+        self._source = _SourceRing(self.latency + self.depth, geom.net_h, geom.net_w, self.device) if self.finish.blends else None
         if self.auto_cuts:
             gh, gw = geom.h // 16, geom.w // 16
             self._grids = torch.zeros((2, 1, gh, gw), dtype=torch.int32, device=self.device)
@@ -613,14 +688,22 @@ class LiveStream:
     def _to_input(self, slot):
         """the slot's frame -> the network input; a format with alpha leaves the frame's alpha codes in the ring's next plane"""
         if self._alpha is None:
-            return self.fmt.to_input(slot.dev_in, self.geom, self.sigma, self.sigma_gain)
-        return self.fmt.to_input(slot.dev_in, self.geom, self.sigma, self.sigma_gain, alpha=self._alpha.next_in())[0]
+            x = self.fmt.to_input(slot.dev_in, self.geom, self.sigma, self.sigma_gain)
+        else:
+            x = self.fmt.to_input(slot.dev_in, self.geom, self.sigma, self.sigma_gain, alpha=self._alpha.next_in())[0]
+        if self._source is not None:
+            self._source.next_in().copy_(x[:, :3])          # the frame's colour planes wait for its denoised self
+        return x
 
     def _to_output(self, y):
         """what a step emitted -> the surface; frames come out in the order they went in, and so do their alpha planes"""
+        y = y.float()
+        if self._source is not None:
+            y = self.finish.blend(y.contiguous(), self._source.next_out())
+        kw = self.finish.dither_kw(y.shape[0])
         if self._alpha is None:
-            return self.fmt.to_output(y.float(), self.geom)
-        return self.fmt.to_output(y.float(), self.geom, alpha=self._alpha.next_out())
+            return self.fmt.to_output(y, self.geom, **kw)
+        return self.fmt.to_output(y, self.geom, alpha=self._alpha.next_out(), **kw)
 
     def _pop(self):
         """oldest in-flight step -> its uint8 frame, or None if that step emitted nothing (pipeline fill)"""
@@ -704,5 +787,8 @@ class LiveStream:
         self._forget_scene()
         if self._alpha is not None:
             self._alpha.reset()
+        if self._source is not None:
+            self._source.reset()
+        self.finish.emitted = 0
         self._reopen_overlap()                        # the next stream decides again (free HBM may have changed)
         return outs

@@ -556,6 +556,61 @@ int bsvd_planar_to_rgb(const float *src, void *dst, int32_t frames, int32_t Hp, 
                        const BsvdRgbSurface *surface, const void *alpha_in, void *stream);
 
 /*
+ * The output finish: what happens between the network's [frames][3][Hp][Wp] fp32 result and the surface, on the device -- a denoise
+ * strength (bsvd_blend_planar) and dither at the quantiser (the `_d` forms of the three surface encoders).  Added without a new
+ * BSVD_ABI_VERSION: discover the four entry points by symbol (dlsym), like the YUV and RGB entry points above.  Every existing entry point
+ * is unchanged, signature and bits; the bsvd_planar_to_u8* kernels have no dithered form (rgb24 is a BsvdRgbSurface, with the same bits).
+ *
+ * bsvd_blend_planar mixes the network's output y (planes R, G, B, frames y_frame_stride ELEMENTS apart) with the input x the frames came
+ * from (its first three planes; x_frame_stride differs because x carries the noise-map plane), in place on y, over the whole Hp x Wp plane
+ * (the pad region of x holds mirror images of the picture: harmless).  s_luma / s_chroma in [0, 1]: 1 = the network's result, 0 = the
+ * source; luma_w = the Kr, Kg, Kb of the stream's matrix.  Arithmetic in fp32, no contraction, per pixel and component c:
+ *     m_c   = s_chroma * y_c + om * x_c                     two products, one sum; om = (float)(1 - s_chroma), computed once on the host
+ *     l     = fmaf(w_B, x_B - y_B, fmaf(w_G, x_G - y_G, w_R * (x_R - y_R)))
+ *     out_c = m_c + (s_chroma - s_luma) * l                 the factor is one fp32 subtraction on the host
+ * The ends are exact for finite values: s_luma = s_chroma = 1 gives y bit for bit, s_luma = s_chroma = 0 gives x bit for bit, and with
+ * s_luma == s_chroma the luma term is an exact zero (out_c = m_c).  (A value that is -0 comes out +0.)  One float4 per plane row per lane
+ * when Wp % 4 == 0, both pointers are 16-byte aligned and both strides multiples of 4; scalars otherwise; the same bits either way.
+ * Returns -3, naming the argument in bsvd_last_error(), without a device, for: a NULL y, x or luma_w; frames, Hp or Wp <= 0; a frame
+ * stride below 3 planes; a strength (or a luma weight) outside [0, 1] or not finite; a pointer that is not 4-byte aligned.
+ *
+ * Dither.  bsvd_planar_to_yuv420_crop_d, bsvd_planar_to_yuv_crop_d and bsvd_planar_to_rgb_d take the arguments of the functions they are
+ * named after plus a BsvdDither (Hp == H, Wp == W is the plain case); with mode = BSVD_DITHER_NONE they give those functions' bytes.
+ * A value d, in units of one code, joins the scaled, not yet rounded value t right before the encoder's own clamp and rintf, whose order
+ * stays what it is: YUV rint(clamp(t + d, lo, hi)), RGB clamp(rint(t + d), lo, hi).  t + d is one fp32 addition.  d lies in the OPEN
+ * interval (-0.5, 0.5) in both modes and is rectangular, not triangular: a value that is a whole code already is never moved (at every
+ * served bit depth), and round-half-to-even meets no tie it did not have before.  Alpha and filler samples are never dithered.
+ * A sample is named by its component (0, 1, 2: Y, Cb, Cr / R, G, B), the row and column of its OWN grid (the picture's for luma, 4:4:4 and
+ * RGB; the chroma grid for subsampled chroma) and its frame:
+ *   BSVD_DITHER_ORDERED  d = (B[(row + r_c) & 7][(col + q_c) & 7] + 0.5) / 64 - 0.5, B the 8 x 8 Bayer matrix (0 .. 63, B[0][0..7] =
+ *                        0 32 8 40 2 34 10 42), (r_c, q_c) = (0, 0), (2, 5), (5, 2) for components 0, 1, 2.  Static over frames.
+ *   BSVD_DITHER_RANDOM   d = ((h >> 8) + 0.5) 2^-24 - 0.5, evaluated as ((float)((int)(h >> 8) - 2^23) + 0.5f) * 2^-24 (every step exact in
+ *                        fp32) and limited to +-(0.5 - 2^-7), ORDERED's largest |d|: two spacings of fp32 at the highest 16-bit codes below the
+ *                        tie, so that the ROUNDED sum t + d of a whole code (or of one a round trip left one spacing off) never reaches it.  h = fmix32(kf ^ p), fmix32 = MurmurHash3's 32-bit finaliser (h ^= h >> 16;
+ *                        h *= 0x85ebca6b; h ^= h >> 13; h *= 0xc2b2ae35; h ^= h >> 16); with n = (uint64)(frame0 + f) * 4 + component,
+ *                        kf = fmix32(seed ^ fmix32((uint32)n ^ fmix32((uint32)(n >> 32)))); p = (uint32)col + (uint32)row * 0x9e3779b1.
+ *                        frame0 + f is the frame's STREAM index: a clip encoded in one call of T frames and in T calls of one frame with
+ *                        frame0 counted up gives the same bytes.
+ * The `_d` functions return -3 for what the functions they are named after refuse, and for: a NULL dither; a mode outside 0 .. 2; a
+ * negative frame0; reserved != 0.
+ */
+enum { BSVD_DITHER_NONE = 0, BSVD_DITHER_ORDERED = 1, BSVD_DITHER_RANDOM = 2 };
+typedef struct BsvdDither {
+    int32_t mode;              /* BSVD_DITHER_* */
+    uint32_t seed;             /* RANDOM: the stream's seed */
+    int64_t frame0;            /* RANDOM: the stream index of the call's first frame */
+    int64_t reserved;          /* must be 0 */
+} BsvdDither;                  /* 24 bytes */
+int bsvd_blend_planar(float *y, int64_t y_frame_stride, const float *x, int64_t x_frame_stride, int32_t frames, int32_t Hp, int32_t Wp,
+                      float s_luma, float s_chroma, const float luma_w[3], void *stream);
+int bsvd_planar_to_yuv420_crop_d(const float *src, void *dst, int32_t frames, int32_t Hp, int32_t Wp, int32_t H, int32_t W,
+                                 const BsvdYuvDesc *desc, const BsvdDither *dither, void *stream);
+int bsvd_planar_to_yuv_crop_d(const float *src, void *dst, int32_t frames, int32_t Hp, int32_t Wp, int32_t H, int32_t W,
+                              const BsvdYuvSurface *surface, const BsvdDither *dither, void *stream);
+int bsvd_planar_to_rgb_d(const float *src, void *dst, int32_t frames, int32_t Hp, int32_t Wp, int32_t H, int32_t W,
+                         const BsvdRgbSurface *surface, const void *alpha_in, const BsvdDither *dither, void *stream);
+
+/*
  * The noise level of a frame, estimated on the device.  bsvd_c64 is non-blind: its fourth input channel is the noise map, which the
  * reference fills with a constant the caller knows (temp_denoise's sigma map, validation_seq_infer.py:19-21).  A camera, SDI or ffmpeg
  * feed comes without one.  These entry points stand in for that constant: bsvd_estimate_sigma computes one sigma per frame from the planar

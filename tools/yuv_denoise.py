@@ -15,6 +15,10 @@ steady_frames_per_s (wall clock, reads and writes included) over the steady stat
     python tools/yuv_denoise.py IN OUT --size 1920x1080 --sigma 30 --cuts auto [--cut-threshold 10]      scene cuts detected on the device
                                 (LiveStream(cuts='auto')): no frame is mixed with a frame of another scene; the JSON line then carries the
                                 frame numbers found.  Untested on real footage; a cut one or two frames after another cut scores low
+    python tools/yuv_denoise.py IN OUT --size 1920x1080 --sigma 30 --strength 0.7 | --strength 0.5,1.0  [--dither ordered|random] [--dither-seed N]
+                                the output finish, on the device: how much of the denoising to keep (one amount, or luma,chroma: 0.5,1.0
+                                keeps half the luma grain and removes all chroma noise), and dither at the quantiser (8 x 8 Bayer, or a
+                                per-frame hash) against banding (LiveStream(strength=, dither=)).  The visual effect is unmeasured on real footage
 
     ffmpeg -i in.mp4 -pix_fmt yuv420p -f rawvideo - | python tools/yuv_denoise.py - - --size 1920x1080 --sigma 30 | ffmpeg -f rawvideo ...
                                                                                   (--pix-fmt defaults to yuv420p, ffmpeg's own default)
@@ -46,6 +50,15 @@ def parse_sigma(text):
         raise argparse.ArgumentTypeError("--sigma %r: a number (8-bit code units, e.g. 30) or auto" % text) from None
 
 
+def parse_strength(text):
+    """--strength: S or S_LUMA,S_CHROMA, each in [0, 1] -> what LiveStream(strength=) takes"""
+    try:
+        v = tuple(float(p) for p in text.split(","))
+        return frame_io.check_strength(v[0] if len(v) == 1 else v)
+    except ValueError:
+        raise argparse.ArgumentTypeError("--strength %r: S or S_LUMA,S_CHROMA, each in [0, 1]" % text) from None
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("input")
@@ -60,6 +73,9 @@ def main(argv=None):
     ap.add_argument("--full-range", action="store_true")
     ap.add_argument("--limited-range", action="store_true", help="RGB formats: codes span [16 s, 235 s] instead of the full range")
     ap.add_argument("--chroma", default="linear", choices=["nearest", "linear"])
+    ap.add_argument("--strength", type=parse_strength, default=(1.0, 1.0), help="S or S_LUMA,S_CHROMA in [0, 1]: how much of the denoising to keep (default 1)")
+    ap.add_argument("--dither", default="none", choices=["none", "ordered", "random"], help="dither at the quantiser, on the device")
+    ap.add_argument("--dither-seed", type=int, default=0, help="seed of --dither random")
     ap.add_argument("--depth", type=int, default=2)
     ap.add_argument("--ckpt", default=None)
     ap.add_argument("--precision", default="f16x3")
@@ -85,7 +101,8 @@ def main(argv=None):
                       precision=a.precision).to(torch.device("cuda", 0)).eval()
     live = LiveStream(m, sigma=a.sigma, sigma_gain=a.sigma_gain, depth=a.depth, frame_shape=(H, W), pix_fmt=a.pix_fmt,
                       colour={"full_range": not a.limited_range} if rgb else {"matrix": a.matrix, "full_range": a.full_range, "chroma": a.chroma}, pad=pad,
-                      cuts="auto" if a.cuts == "auto" else None, cut_threshold=a.cut_threshold)
+                      cuts="auto" if a.cuts == "auto" else None, cut_threshold=a.cut_threshold,
+                      strength=a.strength, dither=None if a.dither == "none" else a.dither, dither_seed=a.dither_seed)
     found = []
     fin = sys.stdin.buffer if a.input == "-" else open(a.input, "rb")
     fout = sys.stdout.buffer if a.output == "-" else open(a.output, "wb")
@@ -121,6 +138,10 @@ def main(argv=None):
     if a.sigma == "auto":
         res["sigma_gain"] = a.sigma_gain
         res["last_sigma"] = None if live.last_sigma is None else live.last_sigma * 255.0
+    if a.strength != (1.0, 1.0):
+        res["strength"] = list(a.strength)
+    if a.dither != "none":
+        res["dither"] = a.dither
     if a.cuts == "auto":
         res["cut_threshold"] = a.cut_threshold
         res["cuts"] = found
