@@ -319,20 +319,42 @@ def _frames(name, n, H, W, seed):
     return rs.randint(0, 65536, (n, H, W, 3)).astype(np.uint16)
 
 
-def _by_hand(m, frames, name, cuts, strength, dither, frame0=0):
-    """rgb_to_input -> clip_forward -> blend_output -> output_to_rgb, with the stream's frame indices"""
-    from bsvd_amd.frame_io import blend_output, output_to_rgb, rgb_to_input
-    n, H, W = frames.shape[:3]
+def _by_hand(m, frames, name, cuts, strength, dither, frame0=0, sigma=SIGMA, size=None, pad=None, seed=F.SEED, info=None):
+    """*_to_input -> clip_forward -> blend_output -> output_to_*, with the stream's frame indices, on the default stream and synchronised.
+    ``name``: an RGB surface (frames: natural arrays [n,H,W,c]), 'rgb24', or a surface of bsvd_yuv_to_planar with the colour defaults
+    (frames: [n, samples] with ``size`` = (H, W)).  ``pad``: 'reflect'.  ``cuts``: the scene starts, or 'auto': frame_io.scene_cuts on
+    the converted tensor.  ``sigma``: a number or 'auto'.  ``info`` (a dict): gets 'cuts' (the starts used) and 'sigma' (estimate_sigma
+    per frame, as floats)."""
+    from bsvd_amd.frame_io import (blend_output, estimate_sigma, frames_to_input, network_size, output_to_frames, output_to_rgb, output_to_yuv,
+                                   rgb_to_input, scene_cuts, yuv_to_input)
+    n = frames.shape[0]
+    H, W = frames.shape[1:3] if size is None else size
+    pad_to, crop_to = (network_size(H, W), (H, W)) if pad else (None, None)
     dev = torch.from_numpy(frames.view(np.uint8).reshape(n, -1)).to(DEV)
     alpha = None
-    if R.has_alpha(name):
-        x, alpha = rgb_to_input(dev, H, W, name, sigma=SIGMA, return_alpha=True)
+    if name in YUV_NAMES:
+        x = yuv_to_input(dev, H, W, name, sigma=sigma, pad_to=pad_to)
+    elif name == "rgb24":
+        x = frames_to_input(dev.view(n, H, W, 3), sigma, pad_to=pad_to)
+    elif R.has_alpha(name):
+        x, alpha = rgb_to_input(dev, H, W, name, sigma=sigma, pad_to=pad_to, return_alpha=True)
     else:
-        x = rgb_to_input(dev, H, W, name, sigma=SIGMA)
+        x = rgb_to_input(dev, H, W, name, sigma=sigma, pad_to=pad_to)
+    if isinstance(cuts, str):
+        cuts = scene_cuts(x, picture=(H, W))
+    if info is not None:
+        info["cuts"] = list(cuts or [])
+        info["sigma"] = [float(v) for v in estimate_sigma(x, picture=(H, W)).cpu()]
     y = m.clip_forward(x, **({} if not cuts else dict(cuts=cuts))).float().contiguous()
     if strength is not None:
         blend_output(y, x, strength)
-    out = output_to_rgb(y, name, alpha=alpha, dither=dither, dither_seed=F.SEED, frame0=frame0)
+    if name in YUV_NAMES:
+        out = output_to_yuv(y, name, crop_to=crop_to, dither=dither, dither_seed=seed, frame0=frame0)
+    elif name == "rgb24" and dither is None:
+        out = output_to_frames(y, crop_to=crop_to)
+    else:
+        out = output_to_rgb(y, name, crop_to=crop_to, alpha=alpha, dither=dither, dither_seed=seed, frame0=frame0)
+    torch.cuda.synchronize()
     return out.cpu().numpy().view(frames.dtype).reshape(frames.shape)
 
 
