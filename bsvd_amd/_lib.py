@@ -28,7 +28,8 @@ EXPORTS = ("bsvd_abi_version", "bsvd_conv_args_size", "bsvd_build_info", "bsvd_l
            "bsvd_sigma_workspace_bytes", "bsvd_estimate_sigma", "bsvd_fill_sigma_plane",
            "bsvd_scene_grid", "bsvd_scene_diff",
            "bsvd_rgb_frame_bytes", "bsvd_rgb_to_planar", "bsvd_planar_to_rgb",
-           "bsvd_blend_planar", "bsvd_planar_to_yuv420_crop_d", "bsvd_planar_to_yuv_crop_d", "bsvd_planar_to_rgb_d")
+           "bsvd_blend_planar", "bsvd_planar_to_yuv420_crop_d", "bsvd_planar_to_yuv_crop_d", "bsvd_planar_to_rgb_d",
+           "bsvd_nlf_workspace_bytes", "bsvd_estimate_nlf", "bsvd_finish_nlf", "bsvd_fill_nlf_plane")
 PIX_FMT = {"nv12": 0, "p010": 1}
 MATRIX = {"bt601": 0, "bt709": 1, "bt2020": 2}
 CHROMA = {"nearest": 0, "linear": 1}
@@ -42,6 +43,9 @@ SIGMA_BINS = 4096             # bins of bsvd_estimate_sigma's histogram: 1 / 409
 # the scale from the median bin to sigma, 1 / (4096 * 6 * 0.6744897501960817) (frame_sigma_items.h, SIGMA_K), and where the estimate saturates
 SIGMA_K = float.fromhex("0x1.fa0fc23747344p-15")
 SIGMA_MAX = SIGMA_BINS * SIGMA_K
+# bsvd_estimate_nlf: levels of the noise-level curve, bins per level (1 / 1024 of |r| each: NLF_BINS * NLF_K = SIGMA_MAX), samples a level needs
+NLF_LEVELS, NLF_BINS, NLF_MIN_COUNT = 16, 1024, 512
+NLF_K = 4 * SIGMA_K
 # the surfaces of bsvd_yuv_to_planar / bsvd_planar_to_yuv, by ffmpeg's names: (subsampling, layout, bits, high_bits).  PIX_FMT above stays
 # the table of the bsvd_yuv420_* entry points.
 YUV_FORMATS = {
@@ -248,6 +252,14 @@ def load():
     lib.bsvd_estimate_sigma.argtypes = [vp, i32, i32, i32, i32, i32, i32, i64, f32, f32, f32, vp, vp, vp]
     lib.bsvd_fill_sigma_plane.restype = ctypes.c_int
     lib.bsvd_fill_sigma_plane.argtypes = [vp, i32, i32, i32, i32, i64, vp, vp]
+    lib.bsvd_nlf_workspace_bytes.restype = i64
+    lib.bsvd_nlf_workspace_bytes.argtypes = [i32]
+    lib.bsvd_estimate_nlf.restype = ctypes.c_int
+    lib.bsvd_estimate_nlf.argtypes = [vp, i32, i32, i32, i32, i32, i64, f32, f32, f32, i32, vp, vp, vp]
+    lib.bsvd_finish_nlf.restype = ctypes.c_int
+    lib.bsvd_finish_nlf.argtypes = [vp, i32, f32, f32, f32, i32, vp, vp]
+    lib.bsvd_fill_nlf_plane.restype = ctypes.c_int
+    lib.bsvd_fill_nlf_plane.argtypes = [vp, i32, i32, i32, i32, i64, vp, vp]
     lib.bsvd_scene_grid.restype = ctypes.c_int
     lib.bsvd_scene_grid.argtypes = [vp, i32, i32, i32, i32, i32, i64, vp, vp]
     lib.bsvd_scene_diff.restype = ctypes.c_int

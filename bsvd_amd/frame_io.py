@@ -21,7 +21,10 @@ YUV on the host and over PCIe.  ``network_size(H, W)`` is the (Hp, Wp) the pipel
 
 The noise level: ``sigma`` is a float (the constant the caller knows, as before), ``'auto'`` (one estimate per frame, computed on the device
 from the converted frame and written into that frame's noise-map plane -- ``estimate_sigma``; nothing crosses to the host and nothing waits
-for it), a sequence of per-frame values, or a device tensor [T].
+for it), a sequence of per-frame values, or a device tensor [T].  For sources whose noise depends on the signal level: ``'nlf'`` (a
+noise-level function per frame, sigma at sixteen levels of local intensity, estimated on the device, and a per-pixel noise map written from
+it -- ``estimate_noise_curve`` / ``fill_noise_map``) or a ``NoiseCurve`` the caller knows (``NoiseCurve.from_model(a, b)`` for a sensor's
+Poisson-Gaussian parameters).
 
 Scene cuts: ``scene_scores`` (a 16 x 16 block grid of 8-bit luma sums per frame and its frame-to-frame difference, on the device, in
 integers) and ``scene_cuts`` (the rule on top, on the host) find the frames that start a new scene, for the ``cuts=`` / ``cut=`` arguments of
@@ -84,14 +87,57 @@ def _check_gain(gain):
     return g
 
 
+NLF_LEVELS = _lib.NLF_LEVELS
+NLF_BINS = _lib.NLF_BINS
+NLF_MIN_COUNT = _lib.NLF_MIN_COUNT
+
+
+class NoiseCurve:
+    """a noise-level function the caller knows: sigma ([0,1] units) at the centres (l + 0.5) / 16 of the sixteen intensity levels,
+    for ``sigma=NoiseCurve(...)``: every frame's noise map is ``fill_noise_map`` of these values.  Sixteen finite numbers >= 0."""
+
+    def __init__(self, values):
+        try:
+            vals = tuple(float(v) for v in values)
+        except (TypeError, ValueError):
+            raise ValueError("NoiseCurve: expected %d numbers, got %r" % (NLF_LEVELS, values)) from None
+        if len(vals) != NLF_LEVELS:
+            raise ValueError("NoiseCurve: expected %d values (one per intensity level), got %d" % (NLF_LEVELS, len(vals)))
+        if not all(0.0 <= v < float("inf") for v in vals):
+            raise ValueError("NoiseCurve: values must be finite and not negative, got %r" % (vals,))
+        self.values = vals
+
+    @classmethod
+    def from_model(cls, a, b):
+        """the Poisson-Gaussian sensor model: sigma(I) = sqrt(max(a I + b, 0)) at the level centres, I and sigma in [0,1] units"""
+        try:
+            a, b = float(a), float(b)
+        except (TypeError, ValueError):
+            raise ValueError("NoiseCurve.from_model: expected two numbers, got %r, %r" % (a, b)) from None
+        return cls([max(a * (l + 0.5) / NLF_LEVELS + b, 0.0) ** 0.5 for l in range(NLF_LEVELS)])
+
+    def __eq__(self, other):
+        return isinstance(other, NoiseCurve) and self.values == other.values
+
+    def __hash__(self):
+        return hash(self.values)
+
+    def __repr__(self):
+        return "NoiseCurve(%r)" % (list(self.values),)
+
+
 def _sigma_mode(sigma, T=None):
-    """what ``sigma=`` asks for -> ('const', None | float) -- today's path --, ('auto', None), ('host', [T floats]) or ('device', tensor [T]).
-    Needs no device; T (when known) is checked against the length of per-frame values."""
+    """what ``sigma=`` asks for -> ('const', None | float) -- today's path --, ('auto', None), ('nlf', None), ('curve', [16 floats]),
+    ('host', [T floats]) or ('device', tensor [T]).  Needs no device; T (when known) is checked against the length of per-frame values."""
     if sigma is None:
         return "const", None
+    if isinstance(sigma, NoiseCurve):
+        return "curve", list(sigma.values)
     if isinstance(sigma, str):
+        if sigma == "nlf":
+            return "nlf", None
         if sigma != "auto":
-            raise ValueError("sigma %r: a number, 'auto', a sequence of per-frame values or a device tensor [T]" % (sigma,))
+            raise ValueError("sigma %r: a number, 'auto', 'nlf', a NoiseCurve, a sequence of per-frame values or a device tensor [T]" % (sigma,))
         return "auto", None
     if isinstance(sigma, torch.Tensor) and sigma.dim() >= 1:
         if sigma.dim() != 1 or sigma.dtype != torch.float32:
@@ -157,10 +203,87 @@ def fill_sigma_plane(x, sigma_dev):
     return x
 
 
+def _check_min_count(min_count):
+    try:
+        n = int(min_count)
+    except (TypeError, ValueError):
+        raise ValueError("min_count: expected a positive integer, got %r" % (min_count,)) from None
+    if n != min_count or not (1 <= n < 2 ** 31):
+        raise ValueError("min_count %r: must be a positive integer" % (min_count,))
+    return n
+
+
+def estimate_noise_curve(x, picture=None, gain=1.0, clamp=(0.0, SIGMA_MAX), min_count=NLF_MIN_COUNT, return_hist=False):
+    """x: fp32 device tensor [T,C>=3,Hp,Wp], the tensor the ``*_to_input`` functions build -> fp32 device tensor [T,16]: the frame's
+    noise-level function, sigma ([0,1] units) at sixteen levels of local intensity (level l: 3 x 3 box mean in [l/16, (l+1)/16)), computed
+    on the device, not synchronised with the host.  The sample is ``estimate_sigma``'s (the Laplacian-difference response at the interior
+    pixels of the picture in the three colour planes), binned by the 3 x 3 box sum of the same nine values; per level the median of
+    |response| from a 1024-bin histogram, / (6 * 0.6745), ``* gain``, clamped to ``clamp``.  A level with fewer than ``min_count`` samples
+    takes the value of the nearest level that has them (the lower one on a tie); if none has, every level gets the pooled estimate.
+    Bit-reproducible (integer counts; include/bsvd_hip.h states it operation by operation).  No smoothing across levels and no temporal
+    filter: both are left to the caller.  ``picture=(H, W)``: as for ``estimate_sigma``.  ``return_hist=True``: also the uint32
+    [T,16,1024] histograms.
+
+    What is known: on synthetic frames with sigma(I) = sqrt(a I + b) noise quantised to 8 bits the levels away from the clipped ends are
+    within the bounds of profiles/noise_curve.txt.  Nothing has been measured on real footage, and a per-pixel noise map is outside what
+    the reference's checkpoints were trained on (a constant plane)."""
+    lo, hi = _check_clamp(clamp)
+    gain = _check_gain(gain)
+    min_count = _check_min_count(min_count)
+    T, C, Hp, Wp = _planes(x, "estimate_noise_curve")
+    if C < 3:
+        raise ValueError("estimate_noise_curve: the estimate pools the three colour planes, x has %d" % C)
+    H, W = (Hp, Wp) if picture is None else _pair(picture, "picture")
+    lib = require_hip()
+    hist = torch.empty((T, NLF_LEVELS, NLF_BINS), dtype=torch.int32, device=x.device)
+    out = torch.empty((T, NLF_LEVELS), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(lib.bsvd_estimate_nlf(x.data_ptr(), T, H, W, Hp, Wp, C * Hp * Wp, gain, lo, hi, min_count, hist.data_ptr(), out.data_ptr(),
+                                         _stream()), "bsvd_estimate_nlf")
+    return (out, hist.view(torch.uint32)) if return_hist else out
+
+
+def noise_curve_from_hist(hist, gain=1.0, clamp=(0.0, SIGMA_MAX), min_count=NLF_MIN_COUNT):
+    """hist: uint32 (or int32) device tensor [T,16,1024], e.g. ``estimate_noise_curve(return_hist=True)`` histograms the caller has summed
+    over frames -> fp32 device tensor [T,16]: the curve step of ``estimate_noise_curve`` alone"""
+    lo, hi = _check_clamp(clamp)
+    gain = _check_gain(gain)
+    min_count = _check_min_count(min_count)
+    if (not isinstance(hist, torch.Tensor) or hist.dtype not in (torch.uint32, torch.int32) or not hist.is_cuda or hist.dim() != 3
+            or tuple(hist.shape[1:]) != (NLF_LEVELS, NLF_BINS) or not hist.is_contiguous()):
+        raise ValueError("noise_curve_from_hist: expected a contiguous uint32 device tensor [T,%d,%d]" % (NLF_LEVELS, NLF_BINS))
+    lib = require_hip()
+    out = torch.empty((hist.shape[0], NLF_LEVELS), dtype=torch.float32, device=hist.device)
+    with torch.cuda.device(hist.device):
+        _lib.check(lib.bsvd_finish_nlf(hist.data_ptr(), hist.shape[0], gain, lo, hi, min_count, out.data_ptr(), _stream()), "bsvd_finish_nlf")
+    return out
+
+
+def fill_noise_map(x, curve):
+    """x: fp32 device tensor [T,C>=4,Hp,Wp]; curve: fp32 device tensor [T,16] (``estimate_noise_curve``).  The last plane of frame t becomes
+    that frame's per-pixel noise map, in place, on the device: at every pixel of the whole plane (the mirror margin of ``pad_to`` included)
+    the 3 x 3 box means of R, G, B (replicate borders) mixed 1:2:1 give a position on the level axis, and the curve is interpolated linearly
+    between the level centres.  A flat curve gives exactly that value everywhere; the map is finite whatever the colour planes hold."""
+    T, C, Hp, Wp = _planes(x, "fill_noise_map")
+    if (not isinstance(curve, torch.Tensor) or curve.dtype != torch.float32 or curve.device != x.device
+            or tuple(curve.shape) != (T, NLF_LEVELS) or not curve.is_contiguous()):
+        raise ValueError("fill_noise_map: expected a contiguous float32 tensor [%d,%d] on %s" % (T, NLF_LEVELS, x.device))
+    if C < 4:
+        raise ValueError("fill_noise_map: x needs three colour planes and a plane behind them, it has %d" % C)
+    lib = require_hip()
+    with torch.cuda.device(x.device):
+        _lib.check(lib.bsvd_fill_nlf_plane(x.data_ptr(), T, C - 1, Hp, Wp, C * Hp * Wp, curve.data_ptr(), _stream()), "bsvd_fill_nlf_plane")
+    return x
+
+
 def _with_sigma(y, mode, picture, gain):
-    """the shared second half of the three ``*_to_input`` functions for per-frame sigma: y was converted with its sigma plane at 0;
-    estimate (or upload) the T values, fill the plane"""
+    """the shared second half of the ``*_to_input`` functions for per-frame sigma: y was converted with its sigma plane at 0;
+    estimate (or upload) the T values, fill the plane -- or, for 'nlf' / a NoiseCurve, the T curves and the per-pixel map"""
     kind, val = mode
+    if kind == "nlf":
+        return fill_noise_map(y, estimate_noise_curve(y, picture=picture, gain=gain))
+    if kind == "curve":
+        return fill_noise_map(y, torch.tensor(val, dtype=torch.float32).to(y.device).expand(y.shape[0], NLF_LEVELS).contiguous())
     if kind == "auto":
         s = estimate_sigma(y, picture=picture, gain=gain)
     elif kind == "host":

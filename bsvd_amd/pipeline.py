@@ -34,7 +34,10 @@ and the PCIe transfers stay picture-sized and the results have the shape and dty
 
 ``sigma`` is the noise level of the non-blind models' noise map: a float the caller knows, or 'auto' -- every frame's own estimate, computed
 on the compute stream from the converted frame and written into its noise-map plane (``frame_io.estimate_sigma``; ``sigma_gain`` scales
-it).  The host sees it only afterwards, as ``LiveStream.last_sigma``: 4 bytes that come down with the frame.
+it).  The host sees it only afterwards, as ``LiveStream.last_sigma``: 4 bytes that come down with the frame.  For sources whose noise depends
+on the signal level: 'nlf' -- every frame's own noise-level function, sigma at sixteen levels of local intensity, and a per-pixel noise map
+written from it (``frame_io.estimate_noise_curve`` / ``fill_noise_map``; ``LiveStream.last_noise_curve``: 64 bytes that come down with the
+frame) -- or a ``frame_io.NoiseCurve`` the caller knows.
 
 ``cuts`` is what the pipelines know about scene cuts: None (nothing: the footage is one scene, as before) or 'auto' -- every frame is scored
 against the one before it on the device (``frame_io.scene_scores`` / ``scene_cuts``; ``cut_threshold``) and a frame that scores as a scene
@@ -48,7 +51,7 @@ import torch
 
 from . import _lib
 from .frame_io import (CUT_THRESHOLD, _check_gain, _luma_weights, _sigma_mode, _yuv_desc, _yuv_surface, blend_output, check_cut_threshold, check_dither,
-                       check_strength, cut_scores, frames_to_input, network_size,
+                       check_strength, cut_scores, estimate_noise_curve, fill_noise_map, frames_to_input, network_size,
                        output_to_frames, output_to_rgb, output_to_yuv, output_to_yuv420, rgb_frame_bytes, rgb_to_input, scene_cuts, scene_scores,
                        yuv420_frame_bytes, yuv420_picture_bytes, yuv420_to_input, yuv_to_input)
 
@@ -370,13 +373,16 @@ def _check_cuts_mode(cuts, cut_threshold, what):
 
 
 def _check_sigma(model, sigma, sigma_gain, what):
-    """the pipelines' ``sigma``: None, a float or 'auto' -- which needs a noise-map channel to write into.  Before anything touches a device."""
+    """the pipelines' ``sigma``: None, a float, 'auto', 'nlf' or a NoiseCurve -- the last three need a noise-map channel to write into.
+    Before anything touches a device."""
     if isinstance(sigma, str) or sigma is None or not hasattr(sigma, "__len__"):
         mode = _sigma_mode(sigma)[0]
     else:
-        raise ValueError("%s: sigma must be None, a number or 'auto' (per-frame values: frame_io.frames_to_input(sigma=[...]))" % what)
+        raise ValueError("%s: sigma must be None, a number, 'auto', 'nlf' or a NoiseCurve (per-frame values: frame_io.frames_to_input(sigma=[...]))" % what)
     if mode == "auto" and model.net.net_in_ch == 3:
         raise ValueError("%s(sigma='auto'): the model is blind (3 input channels): it has no noise map to estimate" % what)
+    if mode in ("nlf", "curve") and model.net.net_in_ch == 3:
+        raise ValueError("%s(sigma=%s): the model is blind (3 input channels): it has no noise map to write" % (what, "'nlf'" if mode == "nlf" else "NoiseCurve"))
     return _check_gain(sigma_gain)
 
 
@@ -390,6 +396,7 @@ class _Slot:
         self.downloaded = torch.cuda.Event()
         self.ticket = None          # the in-flight clip occupying this slot
         self.dev_sigma = self.pin_sigma = None      # LiveStream(sigma='auto'): the step's estimate, 4 bytes beside the frame
+        self.dev_curve = self.pin_curve = None      # LiveStream(sigma='nlf'): the step's noise-level curve, 64 bytes beside the frame
         self.dev_alpha = None                       # ClipPipeline, formats with alpha: the clip's alpha plane [T,H,W], held like dev_out
 
 
@@ -417,6 +424,8 @@ class ClipPipeline:
     with frame_shape=(H, W): clips are [T, n] arrays of the tight frames' samples (uint8, uint16 for 10 bit), as ffmpeg's rawvideo.
     sigma='auto' (non-blind models): every frame's noise-map plane holds that frame's own estimate, times sigma_gain, computed on the
     device (``frame_io.estimate_sigma``: what is known about it, and that YUV sources with subsampled chroma read low).
+    sigma='nlf' or a ``frame_io.NoiseCurve`` (non-blind models): a per-pixel noise map from every frame's own noise-level function, or from
+    the caller's curve (``frame_io.estimate_noise_curve`` / ``fill_noise_map``: what is known about them).
     pix_fmt one of the RGB names of the module docstring ('bgra', 'rgba64le', 'gbrp10le', ...): clips are [T,...] arrays of self-describing
     frames (or [T, n] tight samples with frame_shape), colour={'full_range': bool}; the clip's alpha codes stay on the device beside the
     clip and come back with their frames.
@@ -557,6 +566,12 @@ class LiveStream:
     pinned memory beside the frame and is never read earlier.  Nothing is known about the estimate on real footage, and YUV sources with
     subsampled chroma read low (``sigma_gain``).
 
+    sigma='nlf' (non-blind models): the noise-map plane of every frame is that frame's own per-pixel map, written from its noise-level
+    function (``frame_io.estimate_noise_curve`` / ``fill_noise_map``, times ``sigma_gain``), on the same stream at the same place.
+    ``last_noise_curve``: the sixteen values of the most recent input step ``feed`` has already waited for, None before that; ``last_sigma``
+    stays None.  sigma=``frame_io.NoiseCurve``: the map is written from the caller's curve and nothing is reported.  Nothing is known
+    about either on real footage.
+
     Scene cuts.  ``feed(frame, cut=True)`` says that ``frame`` starts a new scene: no temporal-fusion conv mixes it with the frames before it
     (each side sees zeros for the other, as at a stream's ends), nothing is flushed and no feed returns None because of it.  The steps a cut
     passes through have launch plans of their own: batched launches at the first sighting, captured when the same ring phase recurs.
@@ -586,8 +601,10 @@ class LiveStream:
         self._grids = self._sad = self._pin_sad = None       # cuts='auto': two alternating grid buffers, the step's sum on the device and pinned
         self._have_prev, self._prev_mafd, self._n_scored = False, 0.0, 0
         self.sigma_gain = _check_sigma(model, sigma, sigma_gain, "LiveStream")
-        self.auto_sigma = isinstance(sigma, str)
+        self.auto_sigma = isinstance(sigma, str) and sigma == "auto"
+        self.nlf_sigma = isinstance(sigma, str) and sigma == "nlf"
         self.last_sigma = None
+        self.last_noise_curve = None
         self.fmt = _pixel_format(pix_fmt, colour, pad, frame_shape)
         self._alpha = None                                    # formats with alpha: the ring of alpha planes (_AlphaRing), allocated with the slots
         self.finish = _Finish(self.fmt, strength, dither, dither_seed, luma_matrix)
@@ -651,6 +668,9 @@ class LiveStream:
             if self.auto_sigma:
                 s.pin_sigma = torch.zeros(1, dtype=torch.float32).pin_memory()
                 s.dev_sigma = torch.empty(1, dtype=torch.float32, device=self.device)
+            if self.nlf_sigma:
+                s.pin_curve = torch.zeros(_lib.NLF_LEVELS, dtype=torch.float32).pin_memory()
+                s.dev_curve = torch.empty(_lib.NLF_LEVELS, dtype=torch.float32, device=self.device)
             self.slots.append(s)
         if getattr(self.fmt, "has_alpha", False):
             self._alpha = _AlphaRing(self.latency + self.depth, geom.h, geom.w, getattr(torch, self.fmt.dtype.name), self.device)
@@ -687,10 +707,15 @@ class LiveStream:
 
     def _to_input(self, slot):
         """the slot's frame -> the network input; a format with alpha leaves the frame's alpha codes in the ring's next plane"""
+        sigma = 0.0 if self.nlf_sigma else self.sigma
         if self._alpha is None:
-            x = self.fmt.to_input(slot.dev_in, self.geom, self.sigma, self.sigma_gain)
+            x = self.fmt.to_input(slot.dev_in, self.geom, sigma, self.sigma_gain)
         else:
-            x = self.fmt.to_input(slot.dev_in, self.geom, self.sigma, self.sigma_gain, alpha=self._alpha.next_in())[0]
+            x = self.fmt.to_input(slot.dev_in, self.geom, sigma, self.sigma_gain, alpha=self._alpha.next_in())[0]
+        if self.nlf_sigma:                                   # what sigma='nlf' does inside to_input, with the curve kept for the host
+            curve = estimate_noise_curve(x, picture=(self.geom.h, self.geom.w), gain=self.sigma_gain)
+            fill_noise_map(x, curve)
+            slot.dev_curve.copy_(curve[0])
         if self._source is not None:
             self._source.next_in().copy_(x[:, :3])          # the frame's colour planes wait for its denoised self
         return x
@@ -709,8 +734,10 @@ class LiveStream:
         """oldest in-flight step -> its uint8 frame, or None if that step emitted nothing (pipeline fill)"""
         slot, has_out, has_sigma = self.inflight.popleft()
         slot.downloaded.synchronize()
-        if has_sigma:
+        if has_sigma and self.auto_sigma:
             self.last_sigma = float(slot.pin_sigma[0])
+        if has_sigma and self.nlf_sigma:
+            self.last_noise_curve = [float(v) for v in slot.pin_curve]
         return slot.pin_out.numpy().copy().view(self.fmt.dtype).reshape(self.shape) if has_out else None
 
     def _step(self, frame_u8, last=False, cut=False):
@@ -746,8 +773,10 @@ class LiveStream:
                     slot.pin_out.copy_(slot.dev_out[0], non_blocking=True)
                 if self.auto_sigma and frame_u8 is not None:
                     slot.pin_sigma.copy_(slot.dev_sigma, non_blocking=True)
+                if self.nlf_sigma and frame_u8 is not None:
+                    slot.pin_curve.copy_(slot.dev_curve, non_blocking=True)
                 slot.downloaded.record()
-        self.inflight.append((slot, y is not None, self.auto_sigma and frame_u8 is not None))
+        self.inflight.append((slot, y is not None, (self.auto_sigma or self.nlf_sigma) and frame_u8 is not None))
 
     def _drain(self, keep, outs):
         while len(self.inflight) > keep:

@@ -651,6 +651,59 @@ int bsvd_fill_sigma_plane(float *x, int32_t frames, int32_t channels, int32_t Hp
                           void *stream);
 
 /*
+ * The noise-level function (NLF) of a frame and the per-pixel noise map made from it.  One sigma per frame fits white Gaussian noise; the
+ * noise of a camera or a decoder depends on the signal level (shot noise through a tone curve), and the network reads its noise-map plane
+ * per pixel.  bsvd_estimate_nlf computes sigma as a function of local intensity, sixteen values per frame; bsvd_fill_nlf_plane writes the
+ * map from them.  Both run on the device from the planar fp32 tensor the *_to_planar entry points build; nothing crosses to the host.
+ * Added without a new BSVD_ABI_VERSION: discover the entry points by symbol (dlsym), like the sigma entry points above.
+ *
+ * Exactly (tests/nlf_model.py reproduces histogram, curve and map bit for bit), with NLF_LEVELS = 16 and NLF_BINS = 1024:
+ *   input     x [frames][>= 3][Hp][Wp] fp32, frames `frame_stride` FLOATS apart, rows Wp apart.  The picture is the top-left H x W of each
+ *             plane (3 <= H <= Hp, 3 <= W <= Wp).
+ *   samples   the interior pixels 1 <= r <= H - 2, 1 <= c <= W - 2 of the first three planes, pooled per frame.
+ *   response  r: the Laplacian-difference mask of bsvd_estimate_sigma, in its order of operations.
+ *   box sum   S of the same nine values, in fp32, in this order: row = (x_w + x_c) + x_e for each of the three rows,
+ *             S = (row_n + row_c) + row_s.  The box is orthogonal to the mask (1 - 2 + 1 = 0): under white noise S is uncorrelated with
+ *             r, so binning by it does not bias the median.
+ *   level     l = clamp(floor(S * c169), 0, 15) with c169 = 16 / 9 rounded to fp32 once; +inf gives 15, anything not >= 0 gives 0.
+ *   bin       q = min(floor(|r| * 1024), 1023); a sample is counted iff r is finite.  Counts are uint32 [frames][16][1024].  Integer adds
+ *             only: the histogram does not depend on the launch shape.
+ *   curve     c[t][l], fp32.  A level with at least min_count samples is VALID: N = its counts, k = the first bin with 2 cum[k] >= N,
+ *             before = cum[k] - h[k]; in double med = k + (N - 2 before) / (2 h[k]), value = med * K with
+ *             K = 1 / (1024 * 6 * 0.6744897501960817), then * gain, clamped to [lo, hi], converted to fp32.  A level that is not valid
+ *             takes the value of the nearest valid level, the lower one on a tie.  No valid level: every level gets the pooled value, the
+ *             same finish on the histogram summed over the levels (N == 0 gives lo).  No smoothing across levels, no temporal filter.
+ *   map       for every pixel of the whole Hp x Wp plane: the box sums S_R, S_G, S_B of planes 0, 1, 2 with row and column indices clamped
+ *             to the plane (replicate); u = ((S_R + S_B) + 2 S_G) * c1636 - 0.5 with c1636 = 16 / 36 rounded to fp32 once, multiply and
+ *             subtract rounded separately; u clamped to [0, 15], not-a-number gives 0; i = min((int)u, 14), f = u - i;
+ *             map = c[i] + f * (c[i + 1] - c[i]) in fp32, the product rounded before the add.  Level l's value sits at its centre.
+ * Two consequences: a flat curve gives exactly that value at every pixel (f * 0 = 0: the bits bsvd_fill_sigma_plane writes), and the map is
+ * finite whatever the colour planes hold (c is finite, 0 <= f <= 1).
+ * What is known about it: profiles/noise_curve.txt, on synthetic signal-dependent noise only.  Nothing has been measured on real footage,
+ * and a per-pixel map is outside what the reference's checkpoints were trained on (a constant plane).
+ *
+ * bsvd_nlf_workspace_bytes(frames): the bytes of `workspace`, frames * 16 * 1024 * 4; -1 for frames <= 0.
+ * bsvd_estimate_nlf: zeroes the workspace itself, on the stream; afterwards the workspace holds the [frames][16][1024] uint32 histograms
+ *   and curve_out[frames][16] the curves (fp32, device memory).  Rows move as float4 when x is 16-byte aligned and Wp and frame_stride are
+ *   multiples of 4, as scalars otherwise.  Returns -3, naming the argument in bsvd_last_error(), for: a NULL pointer; a pointer that is not
+ *   4-byte aligned; frames outside 1 .. 65535; H or W below 3; Hp < H or Wp < W; frame_stride below 3 * Hp * Wp;
+ *   3 * (H - 2) * (W - 2) >= 2^32; gain not positive and finite; lo or hi not finite, lo < 0 or lo > hi; min_count < 1.  All of it without
+ *   a device.
+ * bsvd_finish_nlf: the curve step alone, from [frames][16][1024] uint32 histograms the caller holds in device memory (a caller who pools
+ *   histograms over frames, or a test of the curve rules).  The workspace is only read.  -3 as above for its arguments.
+ * bsvd_fill_nlf_plane: x [frames][>= channels + 1][Hp][Wp], channels >= 3; every element of plane `channels` of frame t is written from
+ *   planes 0 .. 2 of that frame and curve_dev[t][0 .. 15] (device memory).  float4 loads and stores when x is 16-byte aligned and Wp and
+ *   frame_stride are multiples of 4.  -3 for: a NULL or misaligned pointer; frames outside 1 .. 65535; channels < 3; Hp or Wp <= 0;
+ *   frame_stride below (channels + 1) * Hp * Wp.
+ */
+int64_t bsvd_nlf_workspace_bytes(int32_t frames);
+int bsvd_estimate_nlf(const float *x, int32_t frames, int32_t H, int32_t W, int32_t Hp, int32_t Wp, int64_t frame_stride,
+                      float gain, float lo, float hi, int32_t min_count, void *workspace, float *curve_out /*[frames][16]*/, void *stream);
+int bsvd_finish_nlf(const void *workspace, int32_t frames, float gain, float lo, float hi, int32_t min_count, float *curve_out, void *stream);
+int bsvd_fill_nlf_plane(float *x, int32_t frames, int32_t channels, int32_t Hp, int32_t Wp, int64_t frame_stride,
+                        const float *curve_dev /*[frames][16]*/, void *stream);
+
+/*
  * What a scene-cut detector needs from a frame, computed on the device.  Each temporal-fusion conv mixes a frame with its two neighbours; a
  * caller who knows where a scene starts passes halo_prev = NULL / halo_next = NULL there (a clip end in mid-stream).  These two entry points
  * serve the caller who does not know: they reduce the planar fp32 tensor the *_to_planar entry points build -- so the result does not depend

@@ -12,6 +12,12 @@ steady_frames_per_s (wall clock, reads and writes included) over the steady stat
     python tools/yuv_denoise.py IN OUT --size 1920x1080 --sigma auto [--sigma-gain 1.0]      the noise level of every frame estimated on the
                                 device (LiveStream(sigma='auto')); the JSON line then carries last_sigma, in 8-bit code units.  Untested on
                                 real footage; with subsampled chroma the estimate reads low, which --sigma-gain corrects
+    python tools/yuv_denoise.py IN OUT --size 1920x1080 --sigma nlf [--sigma-gain 1.0]       for noise that depends on the signal level: a
+                                noise-level function per frame (sigma at sixteen levels of local intensity) estimated on the device and a
+                                per-pixel noise map written from it (LiveStream(sigma='nlf')); the JSON line then carries last_noise_curve,
+                                in 8-bit code units.  Untested on real footage, and outside what the reference's checkpoints were trained on
+    python tools/yuv_denoise.py IN OUT --size 1920x1080 --noise-model A,B                    the same map from a sensor model the caller
+                                knows, sigma(I) = sqrt(A I + B) with I and sigma in 8-bit code units (frame_io.NoiseCurve.from_model)
     python tools/yuv_denoise.py IN OUT --size 1920x1080 --sigma 30 --cuts auto [--cut-threshold 10]      scene cuts detected on the device
                                 (LiveStream(cuts='auto')): no frame is mixed with a frame of another scene; the JSON line then carries the
                                 frame numbers found.  Untested on real footage; a cut one or two frames after another cut scores low
@@ -41,13 +47,22 @@ def read_frames(f, nbytes):
 
 
 def parse_sigma(text):
-    """--sigma: 'auto', or the noise std in 8-bit code units -> what LiveStream(sigma=) takes"""
-    if text == "auto":
-        return "auto"
+    """--sigma: 'auto', 'nlf', or the noise std in 8-bit code units -> what LiveStream(sigma=) takes"""
+    if text in ("auto", "nlf"):
+        return text
     try:
         return float(text) / 255.0
     except ValueError:
-        raise argparse.ArgumentTypeError("--sigma %r: a number (8-bit code units, e.g. 30) or auto" % text) from None
+        raise argparse.ArgumentTypeError("--sigma %r: a number (8-bit code units, e.g. 30), auto or nlf" % text) from None
+
+
+def parse_noise_model(text):
+    """--noise-model A,B: sigma(I) = sqrt(A I + B), I and sigma in 8-bit code units -> frame_io.NoiseCurve ([0,1] units: a = A / 255, b = B / 255^2)"""
+    try:
+        A, B = (float(p) for p in text.split(","))
+        return frame_io.NoiseCurve.from_model(A / 255.0, B / 255.0 ** 2)
+    except ValueError:
+        raise argparse.ArgumentTypeError("--noise-model %r: A,B with sigma(I) = sqrt(A I + B) in 8-bit code units" % text) from None
 
 
 def parse_strength(text):
@@ -65,8 +80,10 @@ def main(argv=None):
     ap.add_argument("output")
     ap.add_argument("--size", required=True, help="WxH of the pictures, e.g. 1920x1080")
     ap.add_argument("--pix-fmt", default="yuv420p", choices=["nv12", "p010"] + sorted(_lib.YUV_FORMATS) + sorted(set(_lib.RGB_FORMATS) - {'rgb24'}))
-    ap.add_argument("--sigma", type=parse_sigma, required=True, help="noise std in 8-bit code units (e.g. 30), or auto: estimated per frame on the device")
-    ap.add_argument("--sigma-gain", type=float, default=1.0, help="factor on the estimate of --sigma auto")
+    ap.add_argument("--sigma", type=parse_sigma, default=None, help="noise std in 8-bit code units (e.g. 30); auto: estimated per frame on the device; "
+                    "nlf: a noise-level curve per frame and a per-pixel noise map")
+    ap.add_argument("--noise-model", type=parse_noise_model, default=None, help="A,B instead of --sigma: sigma(I) = sqrt(A I + B) in 8-bit code units")
+    ap.add_argument("--sigma-gain", type=float, default=1.0, help="factor on the estimate of --sigma auto / nlf")
     ap.add_argument("--cuts", default="none", choices=["none", "auto"], help="auto: scene cuts detected per frame on the device")
     ap.add_argument("--cut-threshold", type=float, default=frame_io.CUT_THRESHOLD, help="score at which --cuts auto declares a scene start")
     ap.add_argument("--matrix", default="bt709", choices=["bt601", "bt709", "bt2020"])
@@ -80,6 +97,10 @@ def main(argv=None):
     ap.add_argument("--ckpt", default=None)
     ap.add_argument("--precision", default="f16x3")
     a = ap.parse_args(argv)
+    if (a.sigma is None) == (a.noise_model is None):
+        ap.error("one of --sigma and --noise-model is required")
+    if a.noise_model is not None:
+        a.sigma = a.noise_model
     W, H = map(int, a.size.lower().split("x"))
     rgb = a.pix_fmt in _lib.RGB_FORMATS                  # the RGB formats: 1-D frames too
     surface = a.pix_fmt in _lib.YUV_FORMATS or rgb       # the 1-D frames of the planar / 4:2:2 / 4:4:4 formats
@@ -134,7 +155,12 @@ def main(argv=None):
            "ms_per_feed": {"p50": float(np.percentile(steady, 50)), "p99": float(np.percentile(steady, 99))},
            "steady_frames_per_s": (n_in - k) / (done[-1] - done[k - 1]) if n_in > k >= 1 else 0.0,       # wall clock, reads and writes included
            "size": "%dx%d" % (W, H), "pix_fmt": a.pix_fmt, "depth": a.depth, "frame_latency_feeds": live.latency, "pad": pad,
-           "sigma": "auto" if a.sigma == "auto" else a.sigma * 255.0}
+           "sigma": a.sigma if isinstance(a.sigma, str) else "noise-model" if a.noise_model is not None else a.sigma * 255.0}
+    if a.sigma == "nlf":
+        res["sigma_gain"] = a.sigma_gain
+        res["last_noise_curve"] = None if live.last_noise_curve is None else [v * 255.0 for v in live.last_noise_curve]
+    if a.noise_model is not None:
+        res["last_noise_curve"] = [v * 255.0 for v in a.noise_model.values]
     if a.sigma == "auto":
         res["sigma_gain"] = a.sigma_gain
         res["last_sigma"] = None if live.last_sigma is None else live.last_sigma * 255.0
