@@ -1,0 +1,398 @@
+"""The option matrix of the host pipelines (bsvd_amd/pipeline.py: LiveStream, ClipPipeline): the factors, the rules that say which rows the
+constructors take, and two committed pairwise tables -- every pair of factor values that can meet in a row meets in at least one row.
+Pure Python: nothing here imports torch or the package at module level; tests/test_pipeline_matrix_cpu.py holds the tables to their
+properties and ``refusal`` to the product's own checks, tests/test_gpu_pipeline_matrix.py runs the rows.
+
+A row is a tuple of short keys, one per factor, in the order of ``LIVE_FACTORS`` / ``CLIP_FACTORS``; ``as_dict`` names them, the ``*_of``
+functions turn a key into what the constructors take.
+
+Two kinds of rule:
+  ``refusal(row, pipeline)``   what the product refuses (a restatement of the constructors' checks and of ``geometry``), or None;
+  ``vacuous(row, pipeline)``   what the product takes but the matrix leaves out, because the row could not test what it names, or None.
+``valid`` is neither.  The second kind has one entry, a colour value that is another's synonym.
+
+Three tables ("live", "clip", "clip2").  rgb0 and x2rgb10le: with eleven formats against six sigma values an array needs 66 rows before any
+rule; the LiveStream table, capped at 64, leaves these two formats to CLIP_ROWS, whose own cap of 32 holds four formats against the six
+sigma values (``CLIP_PIX_FMT``).  CLIP2_ROWS, a second ClipPipeline table under the same cap, takes the other seven formats against three
+sigma values (``CLIP2_SIGMAS``: the constant, and 'auto' and 'nlf' with their gains), so that every format meets ClipPipeline's options."""
+import collections
+import itertools
+import random
+
+PIX_FMT = ("rgb24", "nv12", "p010", "yuv420p", "uyvy422", "yuv444p10le", "bgra", "rgba64le", "x2rgb10le", "gbrap10le", "rgb0")
+LIVE_PIX_FMT = tuple(f for f in PIX_FMT if f not in ("rgb0", "x2rgb10le"))       # these two: CLIP_ROWS only (module docstring)
+# ClipPipeline's cap of 32 rows holds five formats at most against six sigma values (5 x 6 = 30), and the greedy generator reaches the cap
+# with four (33 to 37 rows with five): the two the LiveStream table leaves out and the two of the mandatory rows.  The other seven are
+# CLIP2_ROWS', against three sigma values.
+CLIP_PIX_FMT = ("rgb0", "x2rgb10le", "rgba64le", "p010")
+CLIP2_PIX_FMT = tuple(f for f in PIX_FMT if f not in CLIP_PIX_FMT)
+CLIP2_SIGMAS = ("const", "auto*1.25", "nlf*0.8")
+PIPELINES = ("live", "clip", "clip2")
+YUV420_2D = ("nv12", "p010")                             # 2-D surfaces [H*3/2, pitch], always with row_pitch > width here
+YUV_1D = ("yuv420p", "uyvy422", "yuv444p10le")           # 1-D arrays of the tight frame's samples: frame_shape is required
+RGB_SURFACE = ("bgra", "rgba64le", "x2rgb10le", "gbrap10le", "rgb0")
+ALPHA = ("bgra", "rgba64le", "gbrap10le")
+
+SIZES = collections.OrderedDict([("16x24", ((16, 24), None)), ("32x48", ((32, 48), None)), ("30x42r", ((30, 42), "reflect")),
+                                 ("6x10r", ((6, 10), "reflect"))])
+SIGMAS = collections.OrderedDict([("const", (30 / 255.0, 1.0)), ("auto", ("auto", 1.0)), ("auto*1.25", ("auto", 1.25)), ("nlf", ("nlf", 1.0)),
+                                  ("nlf*0.8", ("nlf", 0.8)), ("curve", ("curve", 1.0))])
+CURVE_AB = (2.0e-3, 1.0e-4)                              # NoiseCurve.from_model(a, b) of the 'curve' value
+CUTS = ("none", "manual", "auto")
+STRENGTHS = collections.OrderedDict([("1", 1.0), ("0.5", 0.5), ("0.4/1", (0.4, 1.0)), ("0", 0.0)])
+DITHERS = ("none", "ordered", "random")
+DITHER_SEED = 0x5EED1234
+DEPTHS = (1, 2, 3)
+OVERLAPS = collections.OrderedDict([("default", None), ("off", False), ("on", True)])
+COLOURS = collections.OrderedDict([("default", None), ("bt601-full", dict(matrix="bt601", full_range=True)),
+                                   ("bt2020-limited", dict(matrix="bt2020", full_range=False)), ("rgb-limited", dict(full_range=False))])
+FRAME_SHAPE = ("given", "none")
+STREAMS = ("A", "B", "C")
+CLIPS = collections.OrderedDict([("3-4-3", (3, 4, 3)), ("1-5-2-5-1", (1, 5, 2, 5, 1))])
+PITCH_EXTRA = 8                                          # samples a row of an nv12 / p010 surface is longer than the picture
+
+FACTORS = collections.OrderedDict([
+    ("pix_fmt", PIX_FMT), ("size", tuple(SIZES)), ("sigma", tuple(SIGMAS)), ("cuts", CUTS), ("strength", tuple(STRENGTHS)), ("dither", DITHERS),
+    ("depth", DEPTHS), ("overlap", tuple(OVERLAPS)), ("colour", tuple(COLOURS)), ("frame_shape", FRAME_SHAPE), ("stream", STREAMS),
+    ("clips", tuple(CLIPS))])
+LIVE_FACTORS = ("pix_fmt", "size", "sigma", "cuts", "strength", "dither", "depth", "overlap", "colour", "frame_shape", "stream")
+CLIP_FACTORS = ("pix_fmt", "size", "sigma", "cuts", "strength", "dither", "depth", "colour", "clips")
+CAPS = {"live": 64, "clip": 32, "clip2": 32}
+
+
+def factors(pipeline):
+    """-> OrderedDict factor -> values of one pipeline's table"""
+    names = LIVE_FACTORS if pipeline == "live" else CLIP_FACTORS
+    out = collections.OrderedDict((n, FACTORS[n]) for n in names)
+    out["pix_fmt"] = {"live": LIVE_PIX_FMT, "clip": CLIP_PIX_FMT, "clip2": CLIP2_PIX_FMT}[pipeline]
+    if pipeline == "clip2":
+        out["sigma"] = CLIP2_SIGMAS
+    return out
+
+
+def as_dict(row, pipeline):
+    names = LIVE_FACTORS if pipeline == "live" else CLIP_FACTORS
+    assert len(row) == len(names), row
+    return dict(zip(names, row))
+
+
+def refusal(row, pipeline):
+    """row: a dict, possibly partial (a rule speaks once all its factors are there) -> why the product refuses it, or None"""
+    g = row.get
+    fmt, colour = g("pix_fmt"), g("colour")
+    if fmt is not None and colour is not None and colour != "default":
+        if fmt == "rgb24":
+            return "rgb24 takes no colour"
+        if fmt in RGB_SURFACE and colour != "rgb-limited":
+            return "an RGB surface's colour may carry full_range only"
+    if pipeline == "live" and fmt in YUV_1D and g("frame_shape") == "none":
+        return "1-D frames do not say their size: frame_shape is required"
+    if pipeline != "live" and g("cuts") == "manual":
+        return "ClipPipeline has no per-frame cut"
+    if pipeline == "live" and g("stream") == "C" and fmt is not None:
+        if fmt in YUV_1D or fmt in YUV420_2D:
+            return "the frame size is fixed at construction (frame_shape; colour.width and row_pitch of a pitched surface)"
+        if fmt in RGB_SURFACE and g("frame_shape") == "given":
+            return "frame_shape fixes an RGB surface's size"
+    return None
+
+
+def vacuous(row, pipeline):
+    """what the product takes and the matrix leaves out -> the reason, or None"""
+    g = row.get
+    fmt, colour = g("pix_fmt"), g("colour")
+    if fmt in YUV420_2D + YUV_1D and colour == "rgb-limited":
+        return "{'full_range': False} is a YUV surface's default: the row would repeat colour 'default'"
+    return None
+
+
+def valid(row, pipeline):
+    return refusal(row, pipeline) is None and vacuous(row, pipeline) is None
+
+
+# ---- what the keys stand for -------------------------------------------------------------------------------------------------------------
+def size_of(row):
+    """-> ((H, W), pad)"""
+    return SIZES[row["size"]]
+
+
+def other_size(row):
+    """stream shape C: the no-pad size the row does not have ((16, 24) for the rows at a reflect size)"""
+    return (32, 48) if size_of(row)[0] == (16, 24) else (16, 24)
+
+
+def sample_bytes(fmt):
+    return 2 if fmt == "p010" else 1
+
+
+def colour_of(row, size=None):
+    """the ``colour`` argument; nv12 / p010: always a pitched surface, rows PITCH_EXTRA samples longer than the picture"""
+    c = COLOURS[row["colour"]]
+    c = None if c is None else dict(c)
+    if row["pix_fmt"] in YUV420_2D:
+        w = (size or size_of(row)[0])[1]
+        c = dict(c or {}, row_pitch=(w + PITCH_EXTRA) * sample_bytes(row["pix_fmt"]), width=w)
+    return c
+
+
+def sigma_of(row):
+    """-> (sigma, sigma_gain); imports the package for the 'curve' value only"""
+    s, gain = SIGMAS[row["sigma"]]
+    if s == "curve":
+        from bsvd_amd.frame_io import NoiseCurve
+        s = NoiseCurve.from_model(*CURVE_AB)
+    return s, gain
+
+
+def one_d(row, pipeline):
+    """are the row's frames 1-D arrays of samples?  The three YUV surfaces always; an RGB surface of a LiveStream row with frame_shape"""
+    return row["pix_fmt"] in YUV_1D or (pipeline == "live" and row["pix_fmt"] in RGB_SURFACE and row["frame_shape"] == "given")
+
+
+def array_spec(row, pipeline, size=None):
+    """-> (shape, numpy dtype name) of one frame of the row as the pipelines take it"""
+    fmt = row["pix_fmt"]
+    H, W = size or size_of(row)[0]
+    if fmt == "rgb24":
+        return (H, W, 3), "uint8"
+    if fmt in YUV420_2D:
+        return (H * 3 // 2, W + PITCH_EXTRA), "uint8" if fmt == "nv12" else "uint16"
+    if fmt in YUV_1D:
+        return {"yuv420p": ((H * W * 3 // 2,), "uint8"), "uyvy422": ((H * W * 2,), "uint8"), "yuv444p10le": ((H * W * 3,), "uint16")}[fmt]
+    shape, dtype = {"bgra": ((H, W, 4), "uint8"), "rgb0": ((H, W, 4), "uint8"), "rgba64le": ((H, W, 4), "uint16"), "x2rgb10le": ((H, W), "uint32"),
+                    "gbrap10le": ((4, H, W), "uint16")}[fmt]
+    if one_d(row, pipeline):
+        n = 1
+        for d in shape:
+            n *= d
+        shape = (n,)
+    return shape, dtype
+
+
+def constructor_kw(row, pipeline, size=None):
+    """the keywords of LiveStream / ClipPipeline for a row (model excluded)"""
+    (hw, pad) = size_of(row)
+    hw = size or hw
+    sigma, gain = sigma_of(row)
+    kw = dict(sigma=sigma, sigma_gain=gain, depth=row["depth"], pix_fmt=row["pix_fmt"], colour=colour_of(row, hw), pad=pad,
+              cuts="auto" if row["cuts"] == "auto" else None, strength=STRENGTHS[row["strength"]],
+              dither=None if row["dither"] == "none" else row["dither"], dither_seed=DITHER_SEED)
+    if pipeline == "live":
+        kw["overlap_blocks"] = OVERLAPS[row["overlap"]]
+        kw["frame_shape"] = hw if row["frame_shape"] == "given" else None
+    else:
+        kw["frame_shape"] = hw if row["pix_fmt"] in YUV_1D else None
+    return kw
+
+
+# ---- pairs and the generator -------------------------------------------------------------------------------------------------------------
+def _complete(partial, pipeline, fac, order):
+    """a valid full row that extends ``partial`` (depth-first over ``order``), or None"""
+    if not valid(partial, pipeline):
+        return None
+    rest = [n for n in order if n not in partial]
+    if not rest:
+        return dict(partial)
+    for v in fac[rest[0]]:
+        got = _complete(dict(partial, **{rest[0]: v}), pipeline, fac, order)
+        if got is not None:
+            return got
+    return None
+
+
+def pairs_of(row):
+    items = sorted(row.items(), key=lambda kv: kv[0])
+    return {(a, b) for a, b in itertools.combinations(items, 2)}
+
+
+def valid_pairs(pipeline):
+    """every pair of factor values that some valid row holds (by search over the rules' partial form; the CPU test enumerates them again
+    from full rows alone)"""
+    fac = factors(pipeline)
+    out = set()
+    for (fa, va), (fb, vb) in itertools.combinations([(n, v) for n, vs in fac.items() for v in vs], 2):
+        if fa != fb and _complete({fa: va, fb: vb}, pipeline, fac, list(fac)) is not None:
+            out.add(tuple(sorted([(fa, va), (fb, vb)], key=lambda kv: kv[0])))
+    return out
+
+
+def finds_cuts(row):
+    """can the detector of a cuts='auto' row find a cut?  Not in a 6 x 10 picture: it holds no 16 x 16 block, every score is 0.0 and
+    the row checks exactly that (no cut, every score zero, the frames of the run without cuts)"""
+    return row["cuts"] == "auto" and row["size"] != "6x10r"
+
+
+MANDATORY = {
+    "live": (("rgba64le", "30x42r", "nlf*0.8", "manual", "0.4/1", "random", 3, "default", "default", "none", "B"),
+             ("p010", "30x42r", "nlf*0.8", "auto", "0.4/1", "random", 3, "default", "bt2020-limited", "none", "B")),
+    "clip": (("rgba64le", "30x42r", "nlf*0.8", "auto", "0.4/1", "random", 3, "default", "3-4-3"),
+             ("p010", "30x42r", "nlf*0.8", "auto", "0.4/1", "random", 3, "bt2020-limited", "1-5-2-5-1")),
+    "clip2": (),
+}
+SEED = 7            # the first seed at which the three tables hold their caps (55, 32 and 30 rows)
+CANDIDATES = 40
+
+
+def generate(pipeline):
+    """the greedy generator of the committed tables: the mandatory rows first; then, until no valid pair is uncovered, CANDIDATES rows are
+    grown from an uncovered pair -- the other factors in shuffled order, each given the value that covers most uncovered pairs with what
+    the row already holds, among those that leave it completable -- and the candidate that covers most is kept.  Fixed seed."""
+    rng = random.Random(SEED)
+    fac = factors(pipeline)
+    names = list(fac)
+    todo = valid_pairs(pipeline)
+    rows = []
+    for r in MANDATORY[pipeline]:
+        rows.append(tuple(r))
+        todo -= pairs_of(as_dict(r, pipeline))
+    while todo:
+        best, best_gain = None, -1
+        for _ in range(CANDIDATES):
+            seed = rng.choice(sorted(todo, key=repr))
+            row = dict(seed)
+            order = [n for n in names if n not in row]
+            rng.shuffle(order)
+            for n in order:
+                scored = []
+                for v in fac[n]:
+                    trial = dict(row, **{n: v})
+                    if _complete(trial, pipeline, fac, names) is None:
+                        continue
+                    gain = sum(1 for k, w in row.items() if tuple(sorted([(n, v), (k, w)], key=lambda kv: kv[0])) in todo)
+                    scored.append((gain, rng.random(), v))
+                row[n] = max(scored)[2]
+            gain = len(pairs_of(row) & todo)
+            if gain > best_gain:
+                best, best_gain = row, gain
+        rows.append(tuple(best[n] for n in names))
+        todo -= pairs_of(best)
+    return rows
+
+
+# generate('live'): 55 rows over 837 valid pairs
+LIVE_ROWS = (
+    ('rgba64le', '30x42r', 'nlf*0.8', 'manual', '0.4/1', 'random', 3, 'default', 'default', 'none', 'B'),
+    ('p010', '30x42r', 'nlf*0.8', 'auto', '0.4/1', 'random', 3, 'default', 'bt2020-limited', 'none', 'B'),
+    ('gbrap10le', '30x42r', 'auto', 'none', '1', 'none', 2, 'off', 'rgb-limited', 'given', 'A'),
+    ('rgb24', '16x24', 'curve', 'auto', '0', 'ordered', 1, 'on', 'default', 'given', 'C'),
+    ('nv12', '32x48', 'nlf', 'none', '0.5', 'ordered', 3, 'on', 'bt601-full', 'none', 'A'),
+    ('yuv444p10le', '6x10r', 'const', 'manual', '0.5', 'none', 1, 'off', 'bt2020-limited', 'given', 'B'),
+    ('bgra', '6x10r', 'auto*1.25', 'manual', '0', 'ordered', 2, 'default', 'rgb-limited', 'none', 'C'),
+    ('uyvy422', '32x48', 'curve', 'manual', '1', 'random', 1, 'default', 'bt601-full', 'given', 'A'),
+    ('uyvy422', '16x24', 'auto*1.25', 'none', '0.4/1', 'none', 2, 'on', 'bt2020-limited', 'given', 'B'),
+    ('bgra', '16x24', 'const', 'auto', '1', 'none', 3, 'off', 'default', 'none', 'C'),
+    ('yuv420p', '32x48', 'nlf*0.8', 'auto', '0', 'none', 2, 'off', 'bt601-full', 'given', 'A'),
+    ('gbrap10le', '6x10r', 'nlf*0.8', 'none', '0.5', 'random', 1, 'on', 'rgb-limited', 'none', 'C'),
+    ('yuv420p', '30x42r', 'nlf', 'manual', '1', 'ordered', 1, 'on', 'bt2020-limited', 'given', 'B'),
+    ('rgba64le', '6x10r', 'curve', 'auto', '0.4/1', 'ordered', 3, 'off', 'rgb-limited', 'given', 'A'),
+    ('yuv444p10le', '16x24', 'auto', 'auto', '0.5', 'random', 2, 'default', 'default', 'given', 'A'),
+    ('p010', '32x48', 'auto', 'manual', '0.4/1', 'ordered', 1, 'on', 'bt601-full', 'none', 'B'),
+    ('nv12', '30x42r', 'auto*1.25', 'auto', '0', 'random', 1, 'off', 'default', 'given', 'B'),
+    ('p010', '6x10r', 'nlf', 'none', '0', 'none', 2, 'off', 'default', 'given', 'A'),
+    ('rgb24', '30x42r', 'curve', 'none', '0.5', 'none', 2, 'default', 'default', 'none', 'B'),
+    ('rgba64le', '32x48', 'const', 'none', '0', 'none', 2, 'on', 'rgb-limited', 'none', 'C'),
+    ('gbrap10le', '16x24', 'nlf', 'manual', '0', 'random', 3, 'default', 'rgb-limited', 'given', 'B'),
+    ('yuv444p10le', '32x48', 'auto*1.25', 'none', '1', 'ordered', 3, 'on', 'bt601-full', 'given', 'A'),
+    ('nv12', '16x24', 'const', 'manual', '0.4/1', 'none', 2, 'default', 'bt2020-limited', 'given', 'A'),
+    ('uyvy422', '6x10r', 'auto', 'auto', '0', 'ordered', 3, 'off', 'bt2020-limited', 'given', 'B'),
+    ('bgra', '32x48', 'nlf', 'auto', '0.4/1', 'random', 1, 'on', 'default', 'none', 'C'),
+    ('yuv420p', '30x42r', 'const', 'none', '0.5', 'random', 3, 'default', 'bt601-full', 'given', 'A'),
+    ('rgb24', '6x10r', 'nlf*0.8', 'manual', '1', 'ordered', 3, 'off', 'default', 'none', 'A'),
+    ('gbrap10le', '32x48', 'const', 'auto', '0.4/1', 'ordered', 2, 'off', 'default', 'none', 'A'),
+    ('bgra', '30x42r', 'auto', 'none', '0.5', 'random', 3, 'default', 'rgb-limited', 'given', 'B'),
+    ('p010', '16x24', 'auto*1.25', 'auto', '0.5', 'ordered', 2, 'on', 'bt601-full', 'none', 'A'),
+    ('rgb24', '32x48', 'auto', 'none', '0.4/1', 'random', 2, 'off', 'default', 'none', 'C'),
+    ('rgba64le', '16x24', 'nlf', 'manual', '0.5', 'random', 1, 'default', 'default', 'none', 'B'),
+    ('uyvy422', '30x42r', 'nlf', 'auto', '0.5', 'none', 3, 'off', 'default', 'given', 'B'),
+    ('yuv420p', '16x24', 'curve', 'manual', '0.4/1', 'random', 3, 'off', 'bt2020-limited', 'given', 'B'),
+    ('nv12', '6x10r', 'curve', 'auto', '1', 'ordered', 3, 'default', 'bt601-full', 'given', 'B'),
+    ('yuv444p10le', '30x42r', 'nlf', 'none', '0.4/1', 'ordered', 2, 'on', 'bt601-full', 'given', 'A'),
+    ('yuv444p10le', '16x24', 'nlf*0.8', 'none', '0', 'none', 1, 'off', 'bt601-full', 'given', 'B'),
+    ('yuv420p', '6x10r', 'auto', 'auto', '0.4/1', 'none', 1, 'off', 'default', 'given', 'A'),
+    ('p010', '32x48', 'const', 'none', '1', 'random', 3, 'on', 'bt2020-limited', 'none', 'A'),
+    ('rgba64le', '30x42r', 'auto*1.25', 'manual', '1', 'none', 2, 'off', 'rgb-limited', 'none', 'C'),
+    ('bgra', '30x42r', 'curve', 'manual', '1', 'random', 3, 'default', 'default', 'none', 'A'),
+    ('nv12', '30x42r', 'auto', 'auto', '0.5', 'random', 2, 'off', 'bt601-full', 'none', 'B'),
+    ('gbrap10le', '16x24', 'curve', 'none', '0.4/1', 'random', 2, 'default', 'rgb-limited', 'given', 'A'),
+    ('gbrap10le', '16x24', 'auto*1.25', 'none', '0.4/1', 'random', 1, 'on', 'rgb-limited', 'none', 'B'),
+    ('yuv420p', '32x48', 'auto*1.25', 'auto', '0', 'none', 1, 'default', 'default', 'given', 'A'),
+    ('rgb24', '16x24', 'auto*1.25', 'auto', '0', 'random', 1, 'off', 'default', 'none', 'A'),
+    ('p010', '30x42r', 'curve', 'auto', '1', 'ordered', 1, 'off', 'bt2020-limited', 'none', 'A'),
+    ('bgra', '16x24', 'nlf*0.8', 'manual', '1', 'random', 1, 'default', 'default', 'given', 'A'),
+    ('rgba64le', '16x24', 'auto', 'none', '0', 'random', 2, 'off', 'default', 'given', 'A'),
+    ('uyvy422', '30x42r', 'nlf*0.8', 'none', '1', 'random', 1, 'default', 'bt2020-limited', 'given', 'B'),
+    ('yuv444p10le', '30x42r', 'curve', 'manual', '0.5', 'ordered', 3, 'off', 'bt601-full', 'given', 'A'),
+    ('uyvy422', '30x42r', 'const', 'auto', '0.5', 'random', 1, 'off', 'bt601-full', 'given', 'B'),
+    ('rgb24', '6x10r', 'nlf', 'none', '0.5', 'none', 2, 'default', 'default', 'none', 'C'),
+    ('nv12', '16x24', 'nlf*0.8', 'none', '1', 'random', 1, 'on', 'bt2020-limited', 'given', 'A'),
+    ('rgb24', '32x48', 'const', 'none', '0', 'random', 3, 'default', 'default', 'given', 'B'),
+)
+# generate('clip'): 32 rows over 442 valid pairs
+CLIP_ROWS = (
+    ('rgba64le', '30x42r', 'nlf*0.8', 'auto', '0.4/1', 'random', 3, 'default', '3-4-3'),
+    ('p010', '30x42r', 'nlf*0.8', 'auto', '0.4/1', 'random', 3, 'bt2020-limited', '1-5-2-5-1'),
+    ('p010', '6x10r', 'auto', 'none', '0.5', 'ordered', 1, 'bt601-full', '3-4-3'),
+    ('rgb0', '16x24', 'auto*1.25', 'none', '1', 'none', 2, 'default', '1-5-2-5-1'),
+    ('x2rgb10le', '32x48', 'const', 'auto', '0', 'ordered', 2, 'rgb-limited', '1-5-2-5-1'),
+    ('x2rgb10le', '30x42r', 'curve', 'auto', '1', 'none', 1, 'rgb-limited', '3-4-3'),
+    ('rgba64le', '6x10r', 'nlf', 'none', '0', 'none', 3, 'rgb-limited', '1-5-2-5-1'),
+    ('rgb0', '32x48', 'nlf', 'none', '0.4/1', 'random', 1, 'default', '3-4-3'),
+    ('p010', '16x24', 'curve', 'auto', '0', 'random', 2, 'bt601-full', '3-4-3'),
+    ('rgb0', '6x10r', 'curve', 'auto', '0.5', 'ordered', 3, 'default', '1-5-2-5-1'),
+    ('p010', '32x48', 'const', 'none', '0.5', 'none', 2, 'bt2020-limited', '3-4-3'),
+    ('x2rgb10le', '16x24', 'nlf*0.8', 'none', '0.5', 'random', 1, 'rgb-limited', '1-5-2-5-1'),
+    ('rgba64le', '16x24', 'auto', 'auto', '0.4/1', 'ordered', 2, 'rgb-limited', '1-5-2-5-1'),
+    ('p010', '32x48', 'auto*1.25', 'none', '1', 'random', 3, 'bt601-full', '1-5-2-5-1'),
+    ('p010', '30x42r', 'auto*1.25', 'auto', '0', 'ordered', 1, 'bt2020-limited', '3-4-3'),
+    ('x2rgb10le', '6x10r', 'const', 'none', '0.4/1', 'random', 3, 'default', '3-4-3'),
+    ('p010', '6x10r', 'nlf', 'auto', '1', 'ordered', 2, 'bt2020-limited', '1-5-2-5-1'),
+    ('rgb0', '30x42r', 'auto', 'none', '0', 'random', 2, 'default', '3-4-3'),
+    ('p010', '30x42r', 'nlf*0.8', 'none', '0.4/1', 'none', 2, 'bt601-full', '1-5-2-5-1'),
+    ('rgba64le', '32x48', 'curve', 'none', '0.4/1', 'none', 1, 'default', '1-5-2-5-1'),
+    ('p010', '16x24', 'auto', 'none', '1', 'none', 3, 'bt2020-limited', '1-5-2-5-1'),
+    ('rgb0', '32x48', 'nlf*0.8', 'auto', '0', 'ordered', 1, 'rgb-limited', '1-5-2-5-1'),
+    ('rgba64le', '6x10r', 'auto*1.25', 'none', '0.5', 'ordered', 1, 'rgb-limited', '3-4-3'),
+    ('rgba64le', '30x42r', 'const', 'none', '1', 'random', 1, 'default', '3-4-3'),
+    ('x2rgb10le', '30x42r', 'nlf', 'auto', '0.5', 'none', 2, 'rgb-limited', '1-5-2-5-1'),
+    ('p010', '6x10r', 'nlf*0.8', 'auto', '1', 'random', 2, 'default', '3-4-3'),
+    ('p010', '16x24', 'nlf', 'auto', '1', 'ordered', 1, 'bt601-full', '3-4-3'),
+    ('rgb0', '16x24', 'const', 'none', '0.4/1', 'none', 1, 'default', '3-4-3'),
+    ('x2rgb10le', '32x48', 'auto', 'none', '0.4/1', 'ordered', 2, 'default', '1-5-2-5-1'),
+    ('x2rgb10le', '16x24', 'auto*1.25', 'auto', '0.4/1', 'ordered', 2, 'rgb-limited', '3-4-3'),
+    ('p010', '16x24', 'curve', 'auto', '1', 'ordered', 2, 'bt2020-limited', '3-4-3'),
+    ('p010', '30x42r', 'const', 'auto', '0.4/1', 'ordered', 3, 'bt601-full', '1-5-2-5-1'),
+)
+# generate('clip2'): 30 rows over 435 valid pairs
+CLIP2_ROWS = (
+    ('yuv444p10le', '6x10r', 'nlf*0.8', 'auto', '0', 'ordered', 3, 'default', '3-4-3'),
+    ('gbrap10le', '16x24', 'auto*1.25', 'auto', '0.5', 'none', 2, 'rgb-limited', '1-5-2-5-1'),
+    ('nv12', '30x42r', 'auto*1.25', 'none', '1', 'random', 1, 'bt2020-limited', '3-4-3'),
+    ('yuv420p', '32x48', 'const', 'none', '0.4/1', 'ordered', 2, 'bt601-full', '1-5-2-5-1'),
+    ('uyvy422', '32x48', 'nlf*0.8', 'auto', '0', 'random', 1, 'bt601-full', '1-5-2-5-1'),
+    ('bgra', '16x24', 'const', 'none', '0.4/1', 'none', 1, 'default', '3-4-3'),
+    ('rgb24', '30x42r', 'const', 'auto', '1', 'none', 3, 'default', '1-5-2-5-1'),
+    ('bgra', '6x10r', 'nlf*0.8', 'none', '0.5', 'random', 3, 'rgb-limited', '1-5-2-5-1'),
+    ('nv12', '6x10r', 'const', 'auto', '0', 'none', 2, 'bt2020-limited', '1-5-2-5-1'),
+    ('uyvy422', '16x24', 'auto*1.25', 'auto', '0.4/1', 'ordered', 3, 'bt2020-limited', '3-4-3'),
+    ('rgb24', '32x48', 'auto*1.25', 'none', '0.5', 'random', 2, 'default', '3-4-3'),
+    ('gbrap10le', '30x42r', 'nlf*0.8', 'none', '0.4/1', 'ordered', 1, 'rgb-limited', '3-4-3'),
+    ('yuv420p', '16x24', 'nlf*0.8', 'auto', '1', 'none', 3, 'bt601-full', '3-4-3'),
+    ('yuv444p10le', '30x42r', 'const', 'none', '0.5', 'random', 1, 'bt601-full', '1-5-2-5-1'),
+    ('bgra', '32x48', 'const', 'auto', '1', 'ordered', 2, 'rgb-limited', '1-5-2-5-1'),
+    ('nv12', '32x48', 'nlf*0.8', 'auto', '0.5', 'ordered', 3, 'bt2020-limited', '1-5-2-5-1'),
+    ('yuv420p', '6x10r', 'auto*1.25', 'none', '0', 'random', 1, 'bt2020-limited', '3-4-3'),
+    ('uyvy422', '30x42r', 'const', 'none', '0', 'none', 2, 'default', '3-4-3'),
+    ('yuv444p10le', '32x48', 'nlf*0.8', 'none', '0.4/1', 'none', 2, 'bt2020-limited', '3-4-3'),
+    ('gbrap10le', '6x10r', 'const', 'auto', '1', 'random', 3, 'default', '3-4-3'),
+    ('rgb24', '6x10r', 'nlf*0.8', 'none', '0.4/1', 'ordered', 1, 'default', '3-4-3'),
+    ('nv12', '16x24', 'auto*1.25', 'auto', '0.4/1', 'random', 2, 'bt601-full', '1-5-2-5-1'),
+    ('bgra', '30x42r', 'auto*1.25', 'none', '0', 'none', 1, 'rgb-limited', '3-4-3'),
+    ('yuv444p10le', '16x24', 'auto*1.25', 'none', '1', 'ordered', 3, 'bt601-full', '3-4-3'),
+    ('yuv420p', '30x42r', 'const', 'auto', '0.5', 'none', 2, 'default', '1-5-2-5-1'),
+    ('rgb24', '16x24', 'nlf*0.8', 'none', '0', 'random', 2, 'default', '3-4-3'),
+    ('uyvy422', '6x10r', 'auto*1.25', 'none', '1', 'ordered', 3, 'bt601-full', '1-5-2-5-1'),
+    ('gbrap10le', '32x48', 'auto*1.25', 'none', '0', 'random', 3, 'default', '1-5-2-5-1'),
+    ('uyvy422', '16x24', 'const', 'none', '0.5', 'ordered', 2, 'default', '3-4-3'),
+    ('nv12', '16x24', 'nlf*0.8', 'auto', '1', 'ordered', 1, 'default', '3-4-3'),
+)
+ROWS = {"live": LIVE_ROWS, "clip": CLIP_ROWS, "clip2": CLIP2_ROWS}
