@@ -2,7 +2,9 @@
 """4K (2160x3840) through the per-frame streaming API on one MI355X: the stream schedule's rings hold 155 GB -- the clip schedule
 of the same 36 frames would need more HBM than the chip has -- and the f16x3 kernels address a frame with 32-bit byte offsets,
 which a 4K 64-channel frame (2.12 GB) just fits.  Steady-state frames/s and a bitwise check of the first frames against the
-clip schedule on an interior crop (spatial locality, receptive field 96 px).   usage: python tools/stream_4k.py"""
+clip schedule on an interior crop (spatial locality, receptive field 96 px).  The crop says nothing of the frame's right and bottom
+edges -- the highest addresses the kernels form: those are checked layer by layer, against the CPU models at sampled pixels, by the `4k-`
+cases of tests/test_gpu_geometry.py (profiles/production_geometry.txt).   usage: python tools/stream_4k.py"""
 import sys, time
 import os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
