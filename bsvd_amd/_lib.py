@@ -29,7 +29,8 @@ EXPORTS = ("bsvd_abi_version", "bsvd_conv_args_size", "bsvd_build_info", "bsvd_l
            "bsvd_scene_grid", "bsvd_scene_diff",
            "bsvd_rgb_frame_bytes", "bsvd_rgb_to_planar", "bsvd_planar_to_rgb",
            "bsvd_blend_planar", "bsvd_planar_to_yuv420_crop_d", "bsvd_planar_to_yuv_crop_d", "bsvd_planar_to_rgb_d",
-           "bsvd_nlf_workspace_bytes", "bsvd_estimate_nlf", "bsvd_finish_nlf", "bsvd_fill_nlf_plane")
+           "bsvd_nlf_workspace_bytes", "bsvd_estimate_nlf", "bsvd_finish_nlf", "bsvd_fill_nlf_plane",
+           "bsvd_vst_build", "bsvd_vst_forward", "bsvd_vst_inverse")
 PIX_FMT = {"nv12": 0, "p010": 1}
 MATRIX = {"bt601": 0, "bt709": 1, "bt2020": 2}
 CHROMA = {"nearest": 0, "linear": 1}
@@ -46,6 +47,12 @@ SIGMA_MAX = SIGMA_BINS * SIGMA_K
 # bsvd_estimate_nlf: levels of the noise-level curve, bins per level (1 / 1024 of |r| each: NLF_BINS * NLF_K = SIGMA_MAX), samples a level needs
 NLF_LEVELS, NLF_BINS, NLF_MIN_COUNT = 16, 1024, 512
 NLF_K = 4 * SIGMA_K
+# bsvd_vst_build: a table set is G[0 .. 1024] at 0, sigma' at VST_SIGMA_AT, two zeros, R[0 .. 1023] at VST_R_AT; the default noise floor
+VST_KNOTS = 1025
+VST_SIGMA_AT, VST_R_AT = VST_KNOTS, VST_KNOTS + 3
+VST_TABLE_FLOATS = VST_R_AT + VST_KNOTS - 1
+VST_FLOOR = 0.5 / 255
+VST_FLOOR_MIN = 2.0 ** -10
 # the surfaces of bsvd_yuv_to_planar / bsvd_planar_to_yuv, by ffmpeg's names: (subsampling, layout, bits, high_bits).  PIX_FMT above stays
 # the table of the bsvd_yuv420_* entry points.
 YUV_FORMATS = {
@@ -260,6 +267,12 @@ def load():
     lib.bsvd_finish_nlf.argtypes = [vp, i32, f32, f32, f32, i32, vp, vp]
     lib.bsvd_fill_nlf_plane.restype = ctypes.c_int
     lib.bsvd_fill_nlf_plane.argtypes = [vp, i32, i32, i32, i32, i64, vp, vp]
+    lib.bsvd_vst_build.restype = ctypes.c_int
+    lib.bsvd_vst_build.argtypes = [vp, i32, f32, vp, vp]
+    lib.bsvd_vst_forward.restype = ctypes.c_int
+    lib.bsvd_vst_forward.argtypes = [vp, i32, i32, i32, i64, i32, vp, i64, vp]
+    lib.bsvd_vst_inverse.restype = ctypes.c_int
+    lib.bsvd_vst_inverse.argtypes = [vp, i64, i32, i32, i32, vp, i64, vp]
     lib.bsvd_scene_grid.restype = ctypes.c_int
     lib.bsvd_scene_grid.argtypes = [vp, i32, i32, i32, i32, i32, i64, vp, vp]
     lib.bsvd_scene_diff.restype = ctypes.c_int

@@ -24,7 +24,9 @@ from the converted frame and written into that frame's noise-map plane -- ``esti
 for it), a sequence of per-frame values, or a device tensor [T].  For sources whose noise depends on the signal level: ``'nlf'`` (a
 noise-level function per frame, sigma at sixteen levels of local intensity, estimated on the device, and a per-pixel noise map written from
 it -- ``estimate_noise_curve`` / ``fill_noise_map``) or a ``NoiseCurve`` the caller knows (``NoiseCurve.from_model(a, b)`` for a sensor's
-Poisson-Gaussian parameters).
+Poisson-Gaussian parameters).  The same curve as a variance-stabilising transform, which keeps the constant noise plane the reference's
+checkpoints were trained with: ``build_vst`` (the tables, on the device), ``vst_forward`` / ``vst_inverse`` (in place, around the network),
+``vst_sigma`` -- the pipelines' ``vst=``.
 
 Scene cuts: ``scene_scores`` (a 16 x 16 block grid of 8-bit luma sums per frame and its frame-to-frame difference, on the device, in
 integers) and ``scene_cuts`` (the rule on top, on the host) find the frames that start a new scene, for the ``cuts=`` / ``cut=`` arguments of
@@ -226,7 +228,8 @@ def estimate_noise_curve(x, picture=None, gain=1.0, clamp=(0.0, SIGMA_MAX), min_
 
     What is known: on synthetic frames with sigma(I) = sqrt(a I + b) noise quantised to 8 bits the levels away from the clipped ends are
     within the bounds of profiles/noise_curve.txt.  Nothing has been measured on real footage, and a per-pixel noise map is outside what
-    the reference's checkpoints were trained on (a constant plane)."""
+    the reference's checkpoints were trained on (a constant plane): ``build_vst`` / the pipelines' ``vst=`` turn the same curve into a
+    variance-stabilising transform, which keeps the constant plane."""
     lo, hi = _check_clamp(clamp)
     gain = _check_gain(gain)
     min_count = _check_min_count(min_count)
@@ -274,6 +277,112 @@ def fill_noise_map(x, curve):
     with torch.cuda.device(x.device):
         _lib.check(lib.bsvd_fill_nlf_plane(x.data_ptr(), T, C - 1, Hp, Wp, C * Hp * Wp, curve.data_ptr(), _stream()), "bsvd_fill_nlf_plane")
     return x
+
+
+# ---------------------------------------------------------------------------------------------------
+# the variance-stabilising transform of a noise curve (include/bsvd_hip.h, bsvd_vst_build / bsvd_vst_forward / bsvd_vst_inverse)
+
+VST_KNOTS = _lib.VST_KNOTS
+VST_TABLE_FLOATS = _lib.VST_TABLE_FLOATS
+VST_FLOOR = _lib.VST_FLOOR
+
+
+def check_vst_floor(floor):
+    """``floor``: the least sigma the transform divides by, in [2^-10, 1] -> float; ValueError otherwise"""
+    try:
+        f = float(floor)
+    except (TypeError, ValueError):
+        raise ValueError("vst_floor: expected a number in [2^-10, 1], got %r" % (floor,)) from None
+    if isinstance(floor, bool) or not (_lib.VST_FLOOR_MIN <= f <= 1.0):
+        raise ValueError("vst_floor %r: must lie in [2^-10, 1] (the tables' knots stay apart and their reciprocals finite)" % (floor,))
+    return f
+
+
+def _vst_tables(tables, T, device, what):
+    """a table tensor [1 | T, VST_TABLE_FLOATS] -> the table stride in sets (0: shared)"""
+    if (not isinstance(tables, torch.Tensor) or tables.dtype != torch.float32 or tables.device != device or tables.dim() != 2
+            or tables.shape[1] != VST_TABLE_FLOATS or tables.shape[0] not in (1, T) or not tables.is_contiguous()):
+        raise ValueError("%s: tables must be a contiguous float32 tensor [1,%d] (shared) or [%d,%d] (per frame) on %s (build_vst)"
+                         % (what, VST_TABLE_FLOATS, T, VST_TABLE_FLOATS, device))
+    return 0 if tables.shape[0] == 1 else 1
+
+
+def build_vst(curve, floor=VST_FLOOR, out=None):
+    """curve: a ``NoiseCurve`` (n = 1; ``device=`` of the current HIP device) or an fp32 device tensor [n,16] (``estimate_noise_curve``)
+    -> fp32 device tensor [n, VST_TABLE_FLOATS]: the tables of the variance-stabilising transform of each curve, built on the device, not
+    synchronised with the host.  With the curve clamped to [``floor``, 1] and interpolated between the level centres as ``fill_noise_map``
+    does, g(I) ~ integral dI / sigma(I) at 1025 knots over [0, 1] (g(0) = 0, g(1) = 1), the reciprocal rise of every interval, and sigma'
+    = the harmonic mean of the clamped curve: the one standard deviation the noise has after ``vst_forward`` (``vst_sigma``).  Built in
+    double in a fixed order: bit-reproducible (include/bsvd_hip.h states it operation by operation).  ``out``: write into this tensor.
+
+    What is known: on synthetic sigma(I) = sqrt(a I + b) noise the transformed frames are as flat as ``estimate_noise_curve`` can tell
+    (profiles/vst.txt).  No trained checkpoint has been run through it: the effect on denoising quality has not been measured, and nothing
+    has been measured on real footage.  The transform changes the tone curve the network sees."""
+    floor = check_vst_floor(floor)
+    lib = require_hip()
+    if isinstance(curve, NoiseCurve):
+        curve = torch.tensor([curve.values], dtype=torch.float32).to(out.device if out is not None else torch.device("cuda", torch.cuda.current_device()))
+    if (not isinstance(curve, torch.Tensor) or curve.dtype != torch.float32 or not curve.is_cuda or curve.dim() != 2
+            or curve.shape[1] != NLF_LEVELS or curve.shape[0] < 1 or not curve.is_contiguous()):
+        raise ValueError("build_vst: expected a NoiseCurve or a contiguous float32 device tensor [n,%d]" % NLF_LEVELS)
+    n = curve.shape[0]
+    if out is None:
+        out = torch.empty((n, VST_TABLE_FLOATS), dtype=torch.float32, device=curve.device)
+    elif _vst_tables(out, n, curve.device, "build_vst(out=)") != (0 if n == 1 else 1):
+        raise ValueError("build_vst(out=): %d table sets for %d curves" % (out.shape[0], n))
+    with torch.cuda.device(curve.device):
+        _lib.check(lib.bsvd_vst_build(curve.data_ptr(), n, floor, out.data_ptr(), _stream()), "bsvd_vst_build")
+    return out
+
+
+def vst_sigma(tables):
+    """tables: ``build_vst``'s [n, VST_TABLE_FLOATS] -> a device view [n] of the sigma' values (not synchronised with the host)"""
+    if not isinstance(tables, torch.Tensor) or tables.dim() != 2 or tables.shape[1] != VST_TABLE_FLOATS:
+        raise ValueError("vst_sigma: expected build_vst's tensor [n,%d]" % VST_TABLE_FLOATS)
+    return tables[:, _lib.VST_SIGMA_AT]
+
+
+def vst_forward(x, tables, fill_plane=True):
+    """x: fp32 device tensor [T,C>=3,Hp,Wp], the tensor the ``*_to_input`` functions build; tables: ``build_vst``'s [1, ...] (one set for
+    all frames) or [T, ...] (frame t uses set t).  In place, on the device: planes 0 .. 2 go through the forward transform (piecewise
+    linear between the knots; values outside [0, 1] continue on the end intervals' lines, NaN stays NaN), and with ``fill_plane`` (needs
+    C >= 4) every element of the last plane of frame t becomes that frame's sigma' -- the constant noise plane the reference's checkpoints
+    were trained with.  ``fill_plane=False``: no plane is written (a blind model has none).  Returns ``x``."""
+    T, C, Hp, Wp = _planes(x, "vst_forward")
+    if C < 3:
+        raise ValueError("vst_forward: the transform takes the three colour planes, x has %d" % C)
+    if fill_plane and C < 4:
+        raise ValueError("vst_forward(fill_plane=True): x needs a plane behind its colour planes, it has %d (a blind model: fill_plane=False)" % C)
+    stride = _vst_tables(tables, T, x.device, "vst_forward")
+    lib = require_hip()
+    with torch.cuda.device(x.device):
+        _lib.check(lib.bsvd_vst_forward(x.data_ptr(), T, Hp, Wp, C * Hp * Wp, C - 1 if fill_plane else -1, tables.data_ptr(), stride, _stream()),
+                   "bsvd_vst_forward")
+    return x
+
+
+def vst_inverse(y, tables):
+    """y: fp32 device tensor [T,C>=3,Hp,Wp] (the network's output: C = 3); tables: as for ``vst_forward``.  Planes 0 .. 2 go back through
+    the inverse transform, in place, on the device.  The inverse is the algebraic one: a nonlinear inverse of a denoised mean is biased
+    where the curve bends sharply relative to sigma', and no unbiased-inverse correction is applied.  Returns ``y``."""
+    T, C, Hp, Wp = _planes(y, "vst_inverse")
+    if C < 3:
+        raise ValueError("vst_inverse: the transform takes the three colour planes, y has %d" % C)
+    stride = _vst_tables(tables, T, y.device, "vst_inverse")
+    lib = require_hip()
+    with torch.cuda.device(y.device):
+        _lib.check(lib.bsvd_vst_inverse(y.data_ptr(), C * Hp * Wp, T, Hp, Wp, tables.data_ptr(), stride, _stream()), "bsvd_vst_inverse")
+    return y
+
+
+def vst_identity(curve, floor=VST_FLOOR):
+    """curve: a ``NoiseCurve`` -> the one value all sixteen levels have after the clamp to [floor, 1] (in fp32), as a float, or None.
+    With one value the transform is the identity and sigma' is that value: the pipelines launch nothing then.  Needs no device."""
+    import struct
+    floor = check_vst_floor(floor)
+    f32 = lambda v: struct.unpack("f", struct.pack("f", v))[0]
+    vals = {min(max(f32(v), f32(floor)), 1.0) for v in curve.values}
+    return vals.pop() if len(vals) == 1 else None
 
 
 def _with_sigma(y, mode, picture, gain):

@@ -39,6 +39,13 @@ on the signal level: 'nlf' -- every frame's own noise-level function, sigma at s
 written from it (``frame_io.estimate_noise_curve`` / ``fill_noise_map``; ``LiveStream.last_noise_curve``: 64 bytes that come down with the
 frame) -- or a ``frame_io.NoiseCurve`` the caller knows.
 
+``vst`` (with ``sigma=None``) is the remedy for signal-dependent noise that stays inside what the reference's checkpoints were trained on:
+a variance-stabilising transform.  The colour planes are remapped by the curve's g(I) ~ integral dI / sigma(I) before the network
+(``frame_io.build_vst`` / ``vst_forward``), the noise plane is the one sigma' the noise then has everywhere, and the result is mapped back
+(``vst_inverse``) before the strength blend and the encoder.  A ``frame_io.NoiseCurve``: one table set for the stream; 'scene': the frame
+that starts a scene gives the curve (``frame_io.estimate_noise_curve``) and every later frame of the scene uses its tables.  No trained
+checkpoint has been run through it: its effect on denoising quality is not known.
+
 ``cuts`` is what the pipelines know about scene cuts: None (nothing: the footage is one scene, as before) or 'auto' -- every frame is scored
 against the one before it on the device (``frame_io.scene_scores`` / ``scene_cuts``; ``cut_threshold``) and a frame that scores as a scene
 start is fed with ``cut=True``: no temporal-fusion conv mixes the two scenes, nothing is flushed, latency is unchanged.  A caller who knows
@@ -50,10 +57,11 @@ import numpy as np
 import torch
 
 from . import _lib
-from .frame_io import (CUT_THRESHOLD, _check_gain, _luma_weights, _sigma_mode, _yuv_desc, _yuv_surface, blend_output, check_cut_threshold, check_dither,
-                       check_strength, cut_scores, estimate_noise_curve, fill_noise_map, frames_to_input, network_size,
-                       output_to_frames, output_to_rgb, output_to_yuv, output_to_yuv420, rgb_frame_bytes, rgb_to_input, scene_cuts, scene_scores,
-                       yuv420_frame_bytes, yuv420_picture_bytes, yuv420_to_input, yuv_to_input)
+from .frame_io import (CUT_THRESHOLD, VST_FLOOR, VST_TABLE_FLOATS, NoiseCurve, _check_gain, _luma_weights, _sigma_mode, _yuv_desc, _yuv_surface, blend_output,
+                       build_vst, check_cut_threshold, check_dither, check_strength, check_vst_floor, cut_scores, estimate_noise_curve, fill_noise_map,
+                       frames_to_input, network_size, output_to_frames, output_to_rgb, output_to_yuv, output_to_yuv420, rgb_frame_bytes, rgb_to_input,
+                       scene_cuts, scene_scores, vst_forward, vst_identity, vst_inverse, vst_sigma, yuv420_frame_bytes, yuv420_picture_bytes,
+                       yuv420_to_input, yuv_to_input)
 
 Colour = collections.namedtuple("Colour", "matrix full_range chroma row_pitch width", defaults=("bt709", False, "linear", None, None))
 Colour.__doc__ = """How a YUV surface is to be read and written: matrix 'bt601' | 'bt709' | 'bt2020', full_range (False = limited / "TV"
@@ -324,6 +332,68 @@ class _SourceRing:
         self.fed = self.emitted = 0
 
 
+class _TableRing:
+    """LiveStream(vst='scene')'s table sets: the set frame k was transformed with waits on the device until frame k's result emerges and is
+    mapped back with it, as the alpha codes do in ``_AlphaRing`` and by the same bookkeeping -- ``sets`` slots (>= latency + depth) of
+    [1, VST_TABLE_FLOATS], written in feed order, read in the same order when the frames come out, through ``cut=True``, ``cuts='auto'``
+    and ``flush()``.  Allocated once with the slots."""
+
+    def __init__(self, sets, device):
+        self.buf = torch.empty((sets, 1, VST_TABLE_FLOATS), dtype=torch.float32, device=device)
+        self.fed = self.emitted = 0
+
+    def next_in(self):
+        self.fed += 1
+        return self.buf[(self.fed - 1) % self.buf.shape[0]]
+
+    def next_out(self):
+        if self.emitted >= self.fed:
+            raise RuntimeError("table ring: frame %d comes out before it went in" % self.emitted)
+        self.emitted += 1
+        return self.buf[(self.emitted - 1) % self.buf.shape[0]]
+
+    def reset(self):
+        self.fed = self.emitted = 0
+
+
+class _Vst:
+    """the pipelines' ``vst``: None, a NoiseCurve or 'scene', with ``vst_floor``.  Checked before anything touches a device.  ``active``:
+    the transform runs; ``scene``: its curve is estimated at every scene start; ``fills``: the model has a noise plane for sigma';
+    ``sigma_in``: what the decode is asked to put into that plane (the caller's ``sigma`` with vst=None: no kernel, no buffer and no
+    argument more than before; the one value of a curve that is flat after the clamp, whose transform is the identity; otherwise 0,
+    overwritten by the forward transform)."""
+
+    def __init__(self, model, vst, vst_floor, sigma, what):
+        self.floor = check_vst_floor(vst_floor)
+        self.curve = self.shared = None
+        self.active = self.scene = False
+        self.sigma_in = sigma
+        self.fills = False
+        if vst is None:                                       # the defaults: the model is not looked at
+            return
+        if sigma is not None:
+            raise ValueError("%s(vst=...): sigma must be None (the noise plane is the transform's sigma'), got %r" % (what, sigma))
+        self.fills = model.net.net_in_ch != 3
+        if isinstance(vst, NoiseCurve):
+            flat = vst_identity(vst, self.floor)
+            if flat is not None:                              # the identity: the constant plane of sigma=<that value>, nothing launched
+                self.sigma_in = flat if self.fills else None
+                return
+            self.curve = vst
+        elif isinstance(vst, str) and vst == "scene":
+            self.scene = True
+        else:
+            raise ValueError("%s: vst must be None, a NoiseCurve or 'scene', got %r" % (what, vst))
+        self.active = True
+        self.sigma_in = 0.0 if self.fills else None
+
+    def shared_tables(self, device):
+        """vst=NoiseCurve: the stream's one table set [1, VST_TABLE_FLOATS], built at the first call"""
+        if self.shared is None or self.shared.device != device:
+            self.shared = build_vst(torch.tensor([self.curve.values], dtype=torch.float32).to(device), self.floor)
+        return self.shared
+
+
 class _Finish:
     """the pipelines' output finish: ``strength`` (a number or (luma, chroma)), ``dither`` / ``dither_seed``, the luma weights of the blend
     (``luma_matrix``: None = the stream's matrix for YUV formats, BT.709 for RGB ones).  Checked before anything touches a device.  With
@@ -397,6 +467,7 @@ class _Slot:
         self.ticket = None          # the in-flight clip occupying this slot
         self.dev_sigma = self.pin_sigma = None      # LiveStream(sigma='auto'): the step's estimate, 4 bytes beside the frame
         self.dev_curve = self.pin_curve = None      # LiveStream(sigma='nlf'): the step's noise-level curve, 64 bytes beside the frame
+        self.dev_vsig = self.pin_vsig = None        # LiveStream(vst=...): the frame's sigma', 4 bytes beside the frame
         self.dev_alpha = None                       # ClipPipeline, formats with alpha: the clip's alpha plane [T,H,W], held like dev_out
 
 
@@ -436,16 +507,22 @@ class ClipPipeline:
     strength (a number or (luma, chroma), each in [0, 1]; default 1): how much of the denoising to keep -- the network's result is blended
     with the clip's own input on the device before it is encoded (``frame_io.blend_output``; luma weights: the stream's matrix, BT.709 for
     RGB formats, or ``luma_matrix``).  dither None | 'ordered' | 'random' with dither_seed: dither at the encoder's quantiser
-    (``frame_io.output_to_*``); the random pattern's frame index counts the frames submitted since construction.  The defaults launch
-    nothing new and give the bytes they gave."""
+    (``frame_io.output_to_*``); the random pattern's frame index counts the frames submitted since construction.
+    vst (with sigma=None) a ``frame_io.NoiseCurve`` | 'scene', vst_floor: the variance-stabilising transform of the module docstring around
+    the network.  'scene': the clip's scenes are its ``last_cuts`` with cuts='auto', otherwise the clip is one scene; each scene's curve is
+    estimated from its first frame alone (times sigma_gain), so a curve that drifts within a scene (auto-exposure) is not followed until
+    the next cut.  Table sets are per frame in one forward and one inverse launch; ``strength`` blends with the untransformed source.  A
+    blind model gets the transform and no plane.  What is known: ``frame_io.build_vst``.  The defaults launch nothing new and give the
+    bytes they gave."""
 
     def __init__(self, model, sigma=None, depth=2, pix_fmt="rgb24", colour=None, pad=None, frame_shape=None, sigma_gain=1.0, cuts=None,
-                 cut_threshold=CUT_THRESHOLD, strength=1.0, dither=None, dither_seed=0, luma_matrix=None):
+                 cut_threshold=CUT_THRESHOLD, strength=1.0, dither=None, dither_seed=0, luma_matrix=None, vst=None, vst_floor=VST_FLOOR):
         if depth < 1:
             raise ValueError("depth must be >= 1")
         self.auto_cuts, self.cut_threshold = _check_cuts_mode(cuts, cut_threshold, "ClipPipeline")
         self.last_cuts = None
         self.sigma_gain = _check_sigma(model, sigma, sigma_gain, "ClipPipeline")
+        self.vst = _Vst(model, vst, vst_floor, sigma, "ClipPipeline")
         self.fmt = _pixel_format(pix_fmt, colour, pad, frame_shape)
         self.finish = _Finish(self.fmt, strength, dither, dither_seed, luma_matrix)
         self.alpha = getattr(self.fmt, "has_alpha", False)       # the clip's alpha codes ride beside the clip, [T,H,W] on the device
@@ -482,21 +559,29 @@ class ClipPipeline:
             with torch.cuda.stream(self.comp):
                 self.comp.wait_event(slot.uploaded)
                 if self.alpha:
-                    x, slot.dev_alpha = self.fmt.to_input(slot.dev_in, geom, self.sigma, self.sigma_gain, alpha=True)
+                    x, slot.dev_alpha = self.fmt.to_input(slot.dev_in, geom, self.vst.sigma_in, self.sigma_gain, alpha=True)
                 else:
-                    x = self.fmt.to_input(slot.dev_in, geom, self.sigma, self.sigma_gain)
+                    x = self.fmt.to_input(slot.dev_in, geom, self.vst.sigma_in, self.sigma_gain)
                 T, _, H, W = x.shape
                 kw = {}
                 if self.auto_cuts:
                     self.last_cuts = scene_cuts(x, self.cut_threshold, picture=(geom.h, geom.w))
                     kw = dict(cuts=self.last_cuts)
+                src = x
+                if self.vst.active:
+                    if self.finish.blends:
+                        src = x[:, :3].clone()            # strength blends in the picture's own domain
+                    tables = self._clip_tables(x, geom)
+                    vst_forward(x, tables, fill_plane=self.vst.fills)
                 if self.model._pick_mode(T, H, W) == "clip":
                     y = self.model.clip_forward(x, **kw)
                 else:
                     y = self.model.streaming_forward(x, **kw)
                 y = y.float()
+                if self.vst.active:
+                    y = vst_inverse(y.contiguous(), tables)
                 if self.finish.blends:
-                    y = self.finish.blend(y.contiguous(), x)
+                    y = self.finish.blend(y.contiguous(), src)
                 kw = self.finish.dither_kw(T)
                 # held by the slot until its download completed
                 slot.dev_out = self.fmt.to_output(y, geom, alpha=slot.dev_alpha, **kw) if self.alpha else self.fmt.to_output(y, geom, **kw)
@@ -508,6 +593,18 @@ class ClipPipeline:
         slot.ticket = _Ticket(slot, self.fmt.dtype)
         self.pending.append(slot.ticket)
         return slot.ticket
+
+    def _clip_tables(self, x, geom):
+        """the clip's table sets: the stream's one set (vst=NoiseCurve), or with vst='scene' one set per frame, [T, VST_TABLE_FLOATS]: each
+        scene's tables, built from the curve of its first frame, repeated over its frames -- all of it on the device"""
+        if not self.vst.scene:
+            return self.vst.shared_tables(x.device)
+        T = x.shape[0]
+        starts = [0] + [int(c) for c in (self.last_cuts or []) if 0 < int(c) < T] if self.auto_cuts else [0]
+        first = x if len(starts) == T else x[starts].contiguous()
+        sets = build_vst(estimate_noise_curve(first, picture=(geom.h, geom.w), gain=self.sigma_gain), self.vst.floor)
+        scene_of = [sum(1 for s in starts[1:] if s <= t) for t in range(T)]
+        return sets if len(starts) == T else sets[scene_of].contiguous()
 
     def results(self):
         """Drains every clip submitted so far, in submission order."""
@@ -588,10 +685,26 @@ class LiveStream:
     (3 fp32 planes each: about 0.5 GB at 1080p) and is blended with frame k's result when that emerges ``latency`` feeds later
     (``frame_io.blend_output``), through ``cut=True`` and ``flush()`` like the alpha ring; the ring exists only when some strength is
     below 1, and nothing is allocated per feed.  The random dither's frame index counts the frames emitted since construction or the last
-    ``flush()``.  The defaults launch nothing new and give the bytes they gave."""
+    ``flush()``.
+
+    vst (with sigma=None) a ``frame_io.NoiseCurve`` | 'scene', vst_floor: the variance-stabilising transform of the module docstring, on
+    the compute stream: after the conversion, the source ring's copy of the untransformed planes and the cut decision come curve, build and
+    forward, then the pipeline step; what emerges goes through the inverse, then the strength blend (in the picture's own domain:
+    strength=0 still returns the source) and the encoder.  A NoiseCurve: one table set for the stream, built once; every frame's noise
+    plane is sigma'; a curve that is flat after the clamp to [vst_floor, 1] is the identity: nothing is launched and the plane is written
+    as sigma=<that value> writes it.  'scene': the frame that starts a scene -- the first feed after construction or ``flush()``, a
+    ``feed(frame, cut=True)`` frame, a frame cuts='auto' flags -- gets its curve from ``frame_io.estimate_noise_curve`` (times sigma_gain)
+    and a table set built from it; every later frame of the scene uses that set.  A scene's curve comes from its first frame alone: a curve
+    that drifts within a scene (auto-exposure) is not followed until the next cut.  Frame k's set waits for frame k's result in a ring of
+    ``latency + depth`` sets (8 KB each), like the alpha ring, allocated with the slots.  ``last_noise_curve`` ('scene') and
+    ``last_vst_sigma``: the scene's curve and the sigma' of the most recent input step ``feed`` has already waited for.  A blind model
+    gets the transform and no plane.  What is known: ``frame_io.build_vst`` -- nothing about denoising quality, nothing on real footage.
+
+    The defaults launch nothing new and give the bytes they gave."""
 
     def __init__(self, model, sigma=None, depth=2, overlap_blocks=None, frame_shape=None, pix_fmt="rgb24", colour=None, pad=None,
-                 sigma_gain=1.0, cuts=None, cut_threshold=CUT_THRESHOLD, strength=1.0, dither=None, dither_seed=0, luma_matrix=None):
+                 sigma_gain=1.0, cuts=None, cut_threshold=CUT_THRESHOLD, strength=1.0, dither=None, dither_seed=0, luma_matrix=None,
+                 vst=None, vst_floor=VST_FLOOR):
         """frame_shape: optional (H, W) of the frames to come (the picture, also with ``pad``) -- the overlap decision (and with it
         ``latency``) is then final at construction instead of at the first feed."""
         if depth < 1:
@@ -601,6 +714,10 @@ class LiveStream:
         self._grids = self._sad = self._pin_sad = None       # cuts='auto': two alternating grid buffers, the step's sum on the device and pinned
         self._have_prev, self._prev_mafd, self._n_scored = False, 0.0, 0
         self.sigma_gain = _check_sigma(model, sigma, sigma_gain, "LiveStream")
+        self.vst = _Vst(model, vst, vst_floor, sigma, "LiveStream")
+        self.last_vst_sigma = None
+        self._tables = self._scene_tables = self._scene_curve = None    # vst='scene': the ring of table sets, the current scene's set and curve
+        self._in_scene = False
         self.auto_sigma = isinstance(sigma, str) and sigma == "auto"
         self.nlf_sigma = isinstance(sigma, str) and sigma == "nlf"
         self.last_sigma = None
@@ -668,10 +785,18 @@ class LiveStream:
             if self.auto_sigma:
                 s.pin_sigma = torch.zeros(1, dtype=torch.float32).pin_memory()
                 s.dev_sigma = torch.empty(1, dtype=torch.float32, device=self.device)
-            if self.nlf_sigma:
+            if self.nlf_sigma or self.vst.scene:
                 s.pin_curve = torch.zeros(_lib.NLF_LEVELS, dtype=torch.float32).pin_memory()
                 s.dev_curve = torch.empty(_lib.NLF_LEVELS, dtype=torch.float32, device=self.device)
+            if self.vst.active:
+                s.pin_vsig = torch.zeros(1, dtype=torch.float32).pin_memory()
+                s.dev_vsig = torch.empty(1, dtype=torch.float32, device=self.device)
             self.slots.append(s)
+        if self.vst.scene:
+            self._tables = _TableRing(self.latency + self.depth, self.device)
+            self._scene_tables = torch.empty((1, VST_TABLE_FLOATS), dtype=torch.float32, device=self.device)
+            self._scene_curve = torch.empty((1, _lib.NLF_LEVELS), dtype=torch.float32, device=self.device)
+            self._in_scene = False
         if getattr(self.fmt, "has_alpha", False):
             self._alpha = _AlphaRing(self.latency + self.depth, geom.h, geom.w, getattr(torch, self.fmt.dtype.name), self.device)
         self._source = _SourceRing(self.latency + self.depth, geom.net_h, geom.net_w, self.device) if self.finish.blends else None
@@ -707,7 +832,7 @@ class LiveStream:
 
     def _to_input(self, slot):
         """the slot's frame -> the network input; a format with alpha leaves the frame's alpha codes in the ring's next plane"""
-        sigma = 0.0 if self.nlf_sigma else self.sigma
+        sigma = 0.0 if self.nlf_sigma else self.vst.sigma_in
         if self._alpha is None:
             x = self.fmt.to_input(slot.dev_in, self.geom, sigma, self.sigma_gain)
         else:
@@ -720,9 +845,28 @@ class LiveStream:
             self._source.next_in().copy_(x[:, :3])          # the frame's colour planes wait for its denoised self
         return x
 
+    def _vst_forward(self, slot, x, cut):
+        """vst=, on the compute stream behind the conversion, the source ring's copy and the cut decision: at a scene start ('scene') the
+        curve and its table set; the frame's set into the ring; the forward transform.  The host waits for none of it."""
+        if self.vst.scene:
+            if cut or not self._in_scene:
+                estimate = estimate_noise_curve(x, picture=(self.geom.h, self.geom.w), gain=self.sigma_gain)
+                self._scene_curve.copy_(estimate)
+                build_vst(self._scene_curve, self.vst.floor, out=self._scene_tables)
+                self._in_scene = True
+            tables = self._tables.next_in()
+            tables.copy_(self._scene_tables)                 # frame k's set waits for frame k's result
+            slot.dev_curve.copy_(self._scene_curve[0])
+        else:
+            tables = self.vst.shared_tables(self.device)
+        slot.dev_vsig.copy_(vst_sigma(tables))
+        vst_forward(x, tables, fill_plane=self.vst.fills)
+
     def _to_output(self, y):
         """what a step emitted -> the surface; frames come out in the order they went in, and so do their alpha planes"""
         y = y.float()
+        if self.vst.active:
+            y = vst_inverse(y.contiguous(), self._tables.next_out() if self.vst.scene else self.vst.shared_tables(self.device))
         if self._source is not None:
             y = self.finish.blend(y.contiguous(), self._source.next_out())
         kw = self.finish.dither_kw(y.shape[0])
@@ -736,8 +880,10 @@ class LiveStream:
         slot.downloaded.synchronize()
         if has_sigma and self.auto_sigma:
             self.last_sigma = float(slot.pin_sigma[0])
-        if has_sigma and self.nlf_sigma:
+        if has_sigma and (self.nlf_sigma or self.vst.scene):
             self.last_noise_curve = [float(v) for v in slot.pin_curve]
+        if has_sigma and self.vst.active:
+            self.last_vst_sigma = float(slot.pin_vsig[0])
         return slot.pin_out.numpy().copy().view(self.fmt.dtype).reshape(self.shape) if has_out else None
 
     def _step(self, frame_u8, last=False, cut=False):
@@ -762,6 +908,8 @@ class LiveStream:
                         x = self._to_input(slot)
                     if self.auto_sigma:
                         slot.dev_sigma.copy_(x[0, -1, 0, :1])          # the plane holds the estimate: one element of it, device to device
+                    if self.vst.active:
+                        self._vst_forward(slot, x, cut)
                 kw = dict(cut=True) if cut else {}
                 y = self.model.feed_overlapped(x, last=last, **kw) if self.overlap else self.model.feedin_one_element(x, **kw)
                 if y is not None:
@@ -773,10 +921,12 @@ class LiveStream:
                     slot.pin_out.copy_(slot.dev_out[0], non_blocking=True)
                 if self.auto_sigma and frame_u8 is not None:
                     slot.pin_sigma.copy_(slot.dev_sigma, non_blocking=True)
-                if self.nlf_sigma and frame_u8 is not None:
+                if (self.nlf_sigma or self.vst.scene) and frame_u8 is not None:
                     slot.pin_curve.copy_(slot.dev_curve, non_blocking=True)
+                if self.vst.active and frame_u8 is not None:
+                    slot.pin_vsig.copy_(slot.dev_vsig, non_blocking=True)
                 slot.downloaded.record()
-        self.inflight.append((slot, y is not None, (self.auto_sigma or self.nlf_sigma) and frame_u8 is not None))
+        self.inflight.append((slot, y is not None, (self.auto_sigma or self.nlf_sigma or self.vst.active) and frame_u8 is not None))
 
     def _drain(self, keep, outs):
         while len(self.inflight) > keep:
@@ -818,6 +968,9 @@ class LiveStream:
             self._alpha.reset()
         if self._source is not None:
             self._source.reset()
+        if self._tables is not None:
+            self._tables.reset()
+        self._in_scene = False
         self.finish.emitted = 0
         self._reopen_overlap()                        # the next stream decides again (free HBM may have changed)
         return outs

@@ -680,7 +680,8 @@ int bsvd_fill_sigma_plane(float *x, int32_t frames, int32_t channels, int32_t Hp
  * Two consequences: a flat curve gives exactly that value at every pixel (f * 0 = 0: the bits bsvd_fill_sigma_plane writes), and the map is
  * finite whatever the colour planes hold (c is finite, 0 <= f <= 1).
  * What is known about it: profiles/noise_curve.txt, on synthetic signal-dependent noise only.  Nothing has been measured on real footage,
- * and a per-pixel map is outside what the reference's checkpoints were trained on (a constant plane).
+ * and a per-pixel map is outside what the reference's checkpoints were trained on (a constant plane): bsvd_vst_* below turn the same curve
+ * into a variance-stabilising transform, which keeps the constant plane.
  *
  * bsvd_nlf_workspace_bytes(frames): the bytes of `workspace`, frames * 16 * 1024 * 4; -1 for frames <= 0.
  * bsvd_estimate_nlf: zeroes the workspace itself, on the stream; afterwards the workspace holds the [frames][16][1024] uint32 histograms
@@ -702,6 +703,54 @@ int bsvd_estimate_nlf(const float *x, int32_t frames, int32_t H, int32_t W, int3
 int bsvd_finish_nlf(const void *workspace, int32_t frames, float gain, float lo, float hi, int32_t min_count, float *curve_out, void *stream);
 int bsvd_fill_nlf_plane(float *x, int32_t frames, int32_t channels, int32_t Hp, int32_t Wp, int64_t frame_stride,
                         const float *curve_dev /*[frames][16]*/, void *stream);
+
+/*
+ * The variance-stabilising transform (VST) of a noise-level curve.  The per-pixel map above is outside what the reference's checkpoints
+ * were trained on; the transform is the remedy that stays inside it: intensities are remapped by g(I) ~ integral dI / sigma(I), so that
+ * the noise has ONE standard deviation sigma' at every level, the network runs with a constant noise plane at sigma', and the result is
+ * mapped back with the inverse of g.  bsvd_vst_build makes the tables of g from curves in device memory, bsvd_vst_forward and
+ * bsvd_vst_inverse apply them in place.  Added without a new BSVD_ABI_VERSION: discover the three entry points by symbol (dlsym), like the
+ * NLF entry points above.
+ *
+ * Exactly (tests/vst_model.py reproduces tables, forward and inverse bit for bit), with N = 1024 intervals over [0, 1]:
+ *   table set 2052 floats: G[0 .. N] at 0, sigma' at 1025, zeros at 1026 and 1027, R[0 .. N - 1] at 1028.
+ *   s_j       j = 0 .. N - 1, the curve c[0 .. 15] at the midpoint of interval j: u = (j + 0.5) * (16 / N) - 0.5 (exact in fp32), clamped to
+ *             [0, 15]; i = min((int)u, 14); f = u - i; s = c[i] + f * (c[i + 1] - c[i]) in fp32, the product rounded before the add
+ *             (bsvd_fill_nlf_plane's rule); then s = s >= floor ? s : floor (not-a-number gives floor) and s = s <= 1 ? s : 1.
+ *   build     in double, ascending j, every operation rounded once: w_j = 1.0 / (double)s_j; F_0 = 0; F_{j+1} = F_j + w_j;
+ *             G[j] = (float)(F_j / F_N) for j = 0 .. N (G[0] = 0 and G[N] = 1 exactly);
+ *             R[j] = (float)(1.0 / ((double)G[j + 1] - (double)G[j])); sigma' = (float)(N / F_N), the harmonic mean of the clamped curve.
+ *   forward   t = x * 1024; k = t >= 1023 ? 1023 : (t >= 0 ? (int)t : 0) (not-a-number gives 0); fr = t - (float)k;
+ *             y = G[k] + fr * (G[k + 1] - G[k]) in fp32, the difference, the product and the add rounded separately.  Values outside [0, 1]
+ *             continue on the end interval's line (limited-range YUV produces them).  No clamp to G[k + 1] is applied: the model finds the
+ *             forward non-decreasing over every 16-bit code and over every knot +- 1 ulp for the curves of tests/test_vst_cpu.py.
+ *   inverse   k = the largest index in 0 .. 1023 with G[k] <= y, 0 if there is none (not-a-number gives 0);
+ *             x = ((float)k + (y - G[k]) * R[k]) * (1 / 1024) in fp32, each operation rounded separately (the last is exact).
+ * floor is refused below 2^-10 and above 1: consecutive G then differ by at least floor / 1024 >= 16 ulp, so G is strictly increasing and R
+ * is finite.  The build is in double so that the tables do not depend on a device fp32 division; the per-pixel paths multiply only.
+ * Not-a-number in gives not-a-number out; +-inf and -0.0 follow the formulas; no index ever leaves the table.
+ * What is known about it: profiles/vst.txt, on synthetic signal-dependent noise only.  No trained checkpoint has been run through it, so
+ * its effect on denoising quality has not been measured, and nothing has been measured on real footage.  The inverse is the algebraic one:
+ * a nonlinear inverse of a denoised mean is biased where the curve bends sharply relative to sigma', and no unbiased-inverse correction is
+ * applied.  The transform changes the tone curve the network sees.
+ *
+ * bsvd_vst_build: curves [n][16] (device memory) -> tables [n][2052] (device memory), on the stream, nothing crosses to the host.  One
+ *   workgroup per curve; the 1024 adds of F are one lane's, in order.  Returns -3, naming the argument in bsvd_last_error(), without a
+ *   device, for: a NULL or misaligned pointer; n outside 1 .. 65535; floor outside [2^-10, 1] or not finite.
+ * bsvd_vst_forward: in place on planes 0 .. 2 of x [frames][>= 3][Hp][Wp], frames `frame_stride` FLOATS apart.  Frame t uses the table set
+ *   at tables + t * table_stride * 2052; table_stride == 0: one set for all frames.  fill_plane >= 3: every element of that plane of frame
+ *   t becomes that frame's sigma' (the noise-map plane); fill_plane < 0: no plane is written (a blind model has none).  Planes move as
+ *   float4 when x is 16-byte aligned and Hp * Wp and frame_stride are multiples of 4, as scalars otherwise; the same bits either way.  -3
+ *   for: a NULL or misaligned pointer; frames outside 1 .. 65535; Hp or Wp <= 0; fill_plane in 0 .. 2; frame_stride below the planes it
+ *   spans (3, or fill_plane + 1); table_stride outside 0 .. 65535.
+ * bsvd_vst_inverse: in place on the three planes of y, frames y_frame_stride ELEMENTS apart (like bsvd_blend_planar), the same table
+ *   addressing and the same float4 rule.  -3 as for bsvd_vst_forward.
+ */
+int bsvd_vst_build(const float *curves /*[n][16]*/, int32_t n, float floor, float *tables /*[n][2052]*/, void *stream);
+int bsvd_vst_forward(float *x, int32_t frames, int32_t Hp, int32_t Wp, int64_t frame_stride, int32_t fill_plane, const float *tables,
+                     int64_t table_stride, void *stream);
+int bsvd_vst_inverse(float *y, int64_t y_frame_stride, int32_t frames, int32_t Hp, int32_t Wp, const float *tables, int64_t table_stride,
+                     void *stream);
 
 /*
  * What a scene-cut detector needs from a frame, computed on the device.  Each temporal-fusion conv mixes a frame with its two neighbours; a

@@ -18,6 +18,15 @@ steady_frames_per_s (wall clock, reads and writes included) over the steady stat
                                 in 8-bit code units.  Untested on real footage, and outside what the reference's checkpoints were trained on
     python tools/yuv_denoise.py IN OUT --size 1920x1080 --noise-model A,B                    the same map from a sensor model the caller
                                 knows, sigma(I) = sqrt(A I + B) with I and sigma in 8-bit code units (frame_io.NoiseCurve.from_model)
+    python tools/yuv_denoise.py IN OUT --size 1920x1080 --vst scene [--sigma-gain 1.0] [--vst-floor 0.5] | --vst-model A,B
+                                for noise that depends on the signal level, inside what the checkpoints were trained on: a
+                                variance-stabilising transform around the network (LiveStream(vst=)).  Intensities are remapped so that the
+                                noise has one standard deviation sigma' everywhere, the noise plane is that constant, the result is mapped
+                                back.  scene: the curve is estimated on the device from the first frame of every scene (combine with --cuts
+                                auto); --vst-model: from the sensor model sigma(I) = sqrt(A I + B), 8-bit code units.  --vst-floor: the
+                                least sigma the transform divides by, 8-bit code units.  Instead of --sigma / --noise-model.  The JSON line
+                                carries last_vst_sigma (and last_noise_curve for scene), in 8-bit code units.  The effect on denoising
+                                quality is unmeasured (no trained checkpoint has been run through it); untested on real footage
     python tools/yuv_denoise.py IN OUT --size 1920x1080 --sigma 30 --cuts auto [--cut-threshold 10]      scene cuts detected on the device
                                 (LiveStream(cuts='auto')): no frame is mixed with a frame of another scene; the JSON line then carries the
                                 frame numbers found.  Untested on real footage; a cut one or two frames after another cut scores low
@@ -83,7 +92,10 @@ def main(argv=None):
     ap.add_argument("--sigma", type=parse_sigma, default=None, help="noise std in 8-bit code units (e.g. 30); auto: estimated per frame on the device; "
                     "nlf: a noise-level curve per frame and a per-pixel noise map")
     ap.add_argument("--noise-model", type=parse_noise_model, default=None, help="A,B instead of --sigma: sigma(I) = sqrt(A I + B) in 8-bit code units")
-    ap.add_argument("--sigma-gain", type=float, default=1.0, help="factor on the estimate of --sigma auto / nlf")
+    ap.add_argument("--sigma-gain", type=float, default=1.0, help="factor on the estimate of --sigma auto / nlf and of --vst scene")
+    ap.add_argument("--vst", default=None, choices=["scene"], help="instead of --sigma: variance-stabilising transform, the curve estimated at every scene start")
+    ap.add_argument("--vst-model", type=parse_noise_model, default=None, help="A,B instead of --sigma: the transform of sigma(I) = sqrt(A I + B), 8-bit code units")
+    ap.add_argument("--vst-floor", type=float, default=frame_io.VST_FLOOR * 255.0, help="the least sigma the transform divides by, 8-bit code units (default 0.5)")
     ap.add_argument("--cuts", default="none", choices=["none", "auto"], help="auto: scene cuts detected per frame on the device")
     ap.add_argument("--cut-threshold", type=float, default=frame_io.CUT_THRESHOLD, help="score at which --cuts auto declares a scene start")
     ap.add_argument("--matrix", default="bt709", choices=["bt601", "bt709", "bt2020"])
@@ -97,8 +109,18 @@ def main(argv=None):
     ap.add_argument("--ckpt", default=None)
     ap.add_argument("--precision", default="f16x3")
     a = ap.parse_args(argv)
-    if (a.sigma is None) == (a.noise_model is None):
-        ap.error("one of --sigma and --noise-model is required")
+    vst = a.vst if a.vst is not None else a.vst_model
+    if a.vst is not None and a.vst_model is not None:
+        ap.error("--vst scene and --vst-model exclude each other")
+    if vst is not None:
+        if a.sigma is not None or a.noise_model is not None:
+            ap.error("--vst / --vst-model stand in for --sigma / --noise-model: the noise plane is the transform's own sigma'")
+        try:
+            vst_floor = frame_io.check_vst_floor(a.vst_floor / 255.0)
+        except ValueError as e:
+            ap.error("--vst-floor %r (8-bit code units): %s" % (a.vst_floor, e))
+    elif (a.sigma is None) == (a.noise_model is None):
+        ap.error("one of --sigma, --noise-model, --vst and --vst-model is required")
     if a.noise_model is not None:
         a.sigma = a.noise_model
     W, H = map(int, a.size.lower().split("x"))
@@ -123,7 +145,8 @@ def main(argv=None):
     live = LiveStream(m, sigma=a.sigma, sigma_gain=a.sigma_gain, depth=a.depth, frame_shape=(H, W), pix_fmt=a.pix_fmt,
                       colour={"full_range": not a.limited_range} if rgb else {"matrix": a.matrix, "full_range": a.full_range, "chroma": a.chroma}, pad=pad,
                       cuts="auto" if a.cuts == "auto" else None, cut_threshold=a.cut_threshold,
-                      strength=a.strength, dither=None if a.dither == "none" else a.dither, dither_seed=a.dither_seed)
+                      strength=a.strength, dither=None if a.dither == "none" else a.dither, dither_seed=a.dither_seed,
+                      **(dict(vst=vst, vst_floor=vst_floor) if vst is not None else {}))
     found = []
     fin = sys.stdin.buffer if a.input == "-" else open(a.input, "rb")
     fout = sys.stdout.buffer if a.output == "-" else open(a.output, "wb")
@@ -155,7 +178,14 @@ def main(argv=None):
            "ms_per_feed": {"p50": float(np.percentile(steady, 50)), "p99": float(np.percentile(steady, 99))},
            "steady_frames_per_s": (n_in - k) / (done[-1] - done[k - 1]) if n_in > k >= 1 else 0.0,       # wall clock, reads and writes included
            "size": "%dx%d" % (W, H), "pix_fmt": a.pix_fmt, "depth": a.depth, "frame_latency_feeds": live.latency, "pad": pad,
-           "sigma": a.sigma if isinstance(a.sigma, str) else "noise-model" if a.noise_model is not None else a.sigma * 255.0}
+           "sigma": a.sigma if isinstance(a.sigma, str) or a.sigma is None else "noise-model" if a.noise_model is not None else a.sigma * 255.0}
+    if vst is not None:
+        res["vst"] = "scene" if a.vst is not None else "model"
+        res["vst_floor"] = a.vst_floor
+        res["last_vst_sigma"] = None if live.last_vst_sigma is None else live.last_vst_sigma * 255.0
+        if a.vst is not None:
+            res["sigma_gain"] = a.sigma_gain
+            res["last_noise_curve"] = None if live.last_noise_curve is None else [v * 255.0 for v in live.last_noise_curve]
     if a.sigma == "nlf":
         res["sigma_gain"] = a.sigma_gain
         res["last_noise_curve"] = None if live.last_noise_curve is None else [v * 255.0 for v in live.last_noise_curve]
