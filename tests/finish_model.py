@@ -35,7 +35,8 @@ BAYER8 = bayer(8)
 # ---- the blend -------------------------------------------------------------------------------------------------------------------------------
 def fma32(a, b, c):
     """fmaf on float32 arrays: a b is exact in float64, the sum with c rounds once to 53 bits and then to 24.  The two roundings can differ
-    from fmaf's one only where the 53-bit sum is exactly a float32 tie; those elements (none, on random data) are redone in exact rationals"""
+    from fmaf's one only where the 53-bit sum is exactly a float32 tie; those elements (a few in 10^7 on random data) are redone in exact
+    rationals, and where the exact sum IS the tie, fmaf's half-to-even result stands"""
     import fractions
     a, b, c = np.broadcast_arrays(np.asarray(a, f32), np.asarray(b, f32), np.asarray(c, f32))
     s = a.astype(np.float64) * b.astype(np.float64) + c.astype(np.float64)
@@ -44,7 +45,8 @@ def fma32(a, b, c):
     for i in zip(*np.nonzero(hazard)):
         exact = fractions.Fraction(float(a[i])) * fractions.Fraction(float(b[i])) + fractions.Fraction(float(c[i]))
         lo, hi = sorted((float(np.nextafter(out[i], f32(-np.inf))), float(np.nextafter(out[i], f32(np.inf)))))
-        out[i] = min((lo, float(out[i]), hi), key=lambda v: abs(fractions.Fraction(v) - exact))
+        here = float(out[i])                                           # an EXACT tie keeps it: the float64 sum was exact and rounded half to even
+        out[i] = min((here, lo, hi), key=lambda v: abs(fractions.Fraction(v) - exact))
     return out
 
 
