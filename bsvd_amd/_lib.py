@@ -30,7 +30,8 @@ EXPORTS = ("bsvd_abi_version", "bsvd_conv_args_size", "bsvd_build_info", "bsvd_l
            "bsvd_rgb_frame_bytes", "bsvd_rgb_to_planar", "bsvd_planar_to_rgb",
            "bsvd_blend_planar", "bsvd_planar_to_yuv420_crop_d", "bsvd_planar_to_yuv_crop_d", "bsvd_planar_to_rgb_d",
            "bsvd_nlf_workspace_bytes", "bsvd_estimate_nlf", "bsvd_finish_nlf", "bsvd_fill_nlf_plane",
-           "bsvd_vst_build", "bsvd_vst_forward", "bsvd_vst_inverse")
+           "bsvd_vst_build", "bsvd_vst_forward", "bsvd_vst_inverse",
+           "bsvd_grain_stats_bytes", "bsvd_grain_stats", "bsvd_grain_apply")
 PIX_FMT = {"nv12": 0, "p010": 1}
 MATRIX = {"bt601": 0, "bt709": 1, "bt2020": 2}
 CHROMA = {"nearest": 0, "linear": 1}
@@ -53,6 +54,11 @@ VST_SIGMA_AT, VST_R_AT = VST_KNOTS, VST_KNOTS + 3
 VST_TABLE_FLOATS = VST_R_AT + VST_KNOTS - 1
 VST_FLOOR = 0.5 / 255
 VST_FLOOR_MIN = 2.0 ** -10
+# bsvd_grain_stats: a frame's 256 int64 are N[16] at 0, sum q_k at GRAIN_S1_AT + 16 k + l, sum q_k^2 at GRAIN_S2_AT + 16 k + l, the lag
+# products A[k][lag] at GRAIN_A_AT + 46 k + lag; q = noise * GRAIN_QSCALE; bsvd_grain_apply: templates [3][GRAIN_TMPL][GRAIN_TMPL]
+GRAIN_LEVELS, GRAIN_LAGS, GRAIN_TAPS, GRAIN_STATS = 16, 46, 24, 256
+GRAIN_N_AT, GRAIN_S1_AT, GRAIN_S2_AT, GRAIN_A_AT = 0, 16, 64, 112
+GRAIN_QSCALE, GRAIN_TMPL, GRAIN_MIN_COUNT = 4096.0, 128, 512
 # the surfaces of bsvd_yuv_to_planar / bsvd_planar_to_yuv, by ffmpeg's names: (subsampling, layout, bits, high_bits).  PIX_FMT above stays
 # the table of the bsvd_yuv420_* entry points.
 YUV_FORMATS = {
@@ -273,6 +279,12 @@ def load():
     lib.bsvd_vst_forward.argtypes = [vp, i32, i32, i32, i64, i32, vp, i64, vp]
     lib.bsvd_vst_inverse.restype = ctypes.c_int
     lib.bsvd_vst_inverse.argtypes = [vp, i64, i32, i32, i32, vp, i64, vp]
+    lib.bsvd_grain_stats_bytes.restype = ctypes.c_int64
+    lib.bsvd_grain_stats_bytes.argtypes = [i32]
+    lib.bsvd_grain_stats.restype = ctypes.c_int
+    lib.bsvd_grain_stats.argtypes = [vp, i64, vp, i64, i32, i32, i32, i32, i32, vp, vp, vp]
+    lib.bsvd_grain_apply.restype = ctypes.c_int
+    lib.bsvd_grain_apply.argtypes = [vp, i64, i32, i32, i32, vp, vp, f32, vp, f32, ctypes.c_uint32, i64, vp]
     lib.bsvd_scene_grid.restype = ctypes.c_int
     lib.bsvd_scene_grid.argtypes = [vp, i32, i32, i32, i32, i32, i64, vp, vp]
     lib.bsvd_scene_diff.restype = ctypes.c_int

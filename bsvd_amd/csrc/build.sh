@@ -16,7 +16,7 @@ SRCS="$BSVD_SRCS"
 pids=()
 for src in $SRCS; do
   if [ ! -f "$OBJ/$src.o" ] || [ "$HERE/$src.hip" -nt "$OBJ/$src.o" ] || \
-     [ "$HERE/bsvd_internal.h" -nt "$OBJ/$src.o" ] || [ "$HERE/wino_forms.h" -nt "$OBJ/$src.o" ] || [ "$HERE/frame_items.h" -nt "$OBJ/$src.o" ] || [ "$HERE/frame_surface_items.h" -nt "$OBJ/$src.o" ] || [ "$HERE/frame_rgb_items.h" -nt "$OBJ/$src.o" ] || [ "$HERE/frame_sigma_items.h" -nt "$OBJ/$src.o" ] || [ "$HERE/frame_finish_items.h" -nt "$OBJ/$src.o" ] || [ "$HERE/frame_nlf_items.h" -nt "$OBJ/$src.o" ] || [ "$HERE/frame_vst_items.h" -nt "$OBJ/$src.o" ] || [ "$ROOT/include/bsvd_hip.h" -nt "$OBJ/$src.o" ] || \
+     [ "$HERE/bsvd_internal.h" -nt "$OBJ/$src.o" ] || [ "$HERE/wino_forms.h" -nt "$OBJ/$src.o" ] || [ "$HERE/frame_items.h" -nt "$OBJ/$src.o" ] || [ "$HERE/frame_surface_items.h" -nt "$OBJ/$src.o" ] || [ "$HERE/frame_rgb_items.h" -nt "$OBJ/$src.o" ] || [ "$HERE/frame_sigma_items.h" -nt "$OBJ/$src.o" ] || [ "$HERE/frame_finish_items.h" -nt "$OBJ/$src.o" ] || [ "$HERE/frame_nlf_items.h" -nt "$OBJ/$src.o" ] || [ "$HERE/frame_vst_items.h" -nt "$OBJ/$src.o" ] || [ "$HERE/frame_grain_items.h" -nt "$OBJ/$src.o" ] || [ "$ROOT/include/bsvd_hip.h" -nt "$OBJ/$src.o" ] || \
      [ "$(cat "$OBJ/$src.flags" 2>/dev/null)" != "$FLAGS" ]; then
     XF="$(bsvd_src_flags $src)"
     ( $HIPCC $FLAGS $XF -c "$HERE/$src.hip" -o "$OBJ/$src.o" && echo "$FLAGS" > "$OBJ/$src.flags" ) &

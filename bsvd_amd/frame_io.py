@@ -34,9 +34,15 @@ the model's forward functions.  Untested on real footage.
 
 The output finish: ``blend_output`` (the denoise strength: the network's result blended with its input, separate luma and chroma amounts,
 in place, with exact ends) and ``dither=`` on ``output_to_yuv420`` / ``output_to_yuv`` / ``output_to_rgb`` (ordered or random dither at the
-quantiser; a whole code is never moved) -- include/bsvd_hip.h, bsvd_blend_planar / BsvdDither.  The defaults call what was called before."""
+quantiser; a whole code is never moved) -- include/bsvd_hip.h, bsvd_blend_planar / BsvdDither.  The defaults call what was called before.
+
+Film grain: ``estimate_grain`` (the statistics of the noise the network removed, taken on the device in integers -- ``grain_stats`` -- and
+a model fitted to them on the host: ``GrainModel``, standard deviation against brightness and a spatial autoregression per component) and
+``apply_grain`` (clean grain synthesised from a model onto the result, on the device) -- include/bsvd_hip.h, bsvd_grain_stats /
+bsvd_grain_apply; the pipelines' ``grain=``.  Untested on real footage; no encoder has read the model."""
 import ctypes
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -570,6 +576,274 @@ def blend_output(y, x, strength, matrix="bt709"):
     with torch.cuda.device(y.device):
         _lib.check(lib.bsvd_blend_planar(y.data_ptr(), 3 * Hp * Wp, x.data_ptr(), x.shape[1] * Hp * Wp, T, Hp, Wp, sl, sc, w, _stream()),
                    "bsvd_blend_planar")
+    return y
+
+
+# ---------------------------------------------------------------------------------------------------
+# film grain: the removed noise measured on the device, a model fitted on the host, clean grain synthesised on the device
+# (include/bsvd_hip.h, bsvd_grain_stats / bsvd_grain_apply)
+
+GRAIN_LEVELS, GRAIN_LAGS, GRAIN_TAPS, GRAIN_STATS = _lib.GRAIN_LEVELS, _lib.GRAIN_LAGS, _lib.GRAIN_TAPS, _lib.GRAIN_STATS
+GRAIN_TMPL = _lib.GRAIN_TMPL
+GRAIN_MIN_COUNT = _lib.GRAIN_MIN_COUNT
+GRAIN_WARMUP = 16                   # rows above and columns on both sides of a template that the recursion runs through first
+GRAIN_RIDGE = 1e-3                  # times R(0), on the diagonal of the Yule-Walker system
+# the 46 lags (dy, dx) of bsvd_grain_stats in its order, and the 24 taps (dy, dx) of the causal lag-3 neighbourhood: tap i is the
+# neighbour at (r - dy, c - dx) -- the three to the left in the row, then the rows above, nearest first, each from dx = -3 (right) to 3 (left)
+GRAIN_LAG_LIST = [(0, dx) for dx in range(7)] + [(dy, dx) for dy in (1, 2, 3) for dx in range(-6, 7)]
+GRAIN_TAP_LIST = [(0, dx) for dx in (1, 2, 3)] + [(dy, dx) for dy in (1, 2, 3) for dx in range(-3, 4)]
+_GRAIN_LAG_AT = {lag: i for i, lag in enumerate(GRAIN_LAG_LIST)}
+
+
+def _grain_lag_index(dy, dx):
+    """R(-d) = R(d): the index of lag (dy, dx) or of its mirror image in ``GRAIN_LAG_LIST``"""
+    if dy < 0 or (dy == 0 and dx < 0):
+        dy, dx = -dy, -dx
+    return _GRAIN_LAG_AT[(dy, dx)]
+
+
+def _solve(M, b):
+    """M a = b by Gaussian elimination with partial pivoting in float64, written out (no LAPACK); a singular system gives zeros"""
+    n = len(b)
+    A = np.array(M, dtype=np.float64).reshape(n, n).copy()
+    v = np.array(b, dtype=np.float64).copy()
+    for i in range(n):
+        p = i + int(np.argmax(np.abs(A[i:, i])))
+        if not abs(A[p, i]) > 0.0:
+            return np.zeros(n)
+        if p != i:
+            A[[i, p]] = A[[p, i]]
+            v[[i, p]] = v[[p, i]]
+        f = A[i + 1:, i] / A[i, i]
+        A[i + 1:] -= f[:, None] * A[i]
+        v[i + 1:] -= f * v[i]
+    a = np.zeros(n)
+    for i in range(n - 1, -1, -1):
+        a[i] = (v[i] - A[i, i + 1:] @ a[i + 1:]) / A[i, i]
+    return a if np.all(np.isfinite(a)) else np.zeros(n)
+
+
+def grain_template(ar, seed=0):
+    """ar: [3][24] coefficients -> float32 [3,128,128]: one unit-variance grain template per component.  White Gaussian noise from
+    ``numpy.random.default_rng(seed)`` over (128 + 16) x (128 + 32), the raster recursion g(r, c) = e(r, c) + sum_i a_i g(r - dy_i, c - dx_i)
+    over ``GRAIN_TAP_LIST`` (zeros outside), the warm-up border of 16 rows above and 16 columns on both sides cut off, divided by its own
+    standard deviation.  A recursion that does not stay finite (coefficients outside the stable region) gives the white field instead."""
+    ar = np.asarray(ar, dtype=np.float64).reshape(3, GRAIN_TAPS)
+    B, n = GRAIN_WARMUP, GRAIN_TMPL
+    rows, cols = n + B, n + 2 * B
+    white = np.random.default_rng(seed).standard_normal((3, rows, cols))
+    out = np.empty((3, n, n), dtype=np.float32)
+    for k in range(3):
+        g = np.zeros((rows + 3, cols + 6))                 # three zero rows above, three zero columns on both sides
+        a_row = ar[k, :3]
+        with np.errstate(all="ignore"):
+            for r in range(rows):
+                acc = white[k, r].copy()
+                for i, (dy, dx) in enumerate(GRAIN_TAP_LIST[3:], 3):
+                    if ar[k, i] != 0.0:
+                        acc += ar[k, i] * g[3 + r - dy, 3 - dx:3 - dx + cols]
+                if np.any(a_row != 0.0):                   # the row's own three taps: a recursion along the row
+                    line = g[3 + r]
+                    a1, a2, a3 = (float(v) for v in a_row)
+                    for c in range(cols):
+                        line[3 + c] = acc[c] + a1 * line[2 + c] + a2 * line[1 + c] + a3 * line[c]
+                else:
+                    g[3 + r, 3:3 + cols] = acc
+            t = g[3 + B:, 3 + B:3 + B + n]
+            sd = float(t.std())
+        if not (np.all(np.isfinite(t)) and 0.0 < sd < 1e6):
+            t = white[k, B:, B:B + n]
+            sd = float(t.std())
+        out[k] = (t / sd).astype(np.float32)
+    return out
+
+
+class GrainModel:
+    """A film-grain model in the components the statistics use -- 0: the luma of the noise, 1: B minus it, 2: R minus it.
+    ``std`` [3][16]: the standard deviation ([0,1] units) at the centres (l + 0.5) / 16 of sixteen levels of the result's luma;
+    ``ar`` [3][24]: the coefficients of a causal lag-3 autoregression over ``GRAIN_TAP_LIST`` (the grain's spatial correlation, its
+    "size"); ``templates``: float32 [3,128,128], unit-variance fields synthesised from ``ar`` (``grain_template``; built when first asked
+    for).  Plain numpy in float64.  ``from_values`` makes one by hand; ``estimate_grain`` / ``grain_from_stats`` measure one."""
+
+    def __init__(self, std, ar=None, template_seed=0):
+        try:
+            s = np.array(std, dtype=np.float64)
+            a = np.zeros((3, GRAIN_TAPS)) if ar is None else np.array(ar, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("GrainModel: std [3][%d] and ar [3][%d] numbers, got %r / %r" % (GRAIN_LEVELS, GRAIN_TAPS, std, ar)) from None
+        if s.shape != (3, GRAIN_LEVELS) or not np.all(np.isfinite(s)) or np.any(s < 0):
+            raise ValueError("GrainModel: std must be [3][%d] finite numbers >= 0" % GRAIN_LEVELS)
+        if a.shape != (3, GRAIN_TAPS) or not np.all(np.isfinite(a)):
+            raise ValueError("GrainModel: ar must be [3][%d] finite numbers" % GRAIN_TAPS)
+        if np.any(s.astype(np.float32) > 3e38):
+            raise ValueError("GrainModel: std must fit float32")
+        self.std, self.ar, self.template_seed = s, a, int(template_seed)
+        self._templates = None
+        self._dev = {}
+
+    @classmethod
+    def from_values(cls, std, ar=None, template_seed=0):
+        """std: one number (every component, every level), three numbers (one per component) or [3][16]; ar: None (white grain) or [3][24]"""
+        try:
+            s = np.array(std, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("GrainModel.from_values: std must be a number, three numbers or [3][%d], got %r" % (GRAIN_LEVELS, std)) from None
+        if s.shape == ():
+            s = np.full((3, GRAIN_LEVELS), float(s))
+        elif s.shape == (3,):
+            s = np.repeat(s[:, None], GRAIN_LEVELS, axis=1)
+        return cls(s, ar, template_seed)
+
+    @property
+    def templates(self):
+        if self._templates is None:
+            self._templates = grain_template(self.ar, self.template_seed)
+            self._templates.setflags(write=False)
+        return self._templates
+
+    @property
+    def is_zero(self):
+        return not bool((self.std.astype("float32") != 0).any())
+
+    def device_templates(self, device):
+        """the templates as a float32 tensor [3,128,128] on ``device``, uploaded once"""
+        key = str(device)
+        if key not in self._dev:
+            self._dev[key] = torch.from_numpy(self.templates.copy()).to(device)
+        return self._dev[key]
+
+    def __repr__(self):
+        return "GrainModel(std=%r, ar=%r)" % (self.std.tolist(), self.ar.tolist())
+
+
+def grain_from_stats(stats, anchors, min_count=GRAIN_MIN_COUNT, template_seed=0):
+    """stats: 256 integers (``estimate_grain(return_stats=True)``, summed over the frames to pool), anchors: the number of anchor
+    positions they were taken over ((H - 3) (W - 12) per frame) -> ``GrainModel``.  The fit alone, in float64:
+    std[k][l] = sqrt(max(sum q^2 / N - (sum q / N)^2, 0)) / 4096 for the levels with at least ``min_count`` pixels, the others filled
+    from the nearest such level (the lower one on a tie; none: the value pooled over the levels, 0 without pixels);
+    ar[k]: with R(d) = A[k][d] / anchors, the 24 x 24 system sum_j a_j R(d_i - d_j) = R(d_i) over ``GRAIN_TAP_LIST`` with
+    ``GRAIN_RIDGE`` R(0) on the diagonal, solved by elimination; R(0) <= 0 gives zeros."""
+    min_count = _check_min_count(min_count)
+    st = np.asarray(stats)
+    if st.shape != (GRAIN_STATS,) or st.dtype.kind not in "iu":
+        raise ValueError("grain_from_stats: expected %d integers, got %s %s" % (GRAIN_STATS, st.dtype, st.shape))
+    if int(anchors) < 1:
+        raise ValueError("grain_from_stats: anchors %r must be positive" % (anchors,))
+    st = st.astype(np.int64)
+    N = st[_lib.GRAIN_N_AT:_lib.GRAIN_N_AT + GRAIN_LEVELS].astype(np.float64)
+    std = np.zeros((3, GRAIN_LEVELS))
+    ar = np.zeros((3, GRAIN_TAPS))
+    valid = [l for l in range(GRAIN_LEVELS) if N[l] >= min_count]
+    for k in range(3):
+        s1 = st[_lib.GRAIN_S1_AT + 16 * k:_lib.GRAIN_S1_AT + 16 * k + 16].astype(np.float64)
+        s2 = st[_lib.GRAIN_S2_AT + 16 * k:_lib.GRAIN_S2_AT + 16 * k + 16].astype(np.float64)
+
+        def value(n, a, b):
+            return 0.0 if n <= 0 else max(b / n - (a / n) ** 2, 0.0) ** 0.5 / _lib.GRAIN_QSCALE
+
+        own = [value(N[l], s1[l], s2[l]) for l in range(GRAIN_LEVELS)]
+        pooled = value(N.sum(), s1.sum(), s2.sum())
+        for l in range(GRAIN_LEVELS):
+            if not valid:
+                std[k, l] = pooled
+            else:
+                std[k, l] = own[min(valid, key=lambda v: (abs(v - l), v))]
+        R = st[_lib.GRAIN_A_AT + GRAIN_LAGS * k:_lib.GRAIN_A_AT + GRAIN_LAGS * (k + 1)].astype(np.float64) / float(anchors)
+        if R[0] > 0.0:
+            M = np.empty((GRAIN_TAPS, GRAIN_TAPS))
+            for i, (yi, xi) in enumerate(GRAIN_TAP_LIST):
+                for j, (yj, xj) in enumerate(GRAIN_TAP_LIST):
+                    M[i, j] = R[_grain_lag_index(yi - yj, xi - xj)]
+            M[np.diag_indices(GRAIN_TAPS)] += GRAIN_RIDGE * R[0]
+            ar[k] = _solve(M, [R[_grain_lag_index(dy, dx)] for dy, dx in GRAIN_TAP_LIST])
+    return GrainModel(std, ar, template_seed)
+
+
+def grain_stats(x, y, picture=None, matrix="bt709"):
+    """x (the source) fp32 device tensor [T,>=3,Hp,Wp], y (the result) [T,>=3,Hp,Wp] -> int64 device tensor [T,256]: the statistics of the
+    removed noise x - y of every frame (include/bsvd_hip.h, bsvd_grain_stats, states them), not synchronised with the host.
+    ``picture=(H, W)``: the top-left part of the planes that is the picture; default: all of it.  H >= 4, W >= 13."""
+    w = _luma_weights(matrix)
+    Tx, Cx, Hp, Wp = _planes(x, "grain_stats(x)")
+    Ty, Cy, Hy, Wy = _planes(y, "grain_stats(y)")
+    if Cx < 3 or Cy < 3 or (Tx, Hp, Wp) != (Ty, Hy, Wy) or x.device != y.device:
+        raise ValueError("grain_stats: x [T,>=3,Hp,Wp] and y [T,>=3,Hp,Wp] on one device, got %s and %s" % (tuple(x.shape), tuple(y.shape)))
+    H, W = (Hp, Wp) if picture is None else _pair(picture, "picture")
+    lib = require_hip()
+    out = torch.empty((Tx, GRAIN_STATS), dtype=torch.int64, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(lib.bsvd_grain_stats(x.data_ptr(), Cx * Hp * Wp, y.data_ptr(), Cy * Hp * Wp, Tx, H, W, Hp, Wp, w, out.data_ptr(), _stream()),
+                   "bsvd_grain_stats")
+    return out
+
+
+def estimate_grain(x, y, picture=None, matrix="bt709", min_count=GRAIN_MIN_COUNT, return_stats=False):
+    """x: the source, y: the denoised result, fp32 device tensors [T,>=3,Hp,Wp] -> ``GrainModel``: the grain the network removed, as a
+    model.  The statistics are taken on the device (``grain_stats``: integers, bit-reproducible), pooled over the T frames and brought to
+    the host -- ONE synchronisation --, where ``grain_from_stats`` fits standard deviations per luma level and an autoregression per
+    component.  ``return_stats=True``: also the pooled int64 [256] (numpy).
+
+    What is known: synthetic grain of a known model comes back within the figures of profiles/film_grain.txt.  Nothing has been measured
+    on real footage, and no encoder has read the model (there is no AV1 / filmgrn1 table writer)."""
+    min_count = _check_min_count(min_count)
+    st = grain_stats(x, y, picture=picture, matrix=matrix)
+    H, W = (x.shape[2], x.shape[3]) if picture is None else _pair(picture, "picture")
+    pooled = st.sum(dim=0).cpu().numpy()
+    model = grain_from_stats(pooled, x.shape[0] * (H - 3) * (W - 12), min_count)
+    return (model, pooled) if return_stats else model
+
+
+def check_grain(grain, amount=1.0, seed=0):
+    """the pipelines' ``grain`` None | GrainModel | 'scene', ``grain_amount`` finite >= 0, ``grain_seed`` in [0, 2^32)
+    -> (grain, amount, seed); ValueError otherwise.  Needs no device."""
+    if grain is not None and not isinstance(grain, GrainModel) and not (isinstance(grain, str) and grain == "scene"):
+        raise ValueError("grain %r: None, a GrainModel or 'scene'" % (grain,))
+    try:
+        a = float(amount)
+    except (TypeError, ValueError):
+        raise ValueError("grain_amount: expected a number >= 0, got %r" % (amount,)) from None
+    if isinstance(amount, bool) or not (0.0 <= a < 3e38):
+        raise ValueError("grain_amount %r: must be finite and not negative" % (amount,))
+    try:
+        s = int(seed)
+    except (TypeError, ValueError):
+        raise ValueError("grain_seed: expected an int, got %r" % (seed,)) from None
+    if s != seed or not 0 <= s < 2 ** 32:
+        raise ValueError("grain_seed %r: 0 <= seed < 2^32" % (seed,))
+    return grain, a, s
+
+
+def apply_grain(y, model, amount=1.0, seed=0, frame0=0, matrix="bt709"):
+    """Synthetic grain from ``model`` (a ``GrainModel``) onto y, fp32 device tensor [T,3,Hp,Wp], in place over the whole planes: per
+    32 x 32 block a window of the model's templates at an offset hashed from (seed, frame0 + t, block), scaled by ``amount`` times the
+    model's standard deviation at the pixel's luma, turned from (luma, B - luma, R - luma) back into R, G, B with ``matrix``'s weights
+    (include/bsvd_hip.h, bsvd_grain_apply, states the arithmetic).  ``frame0``: the stream index of the first frame -- the pattern of a
+    frame depends on its index, not on how the stream was cut into calls.  ``amount=0`` or a model whose std is all zero: nothing is
+    launched and y keeps its bytes.  No overlap blending of the blocks.  Returns ``y``."""
+    if not isinstance(model, GrainModel):
+        raise ValueError("apply_grain: model must be a GrainModel, got %r" % (model,))
+    _, amount, seed = check_grain(model, amount, seed)
+    try:
+        f0 = int(frame0)
+    except (TypeError, ValueError):
+        raise ValueError("frame0: expected an int, got %r" % (frame0,)) from None
+    if not 0 <= f0 < 2 ** 62:
+        raise ValueError("frame0 %r: the stream index of the first frame, not negative" % (frame0,))
+    w = _luma_weights(matrix)
+    if not w[1] > 0.0:
+        raise ValueError("apply_grain: matrix %r has no green weight to divide by" % (matrix,))
+    T, C, Hp, Wp = _planes(y, "apply_grain")
+    if C != 3:
+        raise ValueError("apply_grain: y must have three planes, it has %d" % C)
+    if amount == 0.0 or model.is_zero:
+        return y
+    lib = require_hip()
+    std = (ctypes.c_float * (3 * GRAIN_LEVELS))(*[float(v) for v in model.std.reshape(-1)])
+    inv_wg = ctypes.c_float(1.0 / float(w[1])).value
+    tmpl = model.device_templates(y.device)
+    with torch.cuda.device(y.device):
+        _lib.check(lib.bsvd_grain_apply(y.data_ptr(), 3 * Hp * Wp, T, Hp, Wp, tmpl.data_ptr(), std, amount, w, inv_wg, seed, f0, _stream()),
+                   "bsvd_grain_apply")
     return y
 
 

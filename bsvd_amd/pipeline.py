@@ -46,6 +46,12 @@ a variance-stabilising transform.  The colour planes are remapped by the curve's
 that starts a scene gives the curve (``frame_io.estimate_noise_curve``) and every later frame of the scene uses its tables.  No trained
 checkpoint has been run through it: its effect on denoising quality is not known.
 
+``grain`` puts film grain back after denoising, as a MODEL instead of the removed signal that ``strength`` mixes back: a
+``frame_io.GrainModel`` (its strength against brightness, its spatial correlation) the caller made, or 'scene' -- the first frame of every
+scene to emerge has its source and result measured on the device (``frame_io.estimate_grain``: one host synchronisation per scene), and the
+model fitted from it is synthesised onto that frame and every later frame of the scene (``frame_io.apply_grain``), after the inverse
+transform and the strength blend and before the encoder and its dither.  Nothing has been measured on real footage.
+
 ``cuts`` is what the pipelines know about scene cuts: None (nothing: the footage is one scene, as before) or 'auto' -- every frame is scored
 against the one before it on the device (``frame_io.scene_scores`` / ``scene_cuts``; ``cut_threshold``) and a frame that scores as a scene
 start is fed with ``cut=True``: no temporal-fusion conv mixes the two scenes, nothing is flushed, latency is unchanged.  A caller who knows
@@ -57,8 +63,9 @@ import numpy as np
 import torch
 
 from . import _lib
-from .frame_io import (CUT_THRESHOLD, VST_FLOOR, VST_TABLE_FLOATS, NoiseCurve, _check_gain, _luma_weights, _sigma_mode, _yuv_desc, _yuv_surface, blend_output,
-                       build_vst, check_cut_threshold, check_dither, check_strength, check_vst_floor, cut_scores, estimate_noise_curve, fill_noise_map,
+from .frame_io import (CUT_THRESHOLD, VST_FLOOR, VST_TABLE_FLOATS, GrainModel, NoiseCurve, _check_gain, _luma_weights, _sigma_mode, _yuv_desc, _yuv_surface,
+                       apply_grain, blend_output, build_vst, check_cut_threshold, check_dither, check_grain, check_strength, check_vst_floor, cut_scores,
+                       estimate_grain, estimate_noise_curve, fill_noise_map,
                        frames_to_input, network_size, output_to_frames, output_to_rgb, output_to_yuv, output_to_yuv420, rgb_frame_bytes, rgb_to_input,
                        scene_cuts, scene_scores, vst_forward, vst_identity, vst_inverse, vst_sigma, yuv420_frame_bytes, yuv420_picture_bytes,
                        yuv420_to_input, yuv_to_input)
@@ -420,6 +427,29 @@ class _Finish:
         return dict(dither=self.dither, dither_seed=self.seed, frame0=f0)
 
 
+class _Grain:
+    """the pipelines' ``grain``: None, a GrainModel or 'scene', with ``grain_amount`` and ``grain_seed``; the luma weights are the
+    finish's.  Checked before anything touches a device.  ``active``: grain is synthesised; ``scene``: its model is measured on the first
+    frame of every scene to emerge; ``model``: the model in use; ``emitted``: the frames given grain since construction / the last flush,
+    the stream index the block offsets are hashed from.  With the default nothing is allocated and nothing launched."""
+
+    def __init__(self, grain, amount, seed, matrix):
+        grain, self.amount, self.seed = check_grain(grain, amount, seed)
+        self.active = grain is not None
+        self.scene = isinstance(grain, str)
+        self.model = grain if isinstance(grain, GrainModel) else None
+        self.matrix = matrix
+        self.emitted = 0
+
+    def measure(self, src, y, picture):
+        """the scene's model from its first frame: source and result [1,>=3,Hp,Wp]; the host waits for 2 KB of statistics here"""
+        self.model = estimate_grain(src, y, picture=picture, matrix=self.matrix)
+        return self.model
+
+    def apply(self, y, frame0):
+        return apply_grain(y, self.model, self.amount, self.seed, frame0, self.matrix)
+
+
 def _pixel_format(pix_fmt, colour, pad=None, frame_shape=None):
     _check_pad(pad)
     if pix_fmt == "rgb24":
@@ -512,11 +542,16 @@ class ClipPipeline:
     the network.  'scene': the clip's scenes are its ``last_cuts`` with cuts='auto', otherwise the clip is one scene; each scene's curve is
     estimated from its first frame alone (times sigma_gain), so a curve that drifts within a scene (auto-exposure) is not followed until
     the next cut.  Table sets are per frame in one forward and one inverse launch; ``strength`` blends with the untransformed source.  A
-    blind model gets the transform and no plane.  What is known: ``frame_io.build_vst``.  The defaults launch nothing new and give the
-    bytes they gave."""
+    blind model gets the transform and no plane.  What is known: ``frame_io.build_vst``.
+    grain None | ``frame_io.GrainModel`` | 'scene', grain_amount, grain_seed: film grain from a model, after the inverse transform and the
+    strength blend, before the encoder (module docstring).  'scene': the clip's scenes are its ``last_cuts`` with cuts='auto', otherwise
+    the clip is one scene; the first frame of each scene is measured against the clip's own input (the host waits once per scene) and the
+    model is used for the scene's frames.  The pattern's frame index counts the frames submitted since construction.
+    ``last_grain_model``: the latest model.  The defaults launch nothing new and give the bytes they gave."""
 
     def __init__(self, model, sigma=None, depth=2, pix_fmt="rgb24", colour=None, pad=None, frame_shape=None, sigma_gain=1.0, cuts=None,
-                 cut_threshold=CUT_THRESHOLD, strength=1.0, dither=None, dither_seed=0, luma_matrix=None, vst=None, vst_floor=VST_FLOOR):
+                 cut_threshold=CUT_THRESHOLD, strength=1.0, dither=None, dither_seed=0, luma_matrix=None, vst=None, vst_floor=VST_FLOOR,
+                 grain=None, grain_amount=1.0, grain_seed=0):
         if depth < 1:
             raise ValueError("depth must be >= 1")
         self.auto_cuts, self.cut_threshold = _check_cuts_mode(cuts, cut_threshold, "ClipPipeline")
@@ -525,6 +560,8 @@ class ClipPipeline:
         self.vst = _Vst(model, vst, vst_floor, sigma, "ClipPipeline")
         self.fmt = _pixel_format(pix_fmt, colour, pad, frame_shape)
         self.finish = _Finish(self.fmt, strength, dither, dither_seed, luma_matrix)
+        self.grain = _Grain(grain, grain_amount, grain_seed, self.finish.matrix)
+        self.last_grain_model = self.grain.model
         self.alpha = getattr(self.fmt, "has_alpha", False)       # the clip's alpha codes ride beside the clip, [T,H,W] on the device
         self.model, self.sigma = model, sigma
         self.device = model._device()
@@ -569,8 +606,8 @@ class ClipPipeline:
                     kw = dict(cuts=self.last_cuts)
                 src = x
                 if self.vst.active:
-                    if self.finish.blends:
-                        src = x[:, :3].clone()            # strength blends in the picture's own domain
+                    if self.finish.blends or self.grain.scene:
+                        src = x[:, :3].clone()            # strength blends, and grain is measured, in the picture's own domain
                     tables = self._clip_tables(x, geom)
                     vst_forward(x, tables, fill_plane=self.vst.fills)
                 if self.model._pick_mode(T, H, W) == "clip":
@@ -582,6 +619,8 @@ class ClipPipeline:
                     y = vst_inverse(y.contiguous(), tables)
                 if self.finish.blends:
                     y = self.finish.blend(y.contiguous(), src)
+                if self.grain.active:
+                    y = self._clip_grain(y.contiguous(), src, geom)
                 kw = self.finish.dither_kw(T)
                 # held by the slot until its download completed
                 slot.dev_out = self.fmt.to_output(y, geom, alpha=slot.dev_alpha, **kw) if self.alpha else self.fmt.to_output(y, geom, **kw)
@@ -605,6 +644,17 @@ class ClipPipeline:
         sets = build_vst(estimate_noise_curve(first, picture=(geom.h, geom.w), gain=self.sigma_gain), self.vst.floor)
         scene_of = [sum(1 for s in starts[1:] if s <= t) for t in range(T)]
         return sets if len(starts) == T else sets[scene_of].contiguous()
+
+    def _clip_grain(self, y, src, geom):
+        """grain onto the clip's result, in place: the caller's model, or with grain='scene' each scene's own, measured on its first frame"""
+        T = y.shape[0]
+        starts = [0] + [int(c) for c in (self.last_cuts or []) if 0 < int(c) < T] if self.auto_cuts and self.grain.scene else [0]
+        for a, b in zip(starts, starts[1:] + [T]):
+            if self.grain.scene:
+                self.last_grain_model = self.grain.measure(src[a:a + 1], y[a:a + 1], (geom.h, geom.w))
+            self.grain.apply(y[a:b], self.grain.emitted + a)
+        self.grain.emitted += T
+        return y
 
     def results(self):
         """Drains every clip submitted so far, in submission order."""
@@ -700,11 +750,22 @@ class LiveStream:
     ``last_vst_sigma``: the scene's curve and the sigma' of the most recent input step ``feed`` has already waited for.  A blind model
     gets the transform and no plane.  What is known: ``frame_io.build_vst`` -- nothing about denoising quality, nothing on real footage.
 
+    grain None | ``frame_io.GrainModel`` | 'scene', grain_amount (default 1), grain_seed: film grain from a model (module docstring), on the
+    compute stream after the inverse transform and the strength blend and before the encoder and its dither.  A GrainModel: every frame
+    gets grain from it (``frame_io.apply_grain``); the block offsets are hashed from (grain_seed, the frames emitted since construction or
+    the last ``flush()``, the block).  'scene': whether a frame starts a scene -- the first feed after construction or ``flush()``,
+    ``cut=True``, a frame cuts='auto' flags -- is noted when it is fed; when the first frame of a scene EMERGES, ``latency`` feeds later,
+    its source (from the source ring, which exists for grain='scene' as it does for a strength below 1) and its result are measured
+    (``frame_io.estimate_grain``), the HOST WAITS for the 2 KB of statistics and fits the model -- once per scene, about the figures of
+    profiles/film_grain.txt --, and that model is used from that frame to the scene's last.  ``last_grain_model``: the latest model.  With
+    a strength below 1 the measured result is the blended one: the model describes what is still missing.  No temporal pooling beyond
+    the scene's first frame, no overlap blending of grain blocks, nothing measured on real footage.
+
     The defaults launch nothing new and give the bytes they gave."""
 
     def __init__(self, model, sigma=None, depth=2, overlap_blocks=None, frame_shape=None, pix_fmt="rgb24", colour=None, pad=None,
                  sigma_gain=1.0, cuts=None, cut_threshold=CUT_THRESHOLD, strength=1.0, dither=None, dither_seed=0, luma_matrix=None,
-                 vst=None, vst_floor=VST_FLOOR):
+                 vst=None, vst_floor=VST_FLOOR, grain=None, grain_amount=1.0, grain_seed=0):
         """frame_shape: optional (H, W) of the frames to come (the picture, also with ``pad``) -- the overlap decision (and with it
         ``latency``) is then final at construction instead of at the first feed."""
         if depth < 1:
@@ -725,7 +786,11 @@ class LiveStream:
         self.fmt = _pixel_format(pix_fmt, colour, pad, frame_shape)
         self._alpha = None                                    # formats with alpha: the ring of alpha planes (_AlphaRing), allocated with the slots
         self.finish = _Finish(self.fmt, strength, dither, dither_seed, luma_matrix)
-        self._source = None                                   # strength < 1: the ring of source frames (_SourceRing), allocated with the slots
+        self._source = None                                   # strength < 1 or grain='scene': the ring of source frames (_SourceRing), allocated with the slots
+        self.grain = _Grain(grain, grain_amount, grain_seed, self.finish.matrix)
+        self.last_grain_model = self.grain.model
+        self._scene_starts = collections.deque()             # grain='scene': per frame inside the network, does it start a scene?
+        self._grain_in_scene = False
         self.model, self.sigma, self.depth = model, sigma, depth
         self._overlap_wanted = (depth >= 2) if overlap_blocks is None else bool(overlap_blocks)
         self._overlap_explicit = overlap_blocks is not None
@@ -799,7 +864,7 @@ class LiveStream:
             self._in_scene = False
         if getattr(self.fmt, "has_alpha", False):
             self._alpha = _AlphaRing(self.latency + self.depth, geom.h, geom.w, getattr(torch, self.fmt.dtype.name), self.device)
-        self._source = _SourceRing(self.latency + self.depth, geom.net_h, geom.net_w, self.device) if self.finish.blends else None
+        self._source = _SourceRing(self.latency + self.depth, geom.net_h, geom.net_w, self.device) if self.finish.blends or self.grain.scene else None
         if self.auto_cuts:
             gh, gw = geom.h // 16, geom.w // 16
             self._grids = torch.zeros((2, 1, gh, gw), dtype=torch.int32, device=self.device)
@@ -867,8 +932,15 @@ class LiveStream:
         y = y.float()
         if self.vst.active:
             y = vst_inverse(y.contiguous(), self._tables.next_out() if self.vst.scene else self.vst.shared_tables(self.device))
-        if self._source is not None:
-            y = self.finish.blend(y.contiguous(), self._source.next_out())
+        src = self._source.next_out() if self._source is not None else None
+        if self.finish.blends:
+            y = self.finish.blend(y.contiguous(), src)
+        if self.grain.active:
+            y = y.contiguous()
+            if self.grain.scene and self._scene_starts.popleft():    # the scene's first frame emerges: measure, wait, fit
+                self.last_grain_model = self.grain.measure(src, y, (self.geom.h, self.geom.w))
+            self.grain.apply(y, self.grain.emitted)
+            self.grain.emitted += y.shape[0]
         kw = self.finish.dither_kw(y.shape[0])
         if self._alpha is None:
             return self.fmt.to_output(y, self.geom, **kw)
@@ -910,6 +982,9 @@ class LiveStream:
                         slot.dev_sigma.copy_(x[0, -1, 0, :1])          # the plane holds the estimate: one element of it, device to device
                     if self.vst.active:
                         self._vst_forward(slot, x, cut)
+                    if self.grain.scene:
+                        self._scene_starts.append(bool(cut) or not self._grain_in_scene)
+                        self._grain_in_scene = True
                 kw = dict(cut=True) if cut else {}
                 y = self.model.feed_overlapped(x, last=last, **kw) if self.overlap else self.model.feedin_one_element(x, **kw)
                 if y is not None:
@@ -972,5 +1047,8 @@ class LiveStream:
             self._tables.reset()
         self._in_scene = False
         self.finish.emitted = 0
+        self.grain.emitted = 0
+        self._scene_starts.clear()
+        self._grain_in_scene = False
         self._reopen_overlap()                        # the next stream decides again (free HBM may have changed)
         return outs

@@ -753,6 +753,64 @@ int bsvd_vst_inverse(float *y, int64_t y_frame_stride, int32_t frames, int32_t H
                      void *stream);
 
 /*
+ * Film grain: the statistics of the noise the network removed, and clean synthetic grain from a model fitted to them.  The denoise
+ * strength (bsvd_blend_planar) mixes the removed signal itself back -- chroma blotches, fixed-pattern residue and compression artefacts
+ * with it.  A grain MODEL keeps only two things of the removed noise: its standard deviation against the result's brightness and its
+ * spatial autocorrelation ("grain size").  bsvd_grain_stats reduces a source / result pair to 256 integers per frame; the fit is the
+ * host's (bsvd_amd/frame_io.py, GrainModel: 3 x 16 standard deviations, 3 x 24 coefficients of a causal lag-3 autoregression, a
+ * 128 x 128 unit-variance template per component); bsvd_grain_apply adds grain from the templates to the result, in place.  Added
+ * without a new BSVD_ABI_VERSION: discover the three entry points by symbol (dlsym), like the VST entry points above.
+ *
+ * The statistics, exactly (tests/grain_model.py reproduces all 256 integers bit for bit):
+ *   input     x (the source) and y (the result) [frames][>= 3][Hp][Wp] fp32, planes R, G, B, frames x_frame_stride / y_frame_stride FLOATS
+ *             apart, rows Wp apart.  The picture is the top-left H x W of each plane (4 <= H <= Hp, 13 <= W <= Wp); nothing outside it is
+ *             read (the mirror images of a padded tensor would count twice).
+ *   pixel     in fp32, every operation rounded once: d_c = x_c - y_c;
+ *             n0 = fmaf(w_B, d_B, fmaf(w_G, d_G, w_R * d_R)) (bsvd_blend_planar's luma term, in its order); n1 = d_B - n0; n2 = d_R - n0;
+ *             ly = fmaf(w_B, y_B, fmaf(w_G, y_G, w_R * y_R)); t = ly * 16; level l = t >= 15 ? 15 : (t >= 0 ? (int)t : 0) (NaN gives 0);
+ *             q_k = (int)rintf(min(max(n_k * 4096, -2047), 2047)), halves to even.
+ *             A pixel with a non-finite n_k is NOT COUNTED, and all three of its q are 0.
+ *   moments   over the counted pixels of the picture, per level l: N[l], and for k = 0 .. 2 the sums of q_k and of q_k^2.
+ *   products  for k = 0 .. 2 and the 46 lags (dy, dx) -- dy = 0 with dx = 0 .. 6, then dy = 1, 2, 3 with dx = -6 .. 6 each, in that order --
+ *             A[k][lag] = the sum over the anchors p = (r, c), 0 <= r <= H - 4 and 6 <= c <= W - 7, of q_k(p) q_k(p + (dy, dx)).  The
+ *             anchor set is the same for every lag: (H - 3) (W - 12) anchors.  These are the lags whose differences a causal lag-3
+ *             neighbourhood of 24 taps meets in its Yule-Walker system.
+ *   layout    per frame 256 int64: N[16] at 0, sum q_k at 16 + 16 k + l, sum q_k^2 at 64 + 16 k + l, A[k][lag] at 112 + 46 k + lag,
+ *             zeros at 250 .. 255.
+ * Every accumulated quantity is an integer: the result does not depend on the launch shape.  Sums are exact in int64 for every frame
+ * the other checks admit (|q| <= 2047: a product is below 2^22).
+ *
+ * The synthesis, exactly (tests/grain_model.py reproduces it bit for bit), per pixel (r, c) of the whole Hp x Wp plane of frame t:
+ *   block     (by, bx) = (r >> 5, c >> 5); n = (uint64)(frame0 + t) * 4 + 3 (the dither's frame number with the component no dither
+ *             uses); kf = fmix32(seed ^ fmix32((uint32)n ^ fmix32((uint32)(n >> 32)))); h = fmix32(kf ^ ((uint32)bx + (uint32)by *
+ *             0x9e3779b1)) with fmix32 as in BsvdDither above; oy = ((h >> 16) * 97) >> 16, ox = ((h & 0xffff) * 97) >> 16: both 0 .. 96.
+ *   sample    g_k = templates[k][oy + (r & 31)][ox + (c & 31)].  Neighbouring blocks are cut from unrelated places: no overlap blending.
+ *   scale     ly as above; u = ly * 16 - 0.5 (two roundings), clamped to [0, 15], NaN gives 0; i = min((int)u, 14); f = u - i;
+ *             s_k = std[k][i] + f * (std[k][i + 1] - std[k][i]), the product rounded before the add (bsvd_fill_nlf_plane's rule).
+ *   noise     n_k = (amount * s_k) * g_k.
+ *   to RGB    d_R = n2 + n0; d_B = n1 + n0; d_G = (n0 - (w_R * d_R + w_B * d_B)) * inv_wg, two products, one sum, one difference, one
+ *             product; y_c = y_c + d_c.  All fp32, no contraction.  inv_wg is the caller's 1 / w_G.
+ * What is known about it: profiles/film_grain.txt, on synthetic grain only.  Nothing has been measured on real footage, and no encoder
+ * has read the model: there is no AV1 / filmgrn1 table writer.  No overlap blending of blocks; no temporal pooling of the statistics.
+ *
+ * bsvd_grain_stats_bytes(frames): the bytes of `workspace`, frames * 256 * 8; -1 for frames <= 0.
+ * bsvd_grain_stats: zeroes the workspace itself, on the stream; afterwards it holds [frames][256] int64.  Returns -3, naming the argument
+ *   in bsvd_last_error(), without a device, for: a NULL pointer; x or y not 4-byte aligned, workspace not 8-byte aligned; frames outside
+ *   1 .. 65535; H < 4 or W < 13; Hp < H or Wp < W; a frame stride below 3 * Hp * Wp; a weight that is not finite.
+ * bsvd_grain_apply: y [frames][3][Hp][Wp], frames y_frame_stride FLOATS apart, in place.  templates: [3][128][128] fp32 in DEVICE memory;
+ *   std: [3][16] fp32 in HOST memory (read during the call).  Rows move as float4 when y is 16-byte aligned and Wp and the stride are
+ *   multiples of 4, as scalars otherwise; the same bits either way.  amount == 0 or an all-zero std: 0 is returned and nothing is
+ *   launched.  -3 for: a NULL pointer; y or templates not 4-byte aligned; frames outside 1 .. 65535; Hp or Wp <= 0; a stride below
+ *   3 * Hp * Wp; amount, a std value, a weight or inv_wg not finite; amount or a std value negative; frame0 negative.
+ */
+int64_t bsvd_grain_stats_bytes(int32_t frames);
+int bsvd_grain_stats(const float *x, int64_t x_frame_stride, const float *y, int64_t y_frame_stride, int32_t frames, int32_t H, int32_t W,
+                     int32_t Hp, int32_t Wp, const float luma_w[3], void *workspace /*[frames][256] int64*/, void *stream);
+int bsvd_grain_apply(float *y, int64_t y_frame_stride, int32_t frames, int32_t Hp, int32_t Wp, const float *templates /*[3][128][128], device*/,
+                     const float *std /*[3][16], host*/, float amount, const float luma_w[3], float inv_wg, uint32_t seed, int64_t frame0,
+                     void *stream);
+
+/*
  * What a scene-cut detector needs from a frame, computed on the device.  Each temporal-fusion conv mixes a frame with its two neighbours; a
  * caller who knows where a scene starts passes halo_prev = NULL / halo_next = NULL there (a clip end in mid-stream).  These two entry points
  * serve the caller who does not know: they reduce the planar fp32 tensor the *_to_planar entry points build -- so the result does not depend

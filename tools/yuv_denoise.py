@@ -34,6 +34,14 @@ steady_frames_per_s (wall clock, reads and writes included) over the steady stat
                                 the output finish, on the device: how much of the denoising to keep (one amount, or luma,chroma: 0.5,1.0
                                 keeps half the luma grain and removes all chroma noise), and dither at the quantiser (8 x 8 Bayer, or a
                                 per-frame hash) against banding (LiveStream(strength=, dither=)).  The visual effect is unmeasured on real footage
+    python tools/yuv_denoise.py IN OUT --size 1920x1080 --sigma 30 --grain scene | --grain STD[,STD_CHROMA]  [--grain-amount A] [--grain-seed N]
+                                film grain after denoising, from a MODEL instead of the removed signal (LiveStream(grain=)).  scene: the
+                                first frame of every scene to emerge is measured against its source on the device, a model (strength per
+                                luma level, spatial correlation) is fitted on the host -- one synchronisation per scene; combine with
+                                --cuts auto -- and clean grain is synthesised from it onto the scene's frames.  STD[,STD_CHROMA]: white
+                                grain of that standard deviation (8-bit code units) in luma and in the two colour differences.  The JSON
+                                line carries the last model's std curves (8-bit code units).  Nothing has been measured on real footage,
+                                and no encoder has read the model
 
     ffmpeg -i in.mp4 -pix_fmt yuv420p -f rawvideo - | python tools/yuv_denoise.py - - --size 1920x1080 --sigma 30 | ffmpeg -f rawvideo ...
                                                                                   (--pix-fmt defaults to yuv420p, ffmpeg's own default)
@@ -83,6 +91,19 @@ def parse_strength(text):
         raise argparse.ArgumentTypeError("--strength %r: S or S_LUMA,S_CHROMA, each in [0, 1]" % text) from None
 
 
+def parse_grain(text):
+    """--grain: 'scene', or STD[,STD_CHROMA] in 8-bit code units -> what LiveStream(grain=) takes"""
+    if text == "scene":
+        return text
+    try:
+        v = [float(p) / 255.0 for p in text.split(",")]
+        if len(v) not in (1, 2):
+            raise ValueError(text)
+        return frame_io.GrainModel.from_values([v[0], v[-1], v[-1]])
+    except ValueError:
+        raise argparse.ArgumentTypeError("--grain %r: scene, or STD[,STD_CHROMA] in 8-bit code units, not negative" % text) from None
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("input")
@@ -105,6 +126,9 @@ def main(argv=None):
     ap.add_argument("--strength", type=parse_strength, default=(1.0, 1.0), help="S or S_LUMA,S_CHROMA in [0, 1]: how much of the denoising to keep (default 1)")
     ap.add_argument("--dither", default="none", choices=["none", "ordered", "random"], help="dither at the quantiser, on the device")
     ap.add_argument("--dither-seed", type=int, default=0, help="seed of --dither random")
+    ap.add_argument("--grain", type=parse_grain, default=None, help="scene: a grain model measured at every scene start; STD[,STD_CHROMA]: white grain, 8-bit code units")
+    ap.add_argument("--grain-amount", type=float, default=1.0, help="factor on the model's standard deviations (default 1)")
+    ap.add_argument("--grain-seed", type=int, default=0, help="seed of the grain pattern")
     ap.add_argument("--depth", type=int, default=2)
     ap.add_argument("--ckpt", default=None)
     ap.add_argument("--precision", default="f16x3")
@@ -123,6 +147,10 @@ def main(argv=None):
         ap.error("one of --sigma, --noise-model, --vst and --vst-model is required")
     if a.noise_model is not None:
         a.sigma = a.noise_model
+    try:
+        frame_io.check_grain(a.grain, a.grain_amount, a.grain_seed)
+    except ValueError as e:
+        ap.error("--grain-amount / --grain-seed: %s" % e)
     W, H = map(int, a.size.lower().split("x"))
     rgb = a.pix_fmt in _lib.RGB_FORMATS                  # the RGB formats: 1-D frames too
     surface = a.pix_fmt in _lib.YUV_FORMATS or rgb       # the 1-D frames of the planar / 4:2:2 / 4:4:4 formats
@@ -146,7 +174,8 @@ def main(argv=None):
                       colour={"full_range": not a.limited_range} if rgb else {"matrix": a.matrix, "full_range": a.full_range, "chroma": a.chroma}, pad=pad,
                       cuts="auto" if a.cuts == "auto" else None, cut_threshold=a.cut_threshold,
                       strength=a.strength, dither=None if a.dither == "none" else a.dither, dither_seed=a.dither_seed,
-                      **(dict(vst=vst, vst_floor=vst_floor) if vst is not None else {}))
+                      **(dict(vst=vst, vst_floor=vst_floor) if vst is not None else {}),
+                      **(dict(grain=a.grain, grain_amount=a.grain_amount, grain_seed=a.grain_seed) if a.grain is not None else {}))
     found = []
     fin = sys.stdin.buffer if a.input == "-" else open(a.input, "rb")
     fout = sys.stdout.buffer if a.output == "-" else open(a.output, "wb")
@@ -198,6 +227,10 @@ def main(argv=None):
         res["strength"] = list(a.strength)
     if a.dither != "none":
         res["dither"] = a.dither
+    if a.grain is not None:
+        res["grain"] = "scene" if a.grain == "scene" else "model"
+        res["grain_amount"] = a.grain_amount
+        res["last_grain_std"] = None if live.last_grain_model is None else (live.last_grain_model.std * 255.0).tolist()
     if a.cuts == "auto":
         res["cut_threshold"] = a.cut_threshold
         res["cuts"] = found
