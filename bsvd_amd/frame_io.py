@@ -58,12 +58,38 @@ def network_size(H, W):
     return (int(H) + 3) // 4 * 4, (int(W) + 3) // 4 * 4
 
 
+def _call(device, name, *args):
+    """the one way into the library's launching entry points: ``name(*args, stream)`` on ``device`` and torch's current stream there;
+    a status other than 0 raises under that name"""
+    lib = require_hip()
+    with torch.cuda.device(device):
+        _lib.check(getattr(lib, name)(*args, _stream()), name)
+
+
 def _pair(v, what):
     try:
         a, b = v
         return int(a), int(b)
     except (TypeError, ValueError):
         raise ValueError("%s: expected a pair of ints, got %r" % (what, v)) from None
+
+
+def _number(v, message, cast=float):
+    """cast(v), or ValueError(message) for what is no number"""
+    try:
+        return cast(v)
+    except (TypeError, ValueError):
+        raise ValueError(message) from None
+
+
+def _tensor(t, dtype, shape, device, message, contiguous=True):
+    """the tensor-argument check: ``dtype`` (one, or a tuple of them), ``shape`` (None: any length), ``device`` (a torch.device, or 'cuda':
+    any HIP device) and contiguity -> t; ValueError(message) otherwise"""
+    if (not isinstance(t, torch.Tensor) or t.dtype not in (dtype if isinstance(dtype, tuple) else (dtype,))
+            or (not t.is_cuda if device == "cuda" else t.device != device) or t.dim() != len(shape)
+            or any(n is not None and s != n for s, n in zip(t.shape, shape)) or (contiguous and not t.is_contiguous())):
+        raise ValueError(message)
+    return t
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -86,10 +112,7 @@ def _check_clamp(clamp):
 
 
 def _check_gain(gain):
-    try:
-        g = float(gain)
-    except (TypeError, ValueError):
-        raise ValueError("sigma_gain: expected a positive number, got %r" % (gain,)) from None
+    g = _number(gain, "sigma_gain: expected a positive number, got %r" % (gain,))
     if not (0.0 < g < float("inf")):
         raise ValueError("sigma_gain %r: must be positive and finite" % (gain,))
     return g
@@ -118,10 +141,7 @@ class NoiseCurve:
     @classmethod
     def from_model(cls, a, b):
         """the Poisson-Gaussian sensor model: sigma(I) = sqrt(max(a I + b, 0)) at the level centres, I and sigma in [0,1] units"""
-        try:
-            a, b = float(a), float(b)
-        except (TypeError, ValueError):
-            raise ValueError("NoiseCurve.from_model: expected two numbers, got %r, %r" % (a, b)) from None
+        a, b = (_number(v, "NoiseCurve.from_model: expected two numbers, got %r, %r" % (a, b)) for v in (a, b))
         return cls([max(a * (l + 0.5) / NLF_LEVELS + b, 0.0) ** 0.5 for l in range(NLF_LEVELS)])
 
     def __eq__(self, other):
@@ -165,9 +185,7 @@ def _sigma_mode(sigma, T=None):
 
 
 def _planes(x, what):
-    if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or not x.is_cuda or x.dim() != 4 or not x.is_contiguous():
-        raise ValueError("%s: expected a contiguous float32 device tensor [T,C,H,W]" % what)
-    return x.shape
+    return _tensor(x, torch.float32, (None,) * 4, "cuda", "%s: expected a contiguous float32 device tensor [T,C,H,W]" % what).shape
 
 
 def estimate_sigma(x, picture=None, gain=1.0, clamp=(0.0, SIGMA_MAX), return_hist=False):
@@ -187,35 +205,24 @@ def estimate_sigma(x, picture=None, gain=1.0, clamp=(0.0, SIGMA_MAX), return_his
     if C < 3:
         raise ValueError("estimate_sigma: the estimate pools the three colour planes, x has %d" % C)
     H, W = (Hp, Wp) if picture is None else _pair(picture, "picture")
-    lib = require_hip()
     hist = torch.empty((T, SIGMA_BINS), dtype=torch.int32, device=x.device)
     out = torch.empty((T,), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(lib.bsvd_estimate_sigma(x.data_ptr(), T, 3, H, W, Hp, Wp, C * Hp * Wp, gain, lo, hi, hist.data_ptr(), out.data_ptr(),
-                                           _stream()), "bsvd_estimate_sigma")
+    _call(x.device, "bsvd_estimate_sigma", x.data_ptr(), T, 3, H, W, Hp, Wp, C * Hp * Wp, gain, lo, hi, hist.data_ptr(), out.data_ptr())
     return (out, hist.view(torch.uint32)) if return_hist else out
 
 
 def fill_sigma_plane(x, sigma_dev):
     """x: fp32 device tensor [T,C,Hp,Wp]; its last plane of frame t becomes sigma_dev[t] (fp32 device tensor [T]), in place, on the device"""
     T, C, Hp, Wp = _planes(x, "fill_sigma_plane")
-    if (not isinstance(sigma_dev, torch.Tensor) or sigma_dev.dtype != torch.float32 or sigma_dev.device != x.device
-            or tuple(sigma_dev.shape) != (T,) or not sigma_dev.is_contiguous()):
-        raise ValueError("fill_sigma_plane: expected a contiguous float32 tensor [%d] on %s" % (T, x.device))
+    _tensor(sigma_dev, torch.float32, (T,), x.device, "fill_sigma_plane: expected a contiguous float32 tensor [%d] on %s" % (T, x.device))
     if C < 2:
         raise ValueError("fill_sigma_plane: x has no plane behind its picture planes")
-    lib = require_hip()
-    with torch.cuda.device(x.device):
-        _lib.check(lib.bsvd_fill_sigma_plane(x.data_ptr(), T, C - 1, Hp, Wp, C * Hp * Wp, sigma_dev.data_ptr(), _stream()),
-                   "bsvd_fill_sigma_plane")
+    _call(x.device, "bsvd_fill_sigma_plane", x.data_ptr(), T, C - 1, Hp, Wp, C * Hp * Wp, sigma_dev.data_ptr())
     return x
 
 
 def _check_min_count(min_count):
-    try:
-        n = int(min_count)
-    except (TypeError, ValueError):
-        raise ValueError("min_count: expected a positive integer, got %r" % (min_count,)) from None
+    n = _number(min_count, "min_count: expected a positive integer, got %r" % (min_count,), int)
     if n != min_count or not (1 <= n < 2 ** 31):
         raise ValueError("min_count %r: must be a positive integer" % (min_count,))
     return n
@@ -243,12 +250,9 @@ def estimate_noise_curve(x, picture=None, gain=1.0, clamp=(0.0, SIGMA_MAX), min_
     if C < 3:
         raise ValueError("estimate_noise_curve: the estimate pools the three colour planes, x has %d" % C)
     H, W = (Hp, Wp) if picture is None else _pair(picture, "picture")
-    lib = require_hip()
     hist = torch.empty((T, NLF_LEVELS, NLF_BINS), dtype=torch.int32, device=x.device)
     out = torch.empty((T, NLF_LEVELS), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(lib.bsvd_estimate_nlf(x.data_ptr(), T, H, W, Hp, Wp, C * Hp * Wp, gain, lo, hi, min_count, hist.data_ptr(), out.data_ptr(),
-                                         _stream()), "bsvd_estimate_nlf")
+    _call(x.device, "bsvd_estimate_nlf", x.data_ptr(), T, H, W, Hp, Wp, C * Hp * Wp, gain, lo, hi, min_count, hist.data_ptr(), out.data_ptr())
     return (out, hist.view(torch.uint32)) if return_hist else out
 
 
@@ -258,13 +262,10 @@ def noise_curve_from_hist(hist, gain=1.0, clamp=(0.0, SIGMA_MAX), min_count=NLF_
     lo, hi = _check_clamp(clamp)
     gain = _check_gain(gain)
     min_count = _check_min_count(min_count)
-    if (not isinstance(hist, torch.Tensor) or hist.dtype not in (torch.uint32, torch.int32) or not hist.is_cuda or hist.dim() != 3
-            or tuple(hist.shape[1:]) != (NLF_LEVELS, NLF_BINS) or not hist.is_contiguous()):
-        raise ValueError("noise_curve_from_hist: expected a contiguous uint32 device tensor [T,%d,%d]" % (NLF_LEVELS, NLF_BINS))
-    lib = require_hip()
+    _tensor(hist, (torch.uint32, torch.int32), (None, NLF_LEVELS, NLF_BINS), "cuda",
+            "noise_curve_from_hist: expected a contiguous uint32 device tensor [T,%d,%d]" % (NLF_LEVELS, NLF_BINS))
     out = torch.empty((hist.shape[0], NLF_LEVELS), dtype=torch.float32, device=hist.device)
-    with torch.cuda.device(hist.device):
-        _lib.check(lib.bsvd_finish_nlf(hist.data_ptr(), hist.shape[0], gain, lo, hi, min_count, out.data_ptr(), _stream()), "bsvd_finish_nlf")
+    _call(hist.device, "bsvd_finish_nlf", hist.data_ptr(), hist.shape[0], gain, lo, hi, min_count, out.data_ptr())
     return out
 
 
@@ -274,14 +275,11 @@ def fill_noise_map(x, curve):
     the 3 x 3 box means of R, G, B (replicate borders) mixed 1:2:1 give a position on the level axis, and the curve is interpolated linearly
     between the level centres.  A flat curve gives exactly that value everywhere; the map is finite whatever the colour planes hold."""
     T, C, Hp, Wp = _planes(x, "fill_noise_map")
-    if (not isinstance(curve, torch.Tensor) or curve.dtype != torch.float32 or curve.device != x.device
-            or tuple(curve.shape) != (T, NLF_LEVELS) or not curve.is_contiguous()):
-        raise ValueError("fill_noise_map: expected a contiguous float32 tensor [%d,%d] on %s" % (T, NLF_LEVELS, x.device))
+    _tensor(curve, torch.float32, (T, NLF_LEVELS), x.device,
+            "fill_noise_map: expected a contiguous float32 tensor [%d,%d] on %s" % (T, NLF_LEVELS, x.device))
     if C < 4:
         raise ValueError("fill_noise_map: x needs three colour planes and a plane behind them, it has %d" % C)
-    lib = require_hip()
-    with torch.cuda.device(x.device):
-        _lib.check(lib.bsvd_fill_nlf_plane(x.data_ptr(), T, C - 1, Hp, Wp, C * Hp * Wp, curve.data_ptr(), _stream()), "bsvd_fill_nlf_plane")
+    _call(x.device, "bsvd_fill_nlf_plane", x.data_ptr(), T, C - 1, Hp, Wp, C * Hp * Wp, curve.data_ptr())
     return x
 
 
@@ -295,10 +293,7 @@ VST_FLOOR = _lib.VST_FLOOR
 
 def check_vst_floor(floor):
     """``floor``: the least sigma the transform divides by, in [2^-10, 1] -> float; ValueError otherwise"""
-    try:
-        f = float(floor)
-    except (TypeError, ValueError):
-        raise ValueError("vst_floor: expected a number in [2^-10, 1], got %r" % (floor,)) from None
+    f = _number(floor, "vst_floor: expected a number in [2^-10, 1], got %r" % (floor,))
     if isinstance(floor, bool) or not (_lib.VST_FLOOR_MIN <= f <= 1.0):
         raise ValueError("vst_floor %r: must lie in [2^-10, 1] (the tables' knots stay apart and their reciprocals finite)" % (floor,))
     return f
@@ -306,10 +301,10 @@ def check_vst_floor(floor):
 
 def _vst_tables(tables, T, device, what):
     """a table tensor [1 | T, VST_TABLE_FLOATS] -> the table stride in sets (0: shared)"""
-    if (not isinstance(tables, torch.Tensor) or tables.dtype != torch.float32 or tables.device != device or tables.dim() != 2
-            or tables.shape[1] != VST_TABLE_FLOATS or tables.shape[0] not in (1, T) or not tables.is_contiguous()):
-        raise ValueError("%s: tables must be a contiguous float32 tensor [1,%d] (shared) or [%d,%d] (per frame) on %s (build_vst)"
-                         % (what, VST_TABLE_FLOATS, T, VST_TABLE_FLOATS, device))
+    message = ("%s: tables must be a contiguous float32 tensor [1,%d] (shared) or [%d,%d] (per frame) on %s (build_vst)"
+               % (what, VST_TABLE_FLOATS, T, VST_TABLE_FLOATS, device))
+    if _tensor(tables, torch.float32, (None, VST_TABLE_FLOATS), device, message).shape[0] not in (1, T):
+        raise ValueError(message)
     return 0 if tables.shape[0] == 1 else 1
 
 
@@ -325,19 +320,17 @@ def build_vst(curve, floor=VST_FLOOR, out=None):
     (profiles/vst.txt).  No trained checkpoint has been run through it: the effect on denoising quality has not been measured, and nothing
     has been measured on real footage.  The transform changes the tone curve the network sees."""
     floor = check_vst_floor(floor)
-    lib = require_hip()
     if isinstance(curve, NoiseCurve):
         curve = torch.tensor([curve.values], dtype=torch.float32).to(out.device if out is not None else torch.device("cuda", torch.cuda.current_device()))
-    if (not isinstance(curve, torch.Tensor) or curve.dtype != torch.float32 or not curve.is_cuda or curve.dim() != 2
-            or curve.shape[1] != NLF_LEVELS or curve.shape[0] < 1 or not curve.is_contiguous()):
-        raise ValueError("build_vst: expected a NoiseCurve or a contiguous float32 device tensor [n,%d]" % NLF_LEVELS)
-    n = curve.shape[0]
+    message = "build_vst: expected a NoiseCurve or a contiguous float32 device tensor [n,%d]" % NLF_LEVELS
+    n = _tensor(curve, torch.float32, (None, NLF_LEVELS), "cuda", message).shape[0]
+    if n < 1:
+        raise ValueError(message)
     if out is None:
         out = torch.empty((n, VST_TABLE_FLOATS), dtype=torch.float32, device=curve.device)
     elif _vst_tables(out, n, curve.device, "build_vst(out=)") != (0 if n == 1 else 1):
         raise ValueError("build_vst(out=): %d table sets for %d curves" % (out.shape[0], n))
-    with torch.cuda.device(curve.device):
-        _lib.check(lib.bsvd_vst_build(curve.data_ptr(), n, floor, out.data_ptr(), _stream()), "bsvd_vst_build")
+    _call(curve.device, "bsvd_vst_build", curve.data_ptr(), n, floor, out.data_ptr())
     return out
 
 
@@ -360,10 +353,7 @@ def vst_forward(x, tables, fill_plane=True):
     if fill_plane and C < 4:
         raise ValueError("vst_forward(fill_plane=True): x needs a plane behind its colour planes, it has %d (a blind model: fill_plane=False)" % C)
     stride = _vst_tables(tables, T, x.device, "vst_forward")
-    lib = require_hip()
-    with torch.cuda.device(x.device):
-        _lib.check(lib.bsvd_vst_forward(x.data_ptr(), T, Hp, Wp, C * Hp * Wp, C - 1 if fill_plane else -1, tables.data_ptr(), stride, _stream()),
-                   "bsvd_vst_forward")
+    _call(x.device, "bsvd_vst_forward", x.data_ptr(), T, Hp, Wp, C * Hp * Wp, C - 1 if fill_plane else -1, tables.data_ptr(), stride)
     return x
 
 
@@ -375,9 +365,7 @@ def vst_inverse(y, tables):
     if C < 3:
         raise ValueError("vst_inverse: the transform takes the three colour planes, y has %d" % C)
     stride = _vst_tables(tables, T, y.device, "vst_inverse")
-    lib = require_hip()
-    with torch.cuda.device(y.device):
-        _lib.check(lib.bsvd_vst_inverse(y.data_ptr(), C * Hp * Wp, T, Hp, Wp, tables.data_ptr(), stride, _stream()), "bsvd_vst_inverse")
+    _call(y.device, "bsvd_vst_inverse", y.data_ptr(), C * Hp * Wp, T, Hp, Wp, tables.data_ptr(), stride)
     return y
 
 
@@ -420,10 +408,7 @@ CUT_THRESHOLD = 10.0
 
 
 def check_cut_threshold(threshold):
-    try:
-        t = float(threshold)
-    except (TypeError, ValueError):
-        raise ValueError("cut_threshold: expected a positive number, got %r" % (threshold,)) from None
+    t = _number(threshold, "cut_threshold: expected a positive number, got %r" % (threshold,))
     if isinstance(threshold, bool) or not (0.0 < t < float("inf")):
         raise ValueError("cut_threshold %r: must be positive and finite" % (threshold,))
     return t
@@ -448,23 +433,18 @@ def scene_scores(x, picture=None, prev=None, out=None):
     ``out=(sad, grid)``: write into these tensors instead of new ones."""
     T, C, Hp, Wp, H, W = _scene_picture(x, picture, "scene_scores")
     GH, GW = H // SCENE_BLOCK, W // SCENE_BLOCK
-    if prev is not None and (not isinstance(prev, torch.Tensor) or prev.dtype != torch.int32 or prev.device != x.device
-                             or tuple(prev.shape) != (GH, GW) or not prev.is_contiguous()):
-        raise ValueError("scene_scores: prev must be a contiguous int32 tensor [%d,%d] on %s" % (GH, GW, x.device))
-    lib = require_hip()
+    if prev is not None:
+        _tensor(prev, torch.int32, (GH, GW), x.device, "scene_scores: prev must be a contiguous int32 tensor [%d,%d] on %s" % (GH, GW, x.device))
     if out is None:
         sad = torch.empty((T,), dtype=torch.int64, device=x.device)
         grid = torch.empty((T, GH, GW), dtype=torch.int32, device=x.device)
     else:
         sad, grid = out
-        if (sad.dtype != torch.int64 or tuple(sad.shape) != (T,) or grid.dtype != torch.int32 or tuple(grid.shape) != (T, GH, GW)
-                or sad.device != x.device or grid.device != x.device or not sad.is_contiguous() or not grid.is_contiguous()):
-            raise ValueError("scene_scores: out must be (int64 [%d], int32 [%d,%d,%d]) on %s" % (T, T, GH, GW, x.device))
-    with torch.cuda.device(x.device):
-        st = _stream()
-        _lib.check(lib.bsvd_scene_grid(x.data_ptr(), T, H, W, Hp, Wp, C * Hp * Wp, grid.data_ptr() if GH * GW else None, st), "bsvd_scene_grid")
-        _lib.check(lib.bsvd_scene_diff(grid.data_ptr() if GH * GW else None, None if prev is None or not GH * GW else prev.data_ptr(), T, GH * GW,
-                                       sad.data_ptr(), st), "bsvd_scene_diff")
+        for t, dtype, shape in ((sad, torch.int64, (T,)), (grid, torch.int32, (T, GH, GW))):
+            _tensor(t, dtype, shape, x.device, "scene_scores: out must be (int64 [%d], int32 [%d,%d,%d]) on %s" % (T, T, GH, GW, x.device))
+    _call(x.device, "bsvd_scene_grid", x.data_ptr(), T, H, W, Hp, Wp, C * Hp * Wp, grid.data_ptr() if GH * GW else None)
+    _call(x.device, "bsvd_scene_diff", grid.data_ptr() if GH * GW else None, None if prev is None or not GH * GW else prev.data_ptr(), T, GH * GW,
+          sad.data_ptr())
     return sad, grid
 
 
@@ -526,15 +506,17 @@ def check_dither(dither, dither_seed=0, frame0=0):
     """``dither`` None | 'ordered' | 'random', ``dither_seed`` in [0, 2^32), ``frame0`` >= 0 -> (mode, seed, frame0); ValueError otherwise"""
     if dither is not None and not (isinstance(dither, str) and dither in DITHERS):
         raise ValueError("dither %r: None, 'ordered' or 'random'" % (dither,))
-    try:
-        seed, f0 = int(dither_seed), int(frame0)
-    except (TypeError, ValueError):
-        raise ValueError("dither_seed / frame0: expected ints, got %r / %r" % (dither_seed, frame0)) from None
+    seed, f0 = (_number(v, "dither_seed / frame0: expected ints, got %r / %r" % (dither_seed, frame0), int) for v in (dither_seed, frame0))
     if not 0 <= seed < 2 ** 32:
         raise ValueError("dither_seed %r: 0 <= seed < 2^32" % (dither_seed,))
+    return _lib.DITHER[dither], seed, _stream_index(frame0, f0)
+
+
+def _stream_index(frame0, f0):
+    """``frame0`` as an int -> the same; ValueError outside [0, 2^62)"""
     if not 0 <= f0 < 2 ** 62:
         raise ValueError("frame0 %r: the stream index of the first frame, not negative" % (frame0,))
-    return _lib.DITHER[dither], seed, f0
+    return f0
 
 
 def _dither_struct(dither, dither_seed, frame0):
@@ -571,11 +553,8 @@ def blend_output(y, x, strength, matrix="bt709"):
     _planes(x, "blend_output(x)")
     if y.shape[1] != 3 or x.shape[1] < 3 or x.shape[0] != y.shape[0] or x.shape[2:] != y.shape[2:] or x.device != y.device:
         raise ValueError("blend_output: y [T,3,Hp,Wp] and x [T,3(+1),Hp,Wp] on one device, got %s and %s" % (tuple(y.shape), tuple(x.shape)))
-    lib = require_hip()
     T, _, Hp, Wp = y.shape
-    with torch.cuda.device(y.device):
-        _lib.check(lib.bsvd_blend_planar(y.data_ptr(), 3 * Hp * Wp, x.data_ptr(), x.shape[1] * Hp * Wp, T, Hp, Wp, sl, sc, w, _stream()),
-                   "bsvd_blend_planar")
+    _call(y.device, "bsvd_blend_planar", y.data_ptr(), 3 * Hp * Wp, x.data_ptr(), x.shape[1] * Hp * Wp, T, Hp, Wp, sl, sc, w)
     return y
 
 
@@ -769,11 +748,8 @@ def grain_stats(x, y, picture=None, matrix="bt709"):
     if Cx < 3 or Cy < 3 or (Tx, Hp, Wp) != (Ty, Hy, Wy) or x.device != y.device:
         raise ValueError("grain_stats: x [T,>=3,Hp,Wp] and y [T,>=3,Hp,Wp] on one device, got %s and %s" % (tuple(x.shape), tuple(y.shape)))
     H, W = (Hp, Wp) if picture is None else _pair(picture, "picture")
-    lib = require_hip()
     out = torch.empty((Tx, GRAIN_STATS), dtype=torch.int64, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(lib.bsvd_grain_stats(x.data_ptr(), Cx * Hp * Wp, y.data_ptr(), Cy * Hp * Wp, Tx, H, W, Hp, Wp, w, out.data_ptr(), _stream()),
-                   "bsvd_grain_stats")
+    _call(x.device, "bsvd_grain_stats", x.data_ptr(), Cx * Hp * Wp, y.data_ptr(), Cy * Hp * Wp, Tx, H, W, Hp, Wp, w, out.data_ptr())
     return out
 
 
@@ -798,16 +774,10 @@ def check_grain(grain, amount=1.0, seed=0):
     -> (grain, amount, seed); ValueError otherwise.  Needs no device."""
     if grain is not None and not isinstance(grain, GrainModel) and not (isinstance(grain, str) and grain == "scene"):
         raise ValueError("grain %r: None, a GrainModel or 'scene'" % (grain,))
-    try:
-        a = float(amount)
-    except (TypeError, ValueError):
-        raise ValueError("grain_amount: expected a number >= 0, got %r" % (amount,)) from None
+    a = _number(amount, "grain_amount: expected a number >= 0, got %r" % (amount,))
     if isinstance(amount, bool) or not (0.0 <= a < 3e38):
         raise ValueError("grain_amount %r: must be finite and not negative" % (amount,))
-    try:
-        s = int(seed)
-    except (TypeError, ValueError):
-        raise ValueError("grain_seed: expected an int, got %r" % (seed,)) from None
+    s = _number(seed, "grain_seed: expected an int, got %r" % (seed,), int)
     if s != seed or not 0 <= s < 2 ** 32:
         raise ValueError("grain_seed %r: 0 <= seed < 2^32" % (seed,))
     return grain, a, s
@@ -823,12 +793,7 @@ def apply_grain(y, model, amount=1.0, seed=0, frame0=0, matrix="bt709"):
     if not isinstance(model, GrainModel):
         raise ValueError("apply_grain: model must be a GrainModel, got %r" % (model,))
     _, amount, seed = check_grain(model, amount, seed)
-    try:
-        f0 = int(frame0)
-    except (TypeError, ValueError):
-        raise ValueError("frame0: expected an int, got %r" % (frame0,)) from None
-    if not 0 <= f0 < 2 ** 62:
-        raise ValueError("frame0 %r: the stream index of the first frame, not negative" % (frame0,))
+    f0 = _stream_index(frame0, _number(frame0, "frame0: expected an int, got %r" % (frame0,), int))
     w = _luma_weights(matrix)
     if not w[1] > 0.0:
         raise ValueError("apply_grain: matrix %r has no green weight to divide by" % (matrix,))
@@ -837,14 +802,72 @@ def apply_grain(y, model, amount=1.0, seed=0, frame0=0, matrix="bt709"):
         raise ValueError("apply_grain: y must have three planes, it has %d" % C)
     if amount == 0.0 or model.is_zero:
         return y
-    lib = require_hip()
     std = (ctypes.c_float * (3 * GRAIN_LEVELS))(*[float(v) for v in model.std.reshape(-1)])
     inv_wg = ctypes.c_float(1.0 / float(w[1])).value
-    tmpl = model.device_templates(y.device)
-    with torch.cuda.device(y.device):
-        _lib.check(lib.bsvd_grain_apply(y.data_ptr(), 3 * Hp * Wp, T, Hp, Wp, tmpl.data_ptr(), std, amount, w, inv_wg, seed, f0, _stream()),
-                   "bsvd_grain_apply")
+    _call(y.device, "bsvd_grain_apply", y.data_ptr(), 3 * Hp * Wp, T, Hp, Wp, model.device_templates(y.device).data_ptr(), std, amount, w, inv_wg,
+          seed, f0)
     return y
+
+
+# ---------------------------------------------------------------------------------------------------
+# the two cores of the conversions: what the four ``*_to_input`` and the four ``output_to_*`` functions share
+
+def _frames_of(buf):
+    """T of a surface buffer [T, bytes], where its shape says so already (the length check of per-frame ``sigma`` values)"""
+    return buf.shape[0] if isinstance(buf, torch.Tensor) and buf.dim() == 2 else None
+
+
+def _decode(names, src, T, C, H, W, pad_to, sigma, sigma_gain, describe, head=()):
+    """The decode core: ``src`` (the checked device tensor of T frames) -> fp32 [T, C(+1), Hp, Wp].  ``names``: the (plain, padded) entry
+    points -- ``pad_to`` given, also to the size the picture has, takes the padded one; plain None: one entry point serves both.
+    ``sigma`` / ``sigma_gain`` exist here alone: None or a number is the constant the entry point writes; every other kind converts with
+    the plane at 0 and hands over to ``_with_sigma``.  ``describe()``, called once ``sigma`` is understood: the format's own checks ->
+    (the arguments between the sizes and ``extra``, the alpha plane to return beside the tensor or None); ``head``: those before H, W."""
+    mode = _sigma_mode(sigma, T)
+    per_frame = mode[0] != "const"
+    if per_frame:
+        gain = _check_gain(sigma_gain)
+    const = 0.0 if per_frame else sigma
+    tail, alpha = describe()
+    H, W = int(H), int(W)
+    plain, padded = names
+    Hp, Wp = (H, W) if pad_to is None else _pair(pad_to, "pad_to")
+    sizes = (H, W) if pad_to is None and plain is not None else (H, W, Hp, Wp)
+    extra = 0 if const is None else 1
+    x = torch.empty((src.shape[0], C + extra, max(Hp, 0), max(Wp, 0)), dtype=torch.float32, device=src.device)
+    _call(src.device, plain if len(sizes) == 2 else padded, src.data_ptr(), x.data_ptr(), src.shape[0], *head, *sizes, *tail, extra,
+          float(const or 0.0))
+    if per_frame:
+        x = _with_sigma(x, mode, (H, W), gain)
+    return x if alpha is None else (x, alpha)
+
+
+def _encode(what, names, y, crop_to, describe, dith=None, out=None, zeroed=False, labels=("10-bit", "10-bit"), head=()):
+    """The encode core: ``y`` (checked, fp32 [T,C,Hp,Wp]) -> the surfaces.  ``names``: the (plain, cropped, dithered) entry points -- a
+    BsvdDither takes the dithered one, else ``crop_to`` given, also to the size ``y`` has, the cropped one; plain None: the cropped one
+    serves both.  ``describe(T, H, W)``: the format's own checks for H x W surfaces -> (the descriptor whose frame_stride is the buffer's, or
+    None; the bytes of a frame, or without a descriptor the shape of the result; 16-bit samples?; the arguments behind the sizes).
+    ``out`` exists here alone: without it the result is allocated, ``zeroed`` where a pitch or an offset leaves bytes no kernel writes;
+    with it, it is checked (``labels``: how ``_surface_buffer``'s messages name the format)."""
+    plain, cropped, dithered = names
+    T, _, Hp, Wp = y.shape
+    H, W = (Hp, Wp) if crop_to is None else _pair(crop_to, "crop_to")
+    desc, size, sixteen, tail = describe(T, H, W)
+    y = y.contiguous()
+    if out is None:
+        out = (torch.zeros if zeroed else torch.empty)(size if desc is None else (T, size), dtype=torch.uint8, device=y.device)
+    elif out.device != y.device:
+        raise ValueError("%s: out is on %s, y on %s" % (what, out.device, y.device))
+    if desc is not None:
+        desc.frame_stride = _surface_buffer(out, T, size, sixteen, what + "(out=)", *labels)
+    if dith is not None:
+        name, sizes, tail = dithered, (Hp, Wp, H, W), tail + (ctypes.byref(dith),)
+    elif crop_to is not None or plain is None:
+        name, sizes = cropped, (Hp, Wp, H, W)
+    else:
+        name, sizes = plain, (H, W)
+    _call(y.device, name, y.data_ptr(), out.data_ptr(), T, *head, *sizes, *tail)
+    return out
 
 
 def frames_to_input(frames_u8, sigma=None, hwc=True, pad_to=None, sigma_gain=1.0):
@@ -853,50 +876,23 @@ def frames_to_input(frames_u8, sigma=None, hwc=True, pad_to=None, sigma_gain=1.0
     reflect-padded on the right and bottom (F.pad(..., mode='reflect') of the unpadded result, bit for bit).  ``sigma='auto'``: the
     noise-map plane of frame t holds that frame's own estimate (``estimate_sigma`` of the picture, times ``sigma_gain``); a sequence or a
     device tensor [T]: the caller's per-frame values."""
-    lib = require_hip()
-    if frames_u8.dtype != torch.uint8 or not frames_u8.is_cuda or frames_u8.dim() != 4:
-        raise ValueError("expected a uint8 device tensor [T,H,W,C] or [T,C,H,W]")
-    x = frames_u8.contiguous()
+    require_hip()                                           # without a device that is what the caller hears, whatever was passed
+    x = _tensor(frames_u8, torch.uint8, (None,) * 4, "cuda", "expected a uint8 device tensor [T,H,W,C] or [T,C,H,W]", contiguous=False).contiguous()
     T, H, W, C = x.shape if hwc else (x.shape[0], x.shape[2], x.shape[3], x.shape[1])
-    mode = _sigma_mode(sigma, T)
-    if mode[0] != "const":
-        gain = _check_gain(sigma_gain)
-        return _with_sigma(frames_to_input(x, 0.0, hwc, pad_to), mode, (H, W), gain)
-    extra = 0 if sigma is None else 1
-    if pad_to is not None:
-        Hp, Wp = _pair(pad_to, "pad_to")
-        y = torch.empty((T, C + extra, max(Hp, 0), max(Wp, 0)), dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            _lib.check(lib.bsvd_u8_to_planar_pad(x.data_ptr(), y.data_ptr(), T, C, H, W, Hp, Wp, 1 if hwc else 0, extra,
-                                                 float(sigma or 0.0), _stream()), "bsvd_u8_to_planar_pad")
-        return y
-    y = torch.empty((T, C + extra, H, W), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(lib.bsvd_u8_to_planar(x.data_ptr(), y.data_ptr(), T, C, H, W, 1 if hwc else 0, extra,
-                                         float(sigma or 0.0), _stream()), "bsvd_u8_to_planar")
-    return y
+    return _decode(("bsvd_u8_to_planar", "bsvd_u8_to_planar_pad"), x, T, C, H, W, pad_to, sigma, sigma_gain,
+                   lambda: ((1 if hwc else 0,), None), head=(C,))
 
 
 def output_to_frames(y, hwc=True, rgb2bgr=False, crop_to=None):
     """y: fp32 device tensor [T,C,H,W] -> uint8 [T,H,W,C] (or [T,C,H,W]): clamp [0,1], x255, round half to even.  ``crop_to=(H, W)``:
     the frames of ``y[..., :H, :W]``; the rows and columns beyond are not read."""
-    lib = require_hip()
-    if y.dtype != torch.float32 or not y.is_cuda or y.dim() != 4:
-        raise ValueError("expected a float32 device tensor [T,C,H,W]")
-    y = y.contiguous()
-    T, C, H, W = y.shape
-    if crop_to is not None:
-        Hc, Wc = _pair(crop_to, "crop_to")
-        out = torch.empty((T, max(Hc, 0), max(Wc, 0), C) if hwc else (T, C, max(Hc, 0), max(Wc, 0)), dtype=torch.uint8, device=y.device)
-        with torch.cuda.device(y.device):
-            _lib.check(lib.bsvd_planar_to_u8_crop(y.data_ptr(), out.data_ptr(), T, C, H, W, Hc, Wc, 1 if hwc else 0, 1 if rgb2bgr else 0,
-                                                  _stream()), "bsvd_planar_to_u8_crop")
-        return out
-    out = torch.empty((T, H, W, C) if hwc else (T, C, H, W), dtype=torch.uint8, device=y.device)
-    with torch.cuda.device(y.device):
-        _lib.check(lib.bsvd_planar_to_u8(y.data_ptr(), out.data_ptr(), T, C, H, W, 1 if hwc else 0, 1 if rgb2bgr else 0,
-                                         _stream()), "bsvd_planar_to_u8")
-    return out
+    require_hip()                                           # as in frames_to_input
+    _tensor(y, torch.float32, (None,) * 4, "cuda", "expected a float32 device tensor [T,C,H,W]", contiguous=False)
+    C = y.shape[1]
+
+    def describe(T, H, W):
+        return None, (T, max(H, 0), max(W, 0), C) if hwc else (T, C, max(H, 0), max(W, 0)), False, (1 if hwc else 0, 1 if rgb2bgr else 0)
+    return _encode("output_to_frames", ("bsvd_planar_to_u8", "bsvd_planar_to_u8_crop", None), y, crop_to, describe, head=(C,))
 
 
 def _yuv_desc(H, W, pix_fmt, matrix, full_range, chroma, row_pitch, picture=False):
@@ -929,8 +925,8 @@ def yuv420_picture_bytes(H, W, pix_fmt, row_pitch=None):
 def _surface_buffer(buf, T, nbytes, sixteen, what, callers="10-bit", frames="10-bit"):
     """a surface buffer [T, >= frame_bytes] -> its frame stride in bytes.  sixteen: 16-bit samples; callers / frames: how the two
     messages about them name the format ("P010" / "p010" for the 4:2:0 functions)"""
-    if buf.dtype != torch.uint8 or not buf.is_cuda or buf.dim() != 2 or not buf.is_contiguous():
-        raise ValueError("%s: expected a contiguous uint8 device tensor [T, frame_bytes] (%s callers view their uint16 as bytes)" % (what, callers))
+    _tensor(buf, torch.uint8, (None, None), "cuda",
+            "%s: expected a contiguous uint8 device tensor [T, frame_bytes] (%s callers view their uint16 as bytes)" % (what, callers))
     if (T is not None and buf.shape[0] != T) or buf.shape[0] < 1 or buf.shape[1] < nbytes:
         raise ValueError("%s: shape %s, expected [%s, %d] (or longer rows: frames row-length bytes apart)"
                          % (what, tuple(buf.shape), "T" if T is None else T, nbytes))
@@ -949,27 +945,11 @@ def yuv420_to_input(buf, H, W, pix_fmt="nv12", matrix="bt709", full_range=False,
     and the result is [T,3(+1),Hp,Wp]: the picture converted with its chroma clamped at the picture's own edges, then reflect-padded on
     the right and bottom.  ``sigma='auto'`` / a sequence / a device tensor [T] and ``sigma_gain``: as for ``frames_to_input``; the
     estimate is taken on the converted RGB, where 4:2:0 chroma has smoothed the noise of two planes: expect it to read low (``sigma_gain``)."""
-    mode = _sigma_mode(sigma, buf.shape[0] if isinstance(buf, torch.Tensor) and buf.dim() == 2 else None)
-    if mode[0] != "const":
-        gain = _check_gain(sigma_gain)
-        return _with_sigma(yuv420_to_input(buf, H, W, pix_fmt, matrix, full_range, chroma, 0.0, row_pitch, pad_to), mode, (int(H), int(W)), gain)
-    desc, nbytes = _yuv_desc(H, W, pix_fmt, matrix, full_range, chroma, row_pitch, picture=pad_to is not None)
-    lib = require_hip()
-    desc.frame_stride = _surface_buffer(buf, None, nbytes, pix_fmt == "p010", "yuv420_to_input", "P010", "p010")
-    T = buf.shape[0]
-    extra = 0 if sigma is None else 1
-    if pad_to is not None:
-        Hp, Wp = _pair(pad_to, "pad_to")
-        y = torch.empty((T, 3 + extra, max(Hp, 0), max(Wp, 0)), dtype=torch.float32, device=buf.device)
-        with torch.cuda.device(buf.device):
-            _lib.check(lib.bsvd_yuv420_to_planar_pad(buf.data_ptr(), y.data_ptr(), T, H, W, Hp, Wp, ctypes.byref(desc), extra,
-                                                     float(sigma or 0.0), _stream()), "bsvd_yuv420_to_planar_pad")
-        return y
-    y = torch.empty((T, 3 + extra, H, W), dtype=torch.float32, device=buf.device)
-    with torch.cuda.device(buf.device):
-        _lib.check(lib.bsvd_yuv420_to_planar(buf.data_ptr(), y.data_ptr(), T, H, W, ctypes.byref(desc), extra, float(sigma or 0.0),
-                                             _stream()), "bsvd_yuv420_to_planar")
-    return y
+    def describe():
+        desc, nbytes = _yuv_desc(H, W, pix_fmt, matrix, full_range, chroma, row_pitch, picture=pad_to is not None)
+        desc.frame_stride = _surface_buffer(buf, None, nbytes, pix_fmt == "p010", "yuv420_to_input", "P010", "p010")
+        return (ctypes.byref(desc),), None
+    return _decode(("bsvd_yuv420_to_planar", "bsvd_yuv420_to_planar_pad"), buf, _frames_of(buf), 3, H, W, pad_to, sigma, sigma_gain, describe)
 
 
 def output_to_yuv420(y, pix_fmt="nv12", matrix="bt709", full_range=False, chroma="linear", row_pitch=None, out=None, crop_to=None,
@@ -982,47 +962,30 @@ def output_to_yuv420(y, pix_fmt="nv12", matrix="bt709", full_range=False, chroma
     scaled Y, Cb and Cr right before the clamp and the rounding (8 x 8 Bayer, static; or a hash of ``dither_seed``, the frame's stream index
     ``frame0 + t``, the component and the position) -- a whole code is never moved (include/bsvd_hip.h, BsvdDither)."""
     dith = _dither_struct(dither, dither_seed, frame0)
-    if y.dtype != torch.float32 or not y.is_cuda or y.dim() != 4 or y.shape[1] != 3:
-        raise ValueError("expected a float32 device tensor [T,3,H,W]")
-    T, _, H, W = y.shape
-    Hp, Wp = H, W
-    if crop_to is not None:
-        H, W = _pair(crop_to, "crop_to")
-    desc, nbytes = _yuv_desc(H, W, pix_fmt, matrix, full_range, chroma, row_pitch, picture=crop_to is not None)
-    lib = require_hip()
-    y = y.contiguous()
-    if out is None:
-        out = (torch.zeros if row_pitch else torch.empty)((T, nbytes), dtype=torch.uint8, device=y.device)
-    elif out.device != y.device:
-        raise ValueError("output_to_yuv420: out is on %s, y on %s" % (out.device, y.device))
-    desc.frame_stride = _surface_buffer(out, T, nbytes, pix_fmt == "p010", "output_to_yuv420(out=)", "P010", "p010")
-    with torch.cuda.device(y.device):
-        if dith is not None:
-            _lib.check(lib.bsvd_planar_to_yuv420_crop_d(y.data_ptr(), out.data_ptr(), T, Hp, Wp, H, W, ctypes.byref(desc), ctypes.byref(dith),
-                                                        _stream()), "bsvd_planar_to_yuv420_crop_d")
-        elif crop_to is not None:
-            _lib.check(lib.bsvd_planar_to_yuv420_crop(y.data_ptr(), out.data_ptr(), T, Hp, Wp, H, W, ctypes.byref(desc), _stream()),
-                       "bsvd_planar_to_yuv420_crop")
-        else:
-            _lib.check(lib.bsvd_planar_to_yuv420(y.data_ptr(), out.data_ptr(), T, H, W, ctypes.byref(desc), _stream()),
-                       "bsvd_planar_to_yuv420")
-    return out
+    _tensor(y, torch.float32, (None, 3, None, None), "cuda", "expected a float32 device tensor [T,3,H,W]", contiguous=False)
+
+    def describe(T, H, W):
+        desc, nbytes = _yuv_desc(H, W, pix_fmt, matrix, full_range, chroma, row_pitch, picture=crop_to is not None)
+        return desc, nbytes, pix_fmt == "p010", (ctypes.byref(desc),)
+    return _encode("output_to_yuv420", ("bsvd_planar_to_yuv420", "bsvd_planar_to_yuv420_crop", "bsvd_planar_to_yuv420_crop_d"), y, crop_to,
+                   describe, dith, out, bool(row_pitch), ("P010", "p010"))
 
 
 # ---------------------------------------------------------------------------------------------------
 # planar, 4:2:2 and 4:4:4 surfaces (include/bsvd_hip.h, BsvdYuvSurface): the names of _lib.YUV_FORMATS, ffmpeg's
 
-def _triple(v, what, planes):
-    """pitches / offsets: None, or up to ``planes`` non-negative ints (None or 0 = tight / directly behind the plane before)"""
+def _per_plane(v, what, planes, slots=3):
+    """pitches / offsets: None, or up to ``planes`` non-negative ints (None or 0 = tight / directly behind the plane before) -> the
+    ``slots`` values of the descriptor's array"""
     if v is None:
-        return (0, 0, 0)
+        return (0,) * slots
     try:
         v = [int(x or 0) for x in v]
     except TypeError:
         raise ValueError("%s: expected a sequence of up to %d ints, got %r" % (what, planes, v)) from None
     if len(v) > planes or any(x < 0 for x in v):
         raise ValueError("%s %r: the layout has %d plane(s); values must not be negative" % (what, v, planes))
-    return tuple(v) + (0,) * (3 - len(v))
+    return tuple(v) + (0,) * (slots - len(v))
 
 
 def yuv_planes(pix_fmt):
@@ -1042,8 +1005,8 @@ def _yuv_surface(H, W, pix_fmt, matrix, full_range, chroma, pitches, offsets, pi
     sub, layout, bits, high = _lib.YUV_FORMATS[pix_fmt]
     surf = _lib.BsvdYuvSurface(subsampling=sub, layout=layout, bits=bits, high_bits=high, matrix=_lib.MATRIX[matrix],
                                full_range=1 if full_range else 0, chroma=_lib.CHROMA[chroma])
-    surf.pitch[:] = _triple(pitches, "pitches", planes)
-    surf.offset[:] = _triple(offsets, "offsets", planes)
+    surf.pitch[:] = _per_plane(pitches, "pitches", planes)
+    surf.offset[:] = _per_plane(offsets, "offsets", planes)
     H, W = int(H), int(W)
     if not picture and (H <= 0 or W <= 0 or H % 4 or W % 4):
         raise ValueError("%s frame %d x %d: H and W must be positive multiples of 4 (or use pad_to / crop_to)" % (pix_fmt, H, W))
@@ -1070,28 +1033,11 @@ def yuv_to_input(buf, H, W, pix_fmt="yuv420p", matrix="bt709", full_range=False,
     (Wp a multiple of 4; Hp even for 4:2:0): any picture size the format can carry, reflect-padded on the right and bottom after
     conversion.  ``sigma='auto'`` / a sequence / a device tensor [T] and ``sigma_gain``: as for ``yuv420_to_input`` (with subsampled
     chroma the estimate reads low)."""
-    mode = _sigma_mode(sigma, buf.shape[0] if isinstance(buf, torch.Tensor) and buf.dim() == 2 else None)
-    if mode[0] != "const":
-        gain = _check_gain(sigma_gain)
-        return _with_sigma(yuv_to_input(buf, H, W, pix_fmt, matrix, full_range, chroma, 0.0, pitches, pad_to, offsets), mode,
-                           (int(H), int(W)), gain)
-    surf, nbytes = _yuv_surface(H, W, pix_fmt, matrix, full_range, chroma, pitches, offsets, picture=pad_to is not None)
-    lib = require_hip()
-    surf.frame_stride = _surface_buffer(buf, None, nbytes, surf.bits > 8, "yuv_to_input")
-    T = buf.shape[0]
-    extra = 0 if sigma is None else 1
-    if pad_to is not None:
-        Hp, Wp = _pair(pad_to, "pad_to")
-        y = torch.empty((T, 3 + extra, max(Hp, 0), max(Wp, 0)), dtype=torch.float32, device=buf.device)
-        with torch.cuda.device(buf.device):
-            _lib.check(lib.bsvd_yuv_to_planar_pad(buf.data_ptr(), y.data_ptr(), T, H, W, Hp, Wp, ctypes.byref(surf), extra,
-                                                  float(sigma or 0.0), _stream()), "bsvd_yuv_to_planar_pad")
-        return y
-    y = torch.empty((T, 3 + extra, H, W), dtype=torch.float32, device=buf.device)
-    with torch.cuda.device(buf.device):
-        _lib.check(lib.bsvd_yuv_to_planar(buf.data_ptr(), y.data_ptr(), T, H, W, ctypes.byref(surf), extra, float(sigma or 0.0),
-                                          _stream()), "bsvd_yuv_to_planar")
-    return y
+    def describe():
+        surf, nbytes = _yuv_surface(H, W, pix_fmt, matrix, full_range, chroma, pitches, offsets, picture=pad_to is not None)
+        surf.frame_stride = _surface_buffer(buf, None, nbytes, surf.bits > 8, "yuv_to_input")
+        return (ctypes.byref(surf),), None
+    return _decode(("bsvd_yuv_to_planar", "bsvd_yuv_to_planar_pad"), buf, _frames_of(buf), 3, H, W, pad_to, sigma, sigma_gain, describe)
 
 
 def output_to_yuv(y, pix_fmt="yuv420p", matrix="bt709", full_range=False, chroma="linear", pitches=None, out=None, crop_to=None, offsets=None,
@@ -1102,48 +1048,17 @@ def output_to_yuv(y, pix_fmt="yuv420p", matrix="bt709", full_range=False, chroma
     the result's padding is zero.  ``crop_to=(H, W)``: the surfaces of ``y[..., :H, :W]``.  ``dither`` / ``dither_seed`` / ``frame0``: as for
     ``output_to_yuv420``; subsampled chroma is dithered on the chroma grid."""
     dith = _dither_struct(dither, dither_seed, frame0)
-    if y.dtype != torch.float32 or not y.is_cuda or y.dim() != 4 or y.shape[1] != 3:
-        raise ValueError("expected a float32 device tensor [T,3,H,W]")
-    T, _, H, W = y.shape
-    Hp, Wp = H, W
-    if crop_to is not None:
-        H, W = _pair(crop_to, "crop_to")
-    surf, nbytes = _yuv_surface(H, W, pix_fmt, matrix, full_range, chroma, pitches, offsets, picture=crop_to is not None)
-    lib = require_hip()
-    y = y.contiguous()
-    if out is None:
-        out = (torch.zeros if pitches or offsets else torch.empty)((T, nbytes), dtype=torch.uint8, device=y.device)
-    elif out.device != y.device:
-        raise ValueError("output_to_yuv: out is on %s, y on %s" % (out.device, y.device))
-    surf.frame_stride = _surface_buffer(out, T, nbytes, surf.bits > 8, "output_to_yuv(out=)")
-    with torch.cuda.device(y.device):
-        if dith is not None:
-            _lib.check(lib.bsvd_planar_to_yuv_crop_d(y.data_ptr(), out.data_ptr(), T, Hp, Wp, H, W, ctypes.byref(surf), ctypes.byref(dith),
-                                                     _stream()), "bsvd_planar_to_yuv_crop_d")
-        elif crop_to is not None:
-            _lib.check(lib.bsvd_planar_to_yuv_crop(y.data_ptr(), out.data_ptr(), T, Hp, Wp, H, W, ctypes.byref(surf), _stream()),
-                       "bsvd_planar_to_yuv_crop")
-        else:
-            _lib.check(lib.bsvd_planar_to_yuv(y.data_ptr(), out.data_ptr(), T, H, W, ctypes.byref(surf), _stream()),
-                       "bsvd_planar_to_yuv")
-    return out
+    _tensor(y, torch.float32, (None, 3, None, None), "cuda", "expected a float32 device tensor [T,3,H,W]", contiguous=False)
+
+    def describe(T, H, W):
+        surf, nbytes = _yuv_surface(H, W, pix_fmt, matrix, full_range, chroma, pitches, offsets, picture=crop_to is not None)
+        return surf, nbytes, surf.bits > 8, (ctypes.byref(surf),)
+    return _encode("output_to_yuv", ("bsvd_planar_to_yuv", "bsvd_planar_to_yuv_crop", "bsvd_planar_to_yuv_crop_d"), y, crop_to, describe, dith, out,
+                   bool(pitches or offsets))
 
 
 # ---------------------------------------------------------------------------------------------------
 # RGB surfaces (include/bsvd_hip.h, BsvdRgbSurface): the names of _lib.RGB_FORMATS, ffmpeg's
-
-def _quad(v, what, planes):
-    """pitches / offsets: None, or up to ``planes`` non-negative ints (None or 0 = tight / directly behind the plane before)"""
-    if v is None:
-        return (0, 0, 0, 0)
-    try:
-        v = [int(x or 0) for x in v]
-    except TypeError:
-        raise ValueError("%s: expected a sequence of up to %d ints, got %r" % (what, planes, v)) from None
-    if len(v) > planes or any(x < 0 for x in v):
-        raise ValueError("%s %r: the layout has %d plane(s); values must not be negative" % (what, v, planes))
-    return tuple(v) + (0,) * (4 - len(v))
-
 
 def rgb_planes(pix_fmt):
     """planes of an RGB surface format: 1 (packed) or 3 / 4 (gbrp* / gbrap*)"""
@@ -1171,8 +1086,8 @@ def _rgb_surface(H, W, pix_fmt, full_range, pitches, offsets, picture):
     layout, components, bits, pos, fourth = _lib.RGB_FORMATS[pix_fmt]
     surf = _lib.BsvdRgbSurface(layout=layout, components=components, bits=bits, fourth=fourth, full_range=1 if full_range else 0)
     surf.pos[:] = pos
-    surf.pitch[:] = _quad(pitches, "pitches", planes)
-    surf.offset[:] = _quad(offsets, "offsets", planes)
+    surf.pitch[:] = _per_plane(pitches, "pitches", planes, 4)
+    surf.offset[:] = _per_plane(offsets, "offsets", planes, 4)
     H, W = int(H), int(W)
     if not picture and (H <= 0 or W <= 0 or H % 4 or W % 4):
         raise ValueError("%s frame %d x %d: H and W must be positive multiples of 4 (or use pad_to / crop_to)" % (pix_fmt, H, W))
@@ -1192,10 +1107,8 @@ def rgb_frame_bytes(H, W, pix_fmt, pitches=None, offsets=None):
 
 
 def _alpha_plane(alpha, T, H, W, pix_fmt, device, what):
-    if (not isinstance(alpha, torch.Tensor) or alpha.dtype != rgb_sample_dtype(pix_fmt) or tuple(alpha.shape) != (T, H, W)
-            or alpha.device != device or not alpha.is_contiguous()):
-        raise ValueError("%s: expected a contiguous %s tensor [%d,%d,%d] on %s" % (what, rgb_sample_dtype(pix_fmt), T, H, W, device))
-    return alpha
+    dtype = rgb_sample_dtype(pix_fmt)
+    return _tensor(alpha, dtype, (T, H, W), device, "%s: expected a contiguous %s tensor [%d,%d,%d] on %s" % (what, dtype, T, H, W, device))
 
 
 def rgb_to_input(buf, H, W, pix_fmt, full_range=True, sigma=None, pitches=None, offsets=None, pad_to=None, sigma_gain=1.0, return_alpha=False):
@@ -1209,29 +1122,17 @@ def rgb_to_input(buf, H, W, pix_fmt, full_range=True, sigma=None, pitches=None, 
     tensor [T,H,W] (uint8, uint16 above 8 bits), picture-sized also with ``pad_to``; a tensor of that shape: written into and returned."""
     if return_alpha is not False and not rgb_has_alpha(pix_fmt):
         raise ValueError("rgb_to_input(return_alpha=): pix_fmt %r carries no alpha" % (pix_fmt,))
-    mode = _sigma_mode(sigma, buf.shape[0] if isinstance(buf, torch.Tensor) and buf.dim() == 2 else None)
-    if mode[0] != "const":
-        gain = _check_gain(sigma_gain)
-        r = rgb_to_input(buf, H, W, pix_fmt, full_range, 0.0, pitches, offsets, pad_to, 1.0, return_alpha)
-        x = _with_sigma(r[0] if return_alpha is not False else r, mode, (int(H), int(W)), gain)
-        return (x, r[1]) if return_alpha is not False else x
-    surf, nbytes = _rgb_surface(H, W, pix_fmt, full_range, pitches, offsets, picture=pad_to is not None)
-    H, W = int(H), int(W)
-    Hp, Wp = (H, W) if pad_to is None else _pair(pad_to, "pad_to")
-    lib = require_hip()
-    surf.frame_stride = _surface_buffer(buf, None, nbytes, surf.bits > 8, "rgb_to_input", "16-bit", "16-bit")
-    T = buf.shape[0]
-    alpha = None
-    if return_alpha is True:
-        alpha = torch.empty((T, H, W), dtype=rgb_sample_dtype(pix_fmt), device=buf.device)
-    elif return_alpha is not False:
-        alpha = _alpha_plane(return_alpha, T, H, W, pix_fmt, buf.device, "rgb_to_input(return_alpha=)")
-    extra = 0 if sigma is None else 1
-    y = torch.empty((T, 3 + extra, max(Hp, 0), max(Wp, 0)), dtype=torch.float32, device=buf.device)
-    with torch.cuda.device(buf.device):
-        _lib.check(lib.bsvd_rgb_to_planar(buf.data_ptr(), y.data_ptr(), T, H, W, Hp, Wp, ctypes.byref(surf),
-                                          None if alpha is None else alpha.data_ptr(), extra, float(sigma or 0.0), _stream()), "bsvd_rgb_to_planar")
-    return y if alpha is None else (y, alpha)
+
+    def describe():
+        surf, nbytes = _rgb_surface(H, W, pix_fmt, full_range, pitches, offsets, picture=pad_to is not None)
+        surf.frame_stride = _surface_buffer(buf, None, nbytes, surf.bits > 8, "rgb_to_input", "16-bit", "16-bit")
+        alpha = None
+        if return_alpha is True:
+            alpha = torch.empty((buf.shape[0], int(H), int(W)), dtype=rgb_sample_dtype(pix_fmt), device=buf.device)
+        elif return_alpha is not False:
+            alpha = _alpha_plane(return_alpha, buf.shape[0], int(H), int(W), pix_fmt, buf.device, "rgb_to_input(return_alpha=)")
+        return (ctypes.byref(surf), None if alpha is None else alpha.data_ptr()), alpha
+    return _decode((None, "bsvd_rgb_to_planar"), buf, _frames_of(buf), 3, H, W, pad_to, sigma, sigma_gain, describe)
 
 
 def output_to_rgb(y, pix_fmt, full_range=True, pitches=None, offsets=None, out=None, crop_to=None, alpha=None, dither=None, dither_seed=0,
@@ -1246,25 +1147,12 @@ def output_to_rgb(y, pix_fmt, full_range=True, pitches=None, offsets=None, out=N
     if alpha is not None and not rgb_has_alpha(pix_fmt):
         raise ValueError("output_to_rgb(alpha=): pix_fmt %r carries no alpha" % (pix_fmt,))
     rgb_planes(pix_fmt)
-    if not isinstance(y, torch.Tensor) or y.dtype != torch.float32 or not y.is_cuda or y.dim() != 4 or y.shape[1] != 3:
-        raise ValueError("expected a float32 device tensor [T,3,H,W]")
-    T, _, Hp, Wp = y.shape
-    H, W = (Hp, Wp) if crop_to is None else _pair(crop_to, "crop_to")
-    surf, nbytes = _rgb_surface(H, W, pix_fmt, full_range, pitches, offsets, picture=crop_to is not None)
-    lib = require_hip()
-    y = y.contiguous()
-    if alpha is not None:
-        _alpha_plane(alpha, T, H, W, pix_fmt, y.device, "output_to_rgb(alpha=)")
-    if out is None:
-        out = (torch.zeros if pitches or offsets else torch.empty)((T, nbytes), dtype=torch.uint8, device=y.device)
-    elif out.device != y.device:
-        raise ValueError("output_to_rgb: out is on %s, y on %s" % (out.device, y.device))
-    surf.frame_stride = _surface_buffer(out, T, nbytes, surf.bits > 8, "output_to_rgb(out=)", "16-bit", "16-bit")
-    with torch.cuda.device(y.device):
-        if dith is not None:
-            _lib.check(lib.bsvd_planar_to_rgb_d(y.data_ptr(), out.data_ptr(), T, Hp, Wp, H, W, ctypes.byref(surf),
-                                                None if alpha is None else alpha.data_ptr(), ctypes.byref(dith), _stream()), "bsvd_planar_to_rgb_d")
-        else:
-            _lib.check(lib.bsvd_planar_to_rgb(y.data_ptr(), out.data_ptr(), T, Hp, Wp, H, W, ctypes.byref(surf),
-                                              None if alpha is None else alpha.data_ptr(), _stream()), "bsvd_planar_to_rgb")
-    return out
+    _tensor(y, torch.float32, (None, 3, None, None), "cuda", "expected a float32 device tensor [T,3,H,W]", contiguous=False)
+
+    def describe(T, H, W):
+        surf, nbytes = _rgb_surface(H, W, pix_fmt, full_range, pitches, offsets, picture=crop_to is not None)
+        if alpha is not None:
+            _alpha_plane(alpha, T, H, W, pix_fmt, y.device, "output_to_rgb(alpha=)")
+        return surf, nbytes, surf.bits > 8, (ctypes.byref(surf), None if alpha is None else alpha.data_ptr())
+    return _encode("output_to_rgb", (None, "bsvd_planar_to_rgb", "bsvd_planar_to_rgb_d"), y, crop_to, describe, dith, out, bool(pitches or offsets),
+                   ("16-bit", "16-bit"))

@@ -12,6 +12,10 @@ flows through three HIP streams so PCIe never idles the matrix cores:
 ``depth`` slots of pinned staging memory form a ring; slot k is reused once its download has completed.  Results are
 yielded in submission order.
 
+The options of ``ClipPipeline`` and ``LiveStream`` are described here, once; the class docstrings say what differs per class: the
+arrays taken and returned, latency, rings, and when the host waits.  Both check them in one order before anything touches a device,
+and with the defaults both launch nothing new and give the bytes they gave.
+
 ``pix_fmt`` selects what crosses PCIe: 'rgb24' (the default, packed RGB uint8 [H,W,3]) or the YUV 4:2:0 surfaces video sources and
 sinks speak, 'nv12' (uint8) and 'p010' (uint16, 10-bit code in the high bits), as arrays [H*3/2, pitch] -- the Y plane's H rows,
 then the H/2 rows of interleaved CbCr; 1.5 (NV12) or 3 (P010) bytes per pixel each way instead of 3, converted by
@@ -37,25 +41,41 @@ on the compute stream from the converted frame and written into its noise-map pl
 it).  The host sees it only afterwards, as ``LiveStream.last_sigma``: 4 bytes that come down with the frame.  For sources whose noise depends
 on the signal level: 'nlf' -- every frame's own noise-level function, sigma at sixteen levels of local intensity, and a per-pixel noise map
 written from it (``frame_io.estimate_noise_curve`` / ``fill_noise_map``; ``LiveStream.last_noise_curve``: 64 bytes that come down with the
-frame) -- or a ``frame_io.NoiseCurve`` the caller knows.
+frame) -- or a ``frame_io.NoiseCurve`` the caller knows: the map is written from that curve and nothing is reported.  All but the float need a
+non-blind model.  Nothing is known about the estimates on real footage (``frame_io.estimate_sigma`` / ``estimate_noise_curve``: what is
+known), and YUV sources with subsampled chroma read low: ``sigma_gain`` scales every estimate.
 
 ``vst`` (with ``sigma=None``) is the remedy for signal-dependent noise that stays inside what the reference's checkpoints were trained on:
 a variance-stabilising transform.  The colour planes are remapped by the curve's g(I) ~ integral dI / sigma(I) before the network
 (``frame_io.build_vst`` / ``vst_forward``), the noise plane is the one sigma' the noise then has everywhere, and the result is mapped back
 (``vst_inverse``) before the strength blend and the encoder.  A ``frame_io.NoiseCurve``: one table set for the stream; 'scene': the frame
-that starts a scene gives the curve (``frame_io.estimate_noise_curve``) and every later frame of the scene uses its tables.  No trained
-checkpoint has been run through it: its effect on denoising quality is not known.
+that starts a scene gives the curve (``frame_io.estimate_noise_curve``, times ``sigma_gain``) and every later frame of the scene uses its
+tables: a curve that drifts within a scene (auto-exposure) is not followed until the next cut.  A curve that is flat after the clamp to
+[``vst_floor``, 1] is the identity: nothing is launched and the plane is written as sigma=<that value> writes it.  ``strength`` blends in the
+picture's own domain, with the untransformed source (strength=0 still returns the source).  A blind model gets the transform and no plane.
+No trained checkpoint has been run through it: its effect on denoising quality is not known, and nothing has been measured on real
+footage (``frame_io.build_vst``: what is known).
+
+``strength`` (a number or (luma, chroma), each in [0, 1]; default 1) is how much of the denoising to keep: the network's result is blended
+with its own input on the device before it is encoded (``frame_io.blend_output``; luma weights: the stream's matrix for YUV formats, BT.709
+for RGB ones, or ``luma_matrix``).  ``dither`` None | 'ordered' | 'random' with ``dither_seed``: dither at the encoder's quantiser
+(``frame_io.output_to_*``); the random pattern depends on the frame's index in the stream.
 
 ``grain`` puts film grain back after denoising, as a MODEL instead of the removed signal that ``strength`` mixes back: a
 ``frame_io.GrainModel`` (its strength against brightness, its spatial correlation) the caller made, or 'scene' -- the first frame of every
 scene to emerge has its source and result measured on the device (``frame_io.estimate_grain``: one host synchronisation per scene), and the
 model fitted from it is synthesised onto that frame and every later frame of the scene (``frame_io.apply_grain``), after the inverse
-transform and the strength blend and before the encoder and its dither.  Nothing has been measured on real footage.
+transform and the strength blend and before the encoder and its dither; ``grain_amount`` (default 1) scales it, and the block offsets are
+hashed from (``grain_seed``, the frame's index in the stream, the block).  With a strength below 1 the measured result is the blended one:
+the model describes what is still missing.  ``last_grain_model``: the latest model.  No temporal pooling beyond the scene's first frame, no
+overlap blending of grain blocks, nothing measured on real footage (``frame_io.estimate_grain``: what is known; the fit costs about the
+figures of profiles/film_grain.txt).
 
 ``cuts`` is what the pipelines know about scene cuts: None (nothing: the footage is one scene, as before) or 'auto' -- every frame is scored
 against the one before it on the device (``frame_io.scene_scores`` / ``scene_cuts``; ``cut_threshold``) and a frame that scores as a scene
 start is fed with ``cut=True``: no temporal-fusion conv mixes the two scenes, nothing is flushed, latency is unchanged.  A caller who knows
-the cuts says so per frame instead (``LiveStream.feed(frame, cut=True)``).  Nothing is known about the score on real footage.
+the cuts says so per frame instead (``LiveStream.feed(frame, cut=True)``).  Nothing is known about the rule on real footage, the default
+threshold has met none, and a cut one or two frames after another cut scores low (``frame_io.scene_cuts``: the rule and its blind spot).
 """
 import collections
 
@@ -97,12 +117,38 @@ def _padded_size(h, w, what):
     return hp, wp
 
 
-class _Rgb24:
-    """packed RGB uint8 [H,W,3]: staged as it comes, converted by bsvd_u8_to_planar / bsvd_planar_to_u8"""
-    dtype = np.dtype(np.uint8)
+def _frame_shape(frame_shape):
+    """``frame_shape`` -> (H, W) as ints; ValueError otherwise"""
+    try:
+        return int(frame_shape[0]), int(frame_shape[1])
+    except (TypeError, ValueError, IndexError):
+        raise ValueError("frame_shape: expected (H, W), got %r" % (frame_shape,)) from None
+
+
+class _Format:
+    """What the pixel-format adapters share.  ``pad``; ``geometry(a, clip)`` -> the ``_Geometry`` of a submitted array (each format's own);
+    and one signature for every format, with or without alpha:
+        to_input(dev_in, geom, sigma, sigma_gain, alpha=None) -> (x, alpha): the network input, and for a format with alpha the frames'
+            alpha codes, a device tensor [T,H,W] -- written into ``alpha`` where one is given (a ring's plane), else a new one; without
+            alpha in the format: None;
+        to_output(y, geom, alpha=None, **dither) -> the surfaces, with those codes.
+    ``pad_to`` / ``crop_to`` are given here, to the formats' ``_decode`` / ``_encode``: with pad='reflect' always, also for a picture that
+    is a multiple of 4 already."""
+    has_alpha = False
 
     def __init__(self, pad=None):
         self.pad = _check_pad(pad)
+
+    def to_input(self, dev_in, geom, sigma, sigma_gain=1.0, alpha=None):
+        return self._decode(dev_in, geom, alpha, sigma=sigma, sigma_gain=sigma_gain, pad_to=(geom.net_h, geom.net_w) if self.pad else None)
+
+    def to_output(self, y, geom, alpha=None, **dither):
+        return self._encode(y, geom, alpha, crop_to=(geom.h, geom.w) if self.pad else None, **dither)
+
+
+class _Rgb24(_Format):
+    """packed RGB uint8 [H,W,3]: staged as it comes, converted by bsvd_u8_to_planar / bsvd_planar_to_u8"""
+    dtype = np.dtype(np.uint8)
 
     def geometry(self, a, clip):
         if a.dtype != np.uint8 or a.ndim != (4 if clip else 3) or a.shape[-1] != 3:
@@ -116,15 +162,14 @@ class _Rgb24:
             raise ValueError("H and W must be multiples of 4 (pad first: denoise.pad_to_multiple_of_4; or pad='reflect')")
         return _Geometry(h, w, tuple(a.shape), None, h, w)
 
-    def to_input(self, dev_in, geom, sigma, sigma_gain=1.0):
-        return frames_to_input(dev_in, sigma, pad_to=(geom.net_h, geom.net_w) if self.pad else None, sigma_gain=sigma_gain)
+    def _decode(self, dev_in, geom, alpha, sigma, **kw):
+        return frames_to_input(dev_in, sigma, **kw), None
 
-    def to_output(self, y, geom, **dither):
+    def _encode(self, y, geom, alpha, crop_to, **dither):
         if dither.get("dither") is None:
-            return output_to_frames(y, crop_to=(geom.h, geom.w) if self.pad else None)
+            return output_to_frames(y, crop_to=crop_to)
         # dither: the RGB surface kernel, which gives the uint8 kernel's bits with dither off (the uint8 kernels have no dithered form)
-        out = output_to_rgb(y, "rgb24", crop_to=(geom.h, geom.w) if self.pad else None, **dither)
-        return out.view(y.shape[0], geom.h, geom.w, 3)
+        return output_to_rgb(y, "rgb24", crop_to=crop_to, **dither).view(y.shape[0], geom.h, geom.w, 3)
 
 
 def _as_colour(colour):
@@ -138,12 +183,12 @@ def _as_colour(colour):
     return Colour(*colour)
 
 
-class _Yuv420:
+class _Yuv420(_Format):
     """NV12 (uint8) / P010 (uint16) arrays [H*3/2, pitch]: staged as the bytes of the surface, converted by bsvd_yuv420_to_planar /
     bsvd_planar_to_yuv420"""
 
     def __init__(self, pix_fmt, colour, pad=None):
-        self.pad = _check_pad(pad)
+        super().__init__(pad)
         colour = _as_colour(colour)
         self.pix_fmt, self.colour = pix_fmt, colour
         self.dtype = np.dtype(np.uint8 if pix_fmt == "nv12" else np.uint16)
@@ -171,31 +216,27 @@ class _Yuv420:
         nbytes = (yuv420_picture_bytes if self.pad else yuv420_frame_bytes)(h, w, self.pix_fmt, row_bytes)
         return _Geometry(h, w, (a.shape[0], nbytes) if clip else (nbytes,), None if w == pitch else row_bytes, *net)
 
-    def to_input(self, dev_in, geom, sigma, sigma_gain=1.0):
-        return yuv420_to_input(dev_in, geom.h, geom.w, sigma=sigma, row_pitch=geom.row_pitch,
-                               pad_to=(geom.net_h, geom.net_w) if self.pad else None, sigma_gain=sigma_gain, **self.kw)
+    def _decode(self, dev_in, geom, alpha, **kw):
+        return yuv420_to_input(dev_in, geom.h, geom.w, row_pitch=geom.row_pitch, **self.kw, **kw), None
 
-    def to_output(self, y, geom, **dither):
-        return output_to_yuv420(y, row_pitch=geom.row_pitch, crop_to=(geom.h, geom.w) if self.pad else None, **self.kw, **dither)
+    def _encode(self, y, geom, alpha, **kw):
+        return output_to_yuv420(y, row_pitch=geom.row_pitch, **self.kw, **kw)
 
 
-class _YuvSurface:
+class _YuvSurface(_Format):
     """the planar, 4:2:2 and 4:4:4 formats of _lib.YUV_FORMATS: 1-D arrays of the tight frame's samples (uint8; uint16 for the 10-bit
     formats) -- the bytes ``ffmpeg -f rawvideo`` emits --, converted by bsvd_yuv_to_planar / bsvd_planar_to_yuv.  A 1-D array does not
     say its picture size: frame_shape = (H, W) does, at construction."""
 
     def __init__(self, pix_fmt, colour, pad=None, frame_shape=None):
-        self.pad = _check_pad(pad)
+        super().__init__(pad)
         colour = _as_colour(colour)
         if colour.row_pitch is not None or colour.width is not None:
             raise ValueError("pix_fmt %r takes tight 1-D frames: colour.row_pitch / colour.width are for 'nv12' / 'p010' "
                              "(pitched surfaces: frame_io.yuv_to_input(pitches=))" % (pix_fmt,))
         if frame_shape is None:
             raise ValueError("pix_fmt %r frames are 1-D arrays of samples: give frame_shape=(H, W)" % (pix_fmt,))
-        try:
-            self.h, self.w = int(frame_shape[0]), int(frame_shape[1])
-        except (TypeError, ValueError, IndexError):
-            raise ValueError("frame_shape: expected (H, W), got %r" % (frame_shape,)) from None
+        self.h, self.w = _frame_shape(frame_shape)
         self.pix_fmt, self.colour = pix_fmt, colour
         self.dtype = np.dtype(np.uint16 if _lib.YUV_FORMATS[pix_fmt][2] > 8 else np.uint8)
         self.kw = dict(pix_fmt=pix_fmt, matrix=colour.matrix, full_range=bool(colour.full_range), chroma=colour.chroma)
@@ -209,22 +250,21 @@ class _YuvSurface:
                              % (self.pix_fmt, self.dtype.name, "T," if clip else "", self.samples, self.h, self.w, a.dtype, a.shape))
         return _Geometry(self.h, self.w, (a.shape[0], self.nbytes) if clip else (self.nbytes,), None, *self.net)
 
-    def to_input(self, dev_in, geom, sigma, sigma_gain=1.0):
-        return yuv_to_input(dev_in, geom.h, geom.w, sigma=sigma, pad_to=(geom.net_h, geom.net_w) if self.pad else None,
-                            sigma_gain=sigma_gain, **self.kw)
+    def _decode(self, dev_in, geom, alpha, **kw):
+        return yuv_to_input(dev_in, geom.h, geom.w, **self.kw, **kw), None
 
-    def to_output(self, y, geom, **dither):
-        return output_to_yuv(y, crop_to=(geom.h, geom.w) if self.pad else None, **self.kw, **dither)
+    def _encode(self, y, geom, alpha, **kw):
+        return output_to_yuv(y, **self.kw, **kw)
 
 
-class _RgbSurface:
+class _RgbSurface(_Format):
     """the RGB surfaces of _lib.RGB_FORMATS but 'rgb24': self-describing arrays -- packed [H,W,3|4] uint8 / uint16, x2rgb10le / x2bgr10le
     [H,W] uint32, planar [P,H,W] -- or, with frame_shape=(H, W), 1-D arrays of the tight frame's samples (``ffmpeg -f rawvideo``'s bytes);
     staged as the tight surface's bytes, converted by bsvd_rgb_to_planar / bsvd_planar_to_rgb.  A format with alpha hands the frames' alpha
     codes from ``to_input`` to ``to_output`` as a device plane beside the tensor (``alpha=``): the pipelines keep it with its frame."""
 
     def __init__(self, pix_fmt, colour, pad=None, frame_shape=None):
-        self.pad = _check_pad(pad)
+        super().__init__(pad)
         if colour is None:
             colour = {}
         if not isinstance(colour, dict) or set(colour) - {"full_range"}:
@@ -237,10 +277,7 @@ class _RgbSurface:
         self.per_pixel = 1 if self.x2 else self.components            # array elements per pixel
         self.hw = None
         if frame_shape is not None:
-            try:
-                self.hw = (int(frame_shape[0]), int(frame_shape[1]))
-            except (TypeError, ValueError, IndexError):
-                raise ValueError("frame_shape: expected (H, W), got %r" % (frame_shape,)) from None
+            self.hw = _frame_shape(frame_shape)
             self._size(*self.hw)                                      # a size the format cannot carry fails here, not at the first frame
 
     def _size(self, h, w):
@@ -283,84 +320,63 @@ class _RgbSurface:
         net, nbytes = self._size(h, w)
         return _Geometry(h, w, (a.shape[0], nbytes) if clip else (nbytes,), None, *net)
 
-    def to_input(self, dev_in, geom, sigma, sigma_gain=1.0, alpha=None):
-        """alpha (formats with alpha): True -> (x, the frames' alpha plane); a device tensor [T,H,W]: written into"""
-        return rgb_to_input(dev_in, geom.h, geom.w, self.pix_fmt, full_range=self.full_range, sigma=sigma, sigma_gain=sigma_gain,
-                            pad_to=(geom.net_h, geom.net_w) if self.pad else None, return_alpha=False if alpha is None else alpha)
+    def _decode(self, dev_in, geom, alpha, **kw):
+        if not self.has_alpha:
+            return rgb_to_input(dev_in, geom.h, geom.w, self.pix_fmt, full_range=self.full_range, **kw), None
+        return rgb_to_input(dev_in, geom.h, geom.w, self.pix_fmt, full_range=self.full_range, return_alpha=True if alpha is None else alpha, **kw)
 
-    def to_output(self, y, geom, alpha=None, **dither):
-        return output_to_rgb(y, self.pix_fmt, full_range=self.full_range, crop_to=(geom.h, geom.w) if self.pad else None, alpha=alpha, **dither)
+    def _encode(self, y, geom, alpha, **kw):
+        return output_to_rgb(y, self.pix_fmt, full_range=self.full_range, alpha=alpha, **kw)
 
 
-class _AlphaRing:
-    """LiveStream's alpha planes: frame k's alpha codes wait on the device while frame k is inside the network.  ``planes`` picture-sized
-    planes, written in feed order and read in the order the frames come out -- the same order; a plane is written again ``planes`` feeds
-    later, by when the step that read it has been waited for (planes >= latency + depth).  Allocated once with the slots."""
+class _Ring:
+    """What rides on the device beside a frame while the frame is inside LiveStream's network: ``slots`` entries (>= latency + depth),
+    written in feed order and read in the order the frames come out -- the same order, through ``cut=True``, ``cuts='auto'`` and
+    ``flush()``; an entry is written again ``slots`` feeds later, by when the step that read it has been waited for.  Allocated once with
+    the stream's slots.  The subclasses say what an entry is and how the error names the ring."""
+    what = None
+
+    def __init__(self, slots, shape, dtype, device):
+        self.buf = torch.empty((slots,) + shape, dtype=dtype, device=device)
+        self.fed = self.emitted = 0
+
+    def next_in(self):
+        self.fed += 1
+        return self.buf[(self.fed - 1) % self.buf.shape[0]]
+
+    def next_out(self):
+        if self.emitted >= self.fed:
+            raise RuntimeError("%s ring: frame %d comes out before it went in" % (self.what, self.emitted))
+        self.emitted += 1
+        return self.buf[(self.emitted - 1) % self.buf.shape[0]]
+
+    def reset(self):
+        self.fed = self.emitted = 0
+
+
+class _AlphaRing(_Ring):
+    """frame k's alpha codes, a picture-sized plane [1,H,W] of the format's sample type"""
+    what = "alpha"
 
     def __init__(self, planes, h, w, dtype, device):
-        self.buf = torch.empty((planes, 1, h, w), dtype=dtype, device=device)
-        self.fed = self.emitted = 0
-
-    def next_in(self):
-        self.fed += 1
-        return self.buf[(self.fed - 1) % self.buf.shape[0]]
-
-    def next_out(self):
-        if self.emitted >= self.fed:
-            raise RuntimeError("alpha ring: frame %d comes out before it went in" % self.emitted)
-        self.emitted += 1
-        return self.buf[(self.emitted - 1) % self.buf.shape[0]]
-
-    def reset(self):
-        self.fed = self.emitted = 0
+        super().__init__(planes, (1, h, w), dtype, device)
 
 
-class _SourceRing:
-    """LiveStream's source frames, for ``strength`` below 1: frame k's three colour planes at network size wait on the device while frame k
-    is inside the network, as the alpha codes do in ``_AlphaRing`` and by the same bookkeeping -- ``frames`` slots (>= latency + depth),
-    written in feed order by the decode's side, read in the same order when the frames come out.  3 fp32 planes per slot, allocated once
-    with the slots.  A slot is [1,3,Hp,Wp]: what ``frame_io.blend_output`` takes as ``x``."""
+class _SourceRing(_Ring):
+    """for ``strength`` below 1 and grain='scene': frame k's three colour planes at network size, written by the decode's side; an entry
+    is [1,3,Hp,Wp] fp32, what ``frame_io.blend_output`` takes as ``x``"""
+    what = "source"
 
     def __init__(self, frames, h, w, device):
-        self.buf = torch.empty((frames, 1, 3, h, w), dtype=torch.float32, device=device)
-        self.fed = self.emitted = 0
-
-    def next_in(self):
-        self.fed += 1
-        return self.buf[(self.fed - 1) % self.buf.shape[0]]
-
-    def next_out(self):
-        if self.emitted >= self.fed:
-            raise RuntimeError("source ring: frame %d comes out before it went in" % self.emitted)
-        self.emitted += 1
-        return self.buf[(self.emitted - 1) % self.buf.shape[0]]
-
-    def reset(self):
-        self.fed = self.emitted = 0
+        super().__init__(frames, (1, 3, h, w), torch.float32, device)
 
 
-class _TableRing:
-    """LiveStream(vst='scene')'s table sets: the set frame k was transformed with waits on the device until frame k's result emerges and is
-    mapped back with it, as the alpha codes do in ``_AlphaRing`` and by the same bookkeeping -- ``sets`` slots (>= latency + depth) of
-    [1, VST_TABLE_FLOATS], written in feed order, read in the same order when the frames come out, through ``cut=True``, ``cuts='auto'``
-    and ``flush()``.  Allocated once with the slots."""
+class _TableRing(_Ring):
+    """vst='scene': the table set frame k was transformed with, [1, VST_TABLE_FLOATS], mapped back with frame k's result"""
+    what = "table"
 
     def __init__(self, sets, device):
-        self.buf = torch.empty((sets, 1, VST_TABLE_FLOATS), dtype=torch.float32, device=device)
-        self.fed = self.emitted = 0
-
-    def next_in(self):
-        self.fed += 1
-        return self.buf[(self.fed - 1) % self.buf.shape[0]]
-
-    def next_out(self):
-        if self.emitted >= self.fed:
-            raise RuntimeError("table ring: frame %d comes out before it went in" % self.emitted)
-        self.emitted += 1
-        return self.buf[(self.emitted - 1) % self.buf.shape[0]]
-
-    def reset(self):
-        self.fed = self.emitted = 0
+        super().__init__(sets, (1, VST_TABLE_FLOATS), torch.float32, device)
 
 
 class _Vst:
@@ -486,6 +502,17 @@ def _check_sigma(model, sigma, sigma_gain, what):
     return _check_gain(sigma_gain)
 
 
+_Side = collections.namedtuple("_Side", "dev pin")
+# LiveStream's values that come down with a frame, each fp32: (name in ``_Slot.side``, length, the attribute that reports it once ``feed``
+# has waited for the step, when the stream has it).  Written on the compute stream into ``dev``, copied to ``pin`` on the download stream
+# behind the frame, read in ``_pop``: one value as a float, more as a list.
+_SIDE_VALUES = (
+    ("sigma", 1, "last_sigma", lambda live: live.auto_sigma),                                    # sigma='auto': the step's estimate
+    ("curve", _lib.NLF_LEVELS, "last_noise_curve", lambda live: live.nlf_sigma or live.vst.scene),  # sigma='nlf' / vst='scene': the curve
+    ("vsig", 1, "last_vst_sigma", lambda live: live.vst.active),                                 # vst=...: the frame's sigma'
+)
+
+
 class _Slot:
     def __init__(self):
         self.pin_in = self.pin_out = None
@@ -495,9 +522,7 @@ class _Slot:
         self.computed = torch.cuda.Event()
         self.downloaded = torch.cuda.Event()
         self.ticket = None          # the in-flight clip occupying this slot
-        self.dev_sigma = self.pin_sigma = None      # LiveStream(sigma='auto'): the step's estimate, 4 bytes beside the frame
-        self.dev_curve = self.pin_curve = None      # LiveStream(sigma='nlf'): the step's noise-level curve, 64 bytes beside the frame
-        self.dev_vsig = self.pin_vsig = None        # LiveStream(vst=...): the frame's sigma', 4 bytes beside the frame
+        self.side = {}                              # LiveStream: name -> _Side, the values of _SIDE_VALUES that come down beside the frame
         self.dev_alpha = None                       # ClipPipeline, formats with alpha: the clip's alpha plane [T,H,W], held like dev_out
 
 
@@ -516,62 +541,71 @@ class _Ticket:
         return self.result
 
 
-class ClipPipeline:
-    """model: a bsvd_amd.BSVD on a HIP device.  sigma: noise std in [0,1] units for the constant noise map (None for a
-    blind model).  depth >= 2 overlaps the transfers of one clip with the forward of another.  pix_fmt 'rgb24' | 'nv12' | 'p010' and
-    colour (a ``Colour`` or a dict of its fields; YUV only): what ``submit`` takes and the results are, see the module docstring.
-    pad None | 'reflect': 'reflect' takes pictures of any size (even H and W for YUV), padded and cropped on the device.
-    pix_fmt 'yuv420p' | 'yuv420p10le' | 'uyvy422' | 'yuyv422' | 'nv16' | 'p210le' | 'yuv422p' | 'yuv422p10le' | 'yuv444p' | 'yuv444p10le'
-    with frame_shape=(H, W): clips are [T, n] arrays of the tight frames' samples (uint8, uint16 for 10 bit), as ffmpeg's rawvideo.
-    sigma='auto' (non-blind models): every frame's noise-map plane holds that frame's own estimate, times sigma_gain, computed on the
-    device (``frame_io.estimate_sigma``: what is known about it, and that YUV sources with subsampled chroma read low).
-    sigma='nlf' or a ``frame_io.NoiseCurve`` (non-blind models): a per-pixel noise map from every frame's own noise-level function, or from
-    the caller's curve (``frame_io.estimate_noise_curve`` / ``fill_noise_map``: what is known about them).
-    pix_fmt one of the RGB names of the module docstring ('bgra', 'rgba64le', 'gbrp10le', ...): clips are [T,...] arrays of self-describing
-    frames (or [T, n] tight samples with frame_shape), colour={'full_range': bool}; the clip's alpha codes stay on the device beside the
-    clip and come back with their frames.
-    cuts='auto': the scene starts of every clip are detected on the device (``frame_io.scene_cuts`` at ``cut_threshold``; its docstring says
-    what is known about the rule -- nothing on real footage -- and its blind spot: a cut one or two frames after another scores low) and
-    handed to the model's forward, which runs every scene as a clip of its own.  The detection reads T integers back before the forward is
-    enqueued: the host waits for the clip's upload and conversion there.  ``last_cuts``: the cuts of the most recent clip submitted.
-    strength (a number or (luma, chroma), each in [0, 1]; default 1): how much of the denoising to keep -- the network's result is blended
-    with the clip's own input on the device before it is encoded (``frame_io.blend_output``; luma weights: the stream's matrix, BT.709 for
-    RGB formats, or ``luma_matrix``).  dither None | 'ordered' | 'random' with dither_seed: dither at the encoder's quantiser
-    (``frame_io.output_to_*``); the random pattern's frame index counts the frames submitted since construction.
-    vst (with sigma=None) a ``frame_io.NoiseCurve`` | 'scene', vst_floor: the variance-stabilising transform of the module docstring around
-    the network.  'scene': the clip's scenes are its ``last_cuts`` with cuts='auto', otherwise the clip is one scene; each scene's curve is
-    estimated from its first frame alone (times sigma_gain), so a curve that drifts within a scene (auto-exposure) is not followed until
-    the next cut.  Table sets are per frame in one forward and one inverse launch; ``strength`` blends with the untransformed source.  A
-    blind model gets the transform and no plane.  What is known: ``frame_io.build_vst``.
-    grain None | ``frame_io.GrainModel`` | 'scene', grain_amount, grain_seed: film grain from a model, after the inverse transform and the
-    strength blend, before the encoder (module docstring).  'scene': the clip's scenes are its ``last_cuts`` with cuts='auto', otherwise
-    the clip is one scene; the first frame of each scene is measured against the clip's own input (the host waits once per scene) and the
-    model is used for the scene's frames.  The pattern's frame index counts the frames submitted since construction.
-    ``last_grain_model``: the latest model.  The defaults launch nothing new and give the bytes they gave."""
+class _Pipeline:
+    """What ClipPipeline and LiveStream share: the options of the module docstring, checked in one order before anything touches a
+    device; the three streams; and the chain from the network's result to the surface."""
 
-    def __init__(self, model, sigma=None, depth=2, pix_fmt="rgb24", colour=None, pad=None, frame_shape=None, sigma_gain=1.0, cuts=None,
-                 cut_threshold=CUT_THRESHOLD, strength=1.0, dither=None, dither_seed=0, luma_matrix=None, vst=None, vst_floor=VST_FLOOR,
-                 grain=None, grain_amount=1.0, grain_seed=0):
+    def __init__(self, what, model, sigma, depth, pix_fmt, colour, pad, frame_shape, sigma_gain, cuts, cut_threshold, strength, dither,
+                 dither_seed, luma_matrix, vst, vst_floor, grain, grain_amount, grain_seed):
         if depth < 1:
             raise ValueError("depth must be >= 1")
-        self.auto_cuts, self.cut_threshold = _check_cuts_mode(cuts, cut_threshold, "ClipPipeline")
-        self.last_cuts = None
-        self.sigma_gain = _check_sigma(model, sigma, sigma_gain, "ClipPipeline")
-        self.vst = _Vst(model, vst, vst_floor, sigma, "ClipPipeline")
+        self.auto_cuts, self.cut_threshold = _check_cuts_mode(cuts, cut_threshold, what)
+        self.sigma_gain = _check_sigma(model, sigma, sigma_gain, what)
+        self.vst = _Vst(model, vst, vst_floor, sigma, what)
         self.fmt = _pixel_format(pix_fmt, colour, pad, frame_shape)
         self.finish = _Finish(self.fmt, strength, dither, dither_seed, luma_matrix)
         self.grain = _Grain(grain, grain_amount, grain_seed, self.finish.matrix)
         self.last_grain_model = self.grain.model
-        self.alpha = getattr(self.fmt, "has_alpha", False)       # the clip's alpha codes ride beside the clip, [T,H,W] on the device
-        self.model, self.sigma = model, sigma
+        self.model, self.sigma, self.depth = model, sigma, depth
         self.device = model._device()
         if self.device.type != "cuda":
-            raise RuntimeError("ClipPipeline needs the model on a HIP device (model.cuda())")
+            raise RuntimeError("%s needs the model on a HIP device (model.cuda())" % what)
         with torch.cuda.device(self.device):
             self.up, self.comp, self.down = (torch.cuda.Stream(), torch.cuda.Stream(), torch.cuda.Stream())
+        self.count = 0
+
+    def _emit(self, y, geom, tables, src, alpha, grain):
+        """the chain behind the network, on the compute stream: the inverse transform with the table sets the frames went in with, the
+        strength blend with their source ``src``, grain -- ``grain(y, src, geom)``: each pipeline's own, which knows its scenes --, the dither
+        keywords, and the encoder with the frames' alpha codes"""
+        y = y.float()
+        if self.vst.active:
+            y = vst_inverse(y.contiguous(), tables)
+        if self.finish.blends:
+            y = self.finish.blend(y.contiguous(), src)
+        if self.grain.active:
+            y = grain(y.contiguous(), src, geom)
+        return self.fmt.to_output(y, geom, alpha=alpha, **self.finish.dither_kw(y.shape[0]))
+
+
+class ClipPipeline(_Pipeline):
+    """model: a bsvd_amd.BSVD on a HIP device; clips in, clips out, in submission order.  The options are the module docstring's (sigma:
+    the noise std in [0,1] units for the constant noise map, None for a blind model); what is ClipPipeline's own:
+
+    depth >= 2 overlaps the transfers of one clip with the forward of another.
+    Clips are arrays [T,...] of what the module docstring says a frame of ``pix_fmt`` is: [T,H,W,3] uint8 for 'rgb24', [T,H*3/2,pitch] for
+    'nv12' / 'p010', [T, n] tight samples with frame_shape=(H, W) for the planar, 4:2:2 and 4:4:4 YUV surfaces, [T,...] self-describing
+    frames (or [T, n] with frame_shape) for the RGB surfaces; the results have the shape and dtype of what was submitted.  The alpha codes
+    of a clip stay on the device beside the clip and come back with their frames.
+    sigma='auto' / 'nlf': every frame of a clip gets its own estimate; nothing is reported to the host.
+    cuts='auto': the scene starts of every clip are detected (``frame_io.scene_cuts`` at ``cut_threshold``) and handed to the model's
+    forward, which runs every scene as a clip of its own.  The detection reads T integers back before the forward is enqueued: the host
+    waits for the clip's upload and conversion there.  ``last_cuts``: the cuts of the most recent clip submitted.
+    strength blends with the clip's own input; the frame index of dither='random' and of the grain pattern counts the frames submitted
+    since construction.
+    vst='scene' / grain='scene': the clip's scenes are its ``last_cuts`` with cuts='auto', otherwise the clip is one scene.  Each scene's
+    curve is estimated from its first frame alone, and the table sets are per frame in one forward and one inverse launch.  The first
+    frame of each scene is measured against the clip's own input for the grain model: the host waits once per scene."""
+
+    def __init__(self, model, sigma=None, depth=2, pix_fmt="rgb24", colour=None, pad=None, frame_shape=None, sigma_gain=1.0, cuts=None,
+                 cut_threshold=CUT_THRESHOLD, strength=1.0, dither=None, dither_seed=0, luma_matrix=None, vst=None, vst_floor=VST_FLOOR,
+                 grain=None, grain_amount=1.0, grain_seed=0):
+        super().__init__("ClipPipeline", model, sigma, depth, pix_fmt, colour, pad, frame_shape, sigma_gain, cuts, cut_threshold, strength, dither,
+                         dither_seed, luma_matrix, vst, vst_floor, grain, grain_amount, grain_seed)
+        self.last_cuts = None
+        with torch.cuda.device(self.device):
             self.slots = [_Slot() for _ in range(depth)]
         self.pending = collections.deque()
-        self.count = 0
 
     # ------------------------------------------------------------------------------------------------
     def submit(self, frames_u8):
@@ -595,16 +629,14 @@ class ClipPipeline:
                 slot.uploaded.record()
             with torch.cuda.stream(self.comp):
                 self.comp.wait_event(slot.uploaded)
-                if self.alpha:
-                    x, slot.dev_alpha = self.fmt.to_input(slot.dev_in, geom, self.vst.sigma_in, self.sigma_gain, alpha=True)
-                else:
-                    x = self.fmt.to_input(slot.dev_in, geom, self.vst.sigma_in, self.sigma_gain)
+                # a format with alpha: the clip's alpha codes ride beside the clip, [T,H,W] on the device, held like dev_out
+                x, slot.dev_alpha = self.fmt.to_input(slot.dev_in, geom, self.vst.sigma_in, self.sigma_gain)
                 T, _, H, W = x.shape
                 kw = {}
                 if self.auto_cuts:
                     self.last_cuts = scene_cuts(x, self.cut_threshold, picture=(geom.h, geom.w))
                     kw = dict(cuts=self.last_cuts)
-                src = x
+                src, tables = x, None
                 if self.vst.active:
                     if self.finish.blends or self.grain.scene:
                         src = x[:, :3].clone()            # strength blends, and grain is measured, in the picture's own domain
@@ -614,16 +646,8 @@ class ClipPipeline:
                     y = self.model.clip_forward(x, **kw)
                 else:
                     y = self.model.streaming_forward(x, **kw)
-                y = y.float()
-                if self.vst.active:
-                    y = vst_inverse(y.contiguous(), tables)
-                if self.finish.blends:
-                    y = self.finish.blend(y.contiguous(), src)
-                if self.grain.active:
-                    y = self._clip_grain(y.contiguous(), src, geom)
-                kw = self.finish.dither_kw(T)
                 # held by the slot until its download completed
-                slot.dev_out = self.fmt.to_output(y, geom, alpha=slot.dev_alpha, **kw) if self.alpha else self.fmt.to_output(y, geom, **kw)
+                slot.dev_out = self._emit(y, geom, tables, src, slot.dev_alpha, self._clip_grain)
                 slot.computed.record()
             with torch.cuda.stream(self.down):
                 self.down.wait_event(slot.computed)
@@ -671,7 +695,7 @@ class ClipPipeline:
         yield from self.results()
 
 
-class LiveStream:
+class LiveStream(_Pipeline):
     """One live feed through the per-frame streaming API (``BSVD.feedin_one_element``, bsvd_arch.py:485-488) with uint8 frames
     on the host side: the streaming counterpart of ``ClipPipeline``.
 
@@ -690,34 +714,24 @@ class LiveStream:
     submission order and are byte-identical in every mode.  Not re-entrant (one stream per instance, like the reference's
     module state).
 
-    pix_fmt 'nv12' / 'p010' (with ``colour``, a ``Colour`` or a dict of its fields): feed takes and returns uint8 / uint16 surfaces
-    [H*3/2,pitch] instead, converted by ``bsvd_yuv420_to_planar`` / ``bsvd_planar_to_yuv420``; everything else is the same.
+    The options are the module docstring's; what is the stream's own:
 
-    pix_fmt 'yuv420p', 'yuv420p10le', 'uyvy422', 'yuyv422', 'nv16', 'p210le', 'yuv422p', 'yuv422p10le', 'yuv444p', 'yuv444p10le' (the
-    planar, 4:2:2 and 4:4:4 surfaces; ``frame_shape`` is required): feed takes and returns 1-D arrays of the tight frame's samples
-    (uint8, uint16 for 10 bit) -- the bytes ``ffmpeg -f rawvideo`` emits --, converted by ``bsvd_yuv_to_planar`` / ``bsvd_planar_to_yuv``.
+    feed takes and returns one frame of ``pix_fmt`` as the module docstring describes it ([H*3/2,pitch] surfaces for 'nv12' / 'p010', 1-D
+    tight samples for the planar, 4:2:2 and 4:4:4 YUV surfaces -- ``frame_shape`` is required --, self-describing arrays or, with
+    ``frame_shape``, 1-D tight samples for the RGB surfaces); with pad='reflect' latency is the same and frames come back in the fed
+    shape.  What waits on the device for frame k's result, ``latency`` feeds later, waits in a ring of ``latency + depth`` entries
+    (``_Ring``), allocated with the slots, filled on the decode's side and consumed in order on the encode's, through ``cut=True``,
+    cuts='auto' and ``flush()``; nothing is allocated per feed:
+      alpha       a picture-sized plane of codes per entry: the frame returned for source frame k carries frame k's alpha bit for bit;
+      strength    below 1 (and grain='scene'): frame k's three colour planes at network size, 3 fp32 planes per entry -- about 0.5 GB at
+                  1080p --, blended with frame k's result when that emerges;
+      vst='scene' the table set frame k was transformed with (8 KB per entry).
 
-    pix_fmt one of the RGB names of the module docstring ('bgr24', 'bgra', 'rgba64le', 'x2rgb10le', 'gbrp10le', ...): feed takes and returns
-    self-describing arrays ([H,W,3|4], [H,W] uint32, [P,H,W]) or, with ``frame_shape``, 1-D tight samples, converted by
-    ``bsvd_rgb_to_planar`` / ``bsvd_planar_to_rgb``.  Alpha rides with its frame: the frame returned for source frame k carries frame k's
-    alpha codes bit for bit, ``latency`` feeds later, through ``cut=True`` and ``flush()`` -- a ring of ``latency + depth`` picture-sized
-    planes on the device, allocated with the slots, filled by the decode and consumed in order by the encode; nothing is allocated per feed.
-
-    pad None | 'reflect': 'reflect' takes frames of any size (even H and W for YUV): reflect-padded to the next multiples of 4 and cropped
-    again on the device, same latency, frames back in the fed shape.
-
-    sigma='auto' (non-blind models): the noise-map plane of every frame holds that frame's own estimate, times ``sigma_gain``, computed on
-    the compute stream between the conversion and the pipeline step (``frame_io.estimate_sigma``); latency, slot ring and stream order are
-    what they are with a float.  ``last_sigma``: the estimate (a float, [0,1] units) of the most recent input step ``feed`` has already
-    waited for -- i.e. of the frame fed ``depth - 1`` calls ago --, None before that; it comes down on the download stream into the slot's
-    pinned memory beside the frame and is never read earlier.  Nothing is known about the estimate on real footage, and YUV sources with
-    subsampled chroma read low (``sigma_gain``).
-
-    sigma='nlf' (non-blind models): the noise-map plane of every frame is that frame's own per-pixel map, written from its noise-level
-    function (``frame_io.estimate_noise_curve`` / ``fill_noise_map``, times ``sigma_gain``), on the same stream at the same place.
-    ``last_noise_curve``: the sixteen values of the most recent input step ``feed`` has already waited for, None before that; ``last_sigma``
-    stays None.  sigma=``frame_io.NoiseCurve``: the map is written from the caller's curve and nothing is reported.  Nothing is known
-    about either on real footage.
+    sigma='auto' / 'nlf' run on the compute stream between the conversion and the pipeline step; latency, slot ring and stream order are
+    what they are with a float.  ``last_sigma`` ('auto'; a float, [0,1] units), ``last_noise_curve`` ('nlf' and vst='scene'; sixteen
+    values) and ``last_vst_sigma`` (vst): the values of the most recent input step ``feed`` has already waited for -- i.e. of the frame
+    fed ``depth - 1`` calls ago --, None before that and None for what the stream does not estimate (sigma='nlf' leaves ``last_sigma``
+    None); they come down on the download stream into the slot's pinned memory beside the frame and are never read earlier.
 
     Scene cuts.  ``feed(frame, cut=True)`` says that ``frame`` starts a new scene: no temporal-fusion conv mixes it with the frames before it
     (each side sees zeros for the other, as at a stream's ends), nothing is flushed and no feed returns None because of it.  The steps a cut
@@ -727,86 +741,47 @@ class LiveStream:
     waits for them before it plans the step -- the step before is already enqueued, so ``depth >= 2`` keeps its overlap.  A frame whose score
     (``frame_io.scene_cuts``' rule, carried from frame to frame) reaches ``cut_threshold`` starts a scene.  ``last_cut_score`` /
     ``last_cut``: score and decision of the most recent frame fed.  ``flush()`` forgets the previous frame.  With cuts=None the stream order
-    is what it always was.  Nothing is known about the rule on real footage, the default threshold has met none, and a cut one or two
-    frames after another cut scores low (``frame_io.scene_cuts``).
+    is what it always was.
 
-    strength (a number or (luma, chroma), each in [0, 1]; default 1) and dither None | 'ordered' | 'random' with dither_seed: the output
-    finish, on the device.  Frame k's source -- its three colour planes at network size -- waits in a ring of ``latency + depth`` slots
-    (3 fp32 planes each: about 0.5 GB at 1080p) and is blended with frame k's result when that emerges ``latency`` feeds later
-    (``frame_io.blend_output``), through ``cut=True`` and ``flush()`` like the alpha ring; the ring exists only when some strength is
-    below 1, and nothing is allocated per feed.  The random dither's frame index counts the frames emitted since construction or the last
-    ``flush()``.
-
-    vst (with sigma=None) a ``frame_io.NoiseCurve`` | 'scene', vst_floor: the variance-stabilising transform of the module docstring, on
-    the compute stream: after the conversion, the source ring's copy of the untransformed planes and the cut decision come curve, build and
-    forward, then the pipeline step; what emerges goes through the inverse, then the strength blend (in the picture's own domain:
-    strength=0 still returns the source) and the encoder.  A NoiseCurve: one table set for the stream, built once; every frame's noise
-    plane is sigma'; a curve that is flat after the clamp to [vst_floor, 1] is the identity: nothing is launched and the plane is written
-    as sigma=<that value> writes it.  'scene': the frame that starts a scene -- the first feed after construction or ``flush()``, a
-    ``feed(frame, cut=True)`` frame, a frame cuts='auto' flags -- gets its curve from ``frame_io.estimate_noise_curve`` (times sigma_gain)
-    and a table set built from it; every later frame of the scene uses that set.  A scene's curve comes from its first frame alone: a curve
-    that drifts within a scene (auto-exposure) is not followed until the next cut.  Frame k's set waits for frame k's result in a ring of
-    ``latency + depth`` sets (8 KB each), like the alpha ring, allocated with the slots.  ``last_noise_curve`` ('scene') and
-    ``last_vst_sigma``: the scene's curve and the sigma' of the most recent input step ``feed`` has already waited for.  A blind model
-    gets the transform and no plane.  What is known: ``frame_io.build_vst`` -- nothing about denoising quality, nothing on real footage.
-
-    grain None | ``frame_io.GrainModel`` | 'scene', grain_amount (default 1), grain_seed: film grain from a model (module docstring), on the
-    compute stream after the inverse transform and the strength blend and before the encoder and its dither.  A GrainModel: every frame
-    gets grain from it (``frame_io.apply_grain``); the block offsets are hashed from (grain_seed, the frames emitted since construction or
-    the last ``flush()``, the block).  'scene': whether a frame starts a scene -- the first feed after construction or ``flush()``,
-    ``cut=True``, a frame cuts='auto' flags -- is noted when it is fed; when the first frame of a scene EMERGES, ``latency`` feeds later,
-    its source (from the source ring, which exists for grain='scene' as it does for a strength below 1) and its result are measured
-    (``frame_io.estimate_grain``), the HOST WAITS for the 2 KB of statistics and fits the model -- once per scene, about the figures of
-    profiles/film_grain.txt --, and that model is used from that frame to the scene's last.  ``last_grain_model``: the latest model.  With
-    a strength below 1 the measured result is the blended one: the model describes what is still missing.  No temporal pooling beyond
-    the scene's first frame, no overlap blending of grain blocks, nothing measured on real footage.
-
-    The defaults launch nothing new and give the bytes they gave."""
+    A scene starts with the first feed after construction or ``flush()``, a ``feed(frame, cut=True)`` frame, or a frame cuts='auto' flags.
+    vst, on the compute stream: after the conversion, the source ring's copy of the untransformed planes and the cut decision come curve,
+    build and forward, then the pipeline step; what emerges goes through the inverse, then the strength blend and the encoder.  A
+    NoiseCurve: one table set for the stream, built once.  'scene': the frame that starts a scene gets its curve and a table set built
+    from it, and every later frame of the scene uses that set.
+    grain, on the compute stream: 'scene' notes whether a frame starts a scene when it is fed; when the first frame of a scene EMERGES,
+    ``latency`` feeds later, its source (from the source ring) and its result are measured, the HOST WAITS for the 2 KB of statistics
+    and fits the model -- once per scene --, and that model is used from that frame to the scene's last.
+    The frame index of dither='random' and of the grain pattern counts the frames emitted since construction or the last ``flush()``."""
 
     def __init__(self, model, sigma=None, depth=2, overlap_blocks=None, frame_shape=None, pix_fmt="rgb24", colour=None, pad=None,
                  sigma_gain=1.0, cuts=None, cut_threshold=CUT_THRESHOLD, strength=1.0, dither=None, dither_seed=0, luma_matrix=None,
                  vst=None, vst_floor=VST_FLOOR, grain=None, grain_amount=1.0, grain_seed=0):
         """frame_shape: optional (H, W) of the frames to come (the picture, also with ``pad``) -- the overlap decision (and with it
         ``latency``) is then final at construction instead of at the first feed."""
-        if depth < 1:
-            raise ValueError("depth must be >= 1")
-        self.auto_cuts, self.cut_threshold = _check_cuts_mode(cuts, cut_threshold, "LiveStream")
+        super().__init__("LiveStream", model, sigma, depth, pix_fmt, colour, pad, frame_shape, sigma_gain, cuts, cut_threshold, strength, dither,
+                         dither_seed, luma_matrix, vst, vst_floor, grain, grain_amount, grain_seed)
         self.last_cut_score, self.last_cut = None, False
         self._grids = self._sad = self._pin_sad = None       # cuts='auto': two alternating grid buffers, the step's sum on the device and pinned
         self._have_prev, self._prev_mafd, self._n_scored = False, 0.0, 0
-        self.sigma_gain = _check_sigma(model, sigma, sigma_gain, "LiveStream")
-        self.vst = _Vst(model, vst, vst_floor, sigma, "LiveStream")
-        self.last_vst_sigma = None
         self._tables = self._scene_tables = self._scene_curve = None    # vst='scene': the ring of table sets, the current scene's set and curve
         self._in_scene = False
         self.auto_sigma = isinstance(sigma, str) and sigma == "auto"
         self.nlf_sigma = isinstance(sigma, str) and sigma == "nlf"
-        self.last_sigma = None
-        self.last_noise_curve = None
-        self.fmt = _pixel_format(pix_fmt, colour, pad, frame_shape)
+        self._side = [row for row in _SIDE_VALUES if row[3](self)]     # the values this stream brings down beside its frames
+        self.last_sigma = self.last_noise_curve = self.last_vst_sigma = None
         self._alpha = None                                    # formats with alpha: the ring of alpha planes (_AlphaRing), allocated with the slots
-        self.finish = _Finish(self.fmt, strength, dither, dither_seed, luma_matrix)
         self._source = None                                   # strength < 1 or grain='scene': the ring of source frames (_SourceRing), allocated with the slots
-        self.grain = _Grain(grain, grain_amount, grain_seed, self.finish.matrix)
-        self.last_grain_model = self.grain.model
         self._scene_starts = collections.deque()             # grain='scene': per frame inside the network, does it start a scene?
         self._grain_in_scene = False
-        self.model, self.sigma, self.depth = model, sigma, depth
         self._overlap_wanted = (depth >= 2) if overlap_blocks is None else bool(overlap_blocks)
         self._overlap_explicit = overlap_blocks is not None
         self.overlap = self._overlap_wanted
         self._overlap_decided = not self._overlap_wanted     # nothing to decide without the lagged schedule
-        self.device = model._device()
-        if self.device.type != "cuda":
-            raise RuntimeError("LiveStream needs the model on a HIP device (model.cuda())")
-        with torch.cuda.device(self.device):
-            self.up, self.comp, self.down = (torch.cuda.Stream(), torch.cuda.Stream(), torch.cuda.Stream())
         self.slots, self.shape, self.geom = None, None, None
         self.inflight = collections.deque()          # (slot, has_output, has_sigma) in submission order
-        self.count = 0
         model.reset()
         if frame_shape is not None:
-            h, w = int(frame_shape[0]), int(frame_shape[1])
+            h, w = _frame_shape(frame_shape)
             self._decide_overlap(*(_padded_size(h, w, "frame_shape") if pad else (h, w)))
 
     @property
@@ -847,22 +822,15 @@ class LiveStream:
             s.pin_in = torch.empty(geom.staging, dtype=torch.uint8).pin_memory()
             s.pin_out = torch.empty(geom.staging, dtype=torch.uint8).pin_memory()
             s.dev_in = torch.empty((1,) + geom.staging, dtype=torch.uint8, device=self.device)
-            if self.auto_sigma:
-                s.pin_sigma = torch.zeros(1, dtype=torch.float32).pin_memory()
-                s.dev_sigma = torch.empty(1, dtype=torch.float32, device=self.device)
-            if self.nlf_sigma or self.vst.scene:
-                s.pin_curve = torch.zeros(_lib.NLF_LEVELS, dtype=torch.float32).pin_memory()
-                s.dev_curve = torch.empty(_lib.NLF_LEVELS, dtype=torch.float32, device=self.device)
-            if self.vst.active:
-                s.pin_vsig = torch.zeros(1, dtype=torch.float32).pin_memory()
-                s.dev_vsig = torch.empty(1, dtype=torch.float32, device=self.device)
+            for name, n, _, _ in self._side:
+                s.side[name] = _Side(torch.empty(n, dtype=torch.float32, device=self.device), torch.zeros(n, dtype=torch.float32).pin_memory())
             self.slots.append(s)
         if self.vst.scene:
             self._tables = _TableRing(self.latency + self.depth, self.device)
             self._scene_tables = torch.empty((1, VST_TABLE_FLOATS), dtype=torch.float32, device=self.device)
             self._scene_curve = torch.empty((1, _lib.NLF_LEVELS), dtype=torch.float32, device=self.device)
             self._in_scene = False
-        if getattr(self.fmt, "has_alpha", False):
+        if self.fmt.has_alpha:
             self._alpha = _AlphaRing(self.latency + self.depth, geom.h, geom.w, getattr(torch, self.fmt.dtype.name), self.device)
         self._source = _SourceRing(self.latency + self.depth, geom.net_h, geom.net_w, self.device) if self.finish.blends or self.grain.scene else None
         if self.auto_cuts:
@@ -898,14 +866,11 @@ class LiveStream:
     def _to_input(self, slot):
         """the slot's frame -> the network input; a format with alpha leaves the frame's alpha codes in the ring's next plane"""
         sigma = 0.0 if self.nlf_sigma else self.vst.sigma_in
-        if self._alpha is None:
-            x = self.fmt.to_input(slot.dev_in, self.geom, sigma, self.sigma_gain)
-        else:
-            x = self.fmt.to_input(slot.dev_in, self.geom, sigma, self.sigma_gain, alpha=self._alpha.next_in())[0]
+        x, _ = self.fmt.to_input(slot.dev_in, self.geom, sigma, self.sigma_gain, alpha=self._alpha.next_in() if self._alpha is not None else None)
         if self.nlf_sigma:                                   # what sigma='nlf' does inside to_input, with the curve kept for the host
             curve = estimate_noise_curve(x, picture=(self.geom.h, self.geom.w), gain=self.sigma_gain)
             fill_noise_map(x, curve)
-            slot.dev_curve.copy_(curve[0])
+            slot.side["curve"].dev.copy_(curve[0])
         if self._source is not None:
             self._source.next_in().copy_(x[:, :3])          # the frame's colour planes wait for its denoised self
         return x
@@ -921,41 +886,36 @@ class LiveStream:
                 self._in_scene = True
             tables = self._tables.next_in()
             tables.copy_(self._scene_tables)                 # frame k's set waits for frame k's result
-            slot.dev_curve.copy_(self._scene_curve[0])
+            slot.side["curve"].dev.copy_(self._scene_curve[0])
         else:
             tables = self.vst.shared_tables(self.device)
-        slot.dev_vsig.copy_(vst_sigma(tables))
+        slot.side["vsig"].dev.copy_(vst_sigma(tables))
         vst_forward(x, tables, fill_plane=self.vst.fills)
 
     def _to_output(self, y):
         """what a step emitted -> the surface; frames come out in the order they went in, and so do their alpha planes"""
-        y = y.float()
+        tables = None
         if self.vst.active:
-            y = vst_inverse(y.contiguous(), self._tables.next_out() if self.vst.scene else self.vst.shared_tables(self.device))
+            tables = self._tables.next_out() if self.vst.scene else self.vst.shared_tables(self.device)
         src = self._source.next_out() if self._source is not None else None
-        if self.finish.blends:
-            y = self.finish.blend(y.contiguous(), src)
-        if self.grain.active:
-            y = y.contiguous()
-            if self.grain.scene and self._scene_starts.popleft():    # the scene's first frame emerges: measure, wait, fit
-                self.last_grain_model = self.grain.measure(src, y, (self.geom.h, self.geom.w))
-            self.grain.apply(y, self.grain.emitted)
-            self.grain.emitted += y.shape[0]
-        kw = self.finish.dither_kw(y.shape[0])
-        if self._alpha is None:
-            return self.fmt.to_output(y, self.geom, **kw)
-        return self.fmt.to_output(y, self.geom, alpha=self._alpha.next_out(), **kw)
+        return self._emit(y, self.geom, tables, src, self._alpha.next_out() if self._alpha is not None else None, self._stream_grain)
+
+    def _stream_grain(self, y, src, geom):
+        """grain onto the frame that emerges, in place: the caller's model, or with grain='scene' the scene's own"""
+        if self.grain.scene and self._scene_starts.popleft():        # the scene's first frame emerges: measure, wait, fit
+            self.last_grain_model = self.grain.measure(src, y, (geom.h, geom.w))
+        self.grain.apply(y, self.grain.emitted)
+        self.grain.emitted += y.shape[0]
+        return y
 
     def _pop(self):
         """oldest in-flight step -> its uint8 frame, or None if that step emitted nothing (pipeline fill)"""
         slot, has_out, has_sigma = self.inflight.popleft()
         slot.downloaded.synchronize()
-        if has_sigma and self.auto_sigma:
-            self.last_sigma = float(slot.pin_sigma[0])
-        if has_sigma and (self.nlf_sigma or self.vst.scene):
-            self.last_noise_curve = [float(v) for v in slot.pin_curve]
-        if has_sigma and self.vst.active:
-            self.last_vst_sigma = float(slot.pin_vsig[0])
+        if has_sigma:
+            for name, n, attr, _ in self._side:
+                pin = slot.side[name].pin
+                setattr(self, attr, float(pin[0]) if n == 1 else [float(v) for v in pin])
         return slot.pin_out.numpy().copy().view(self.fmt.dtype).reshape(self.shape) if has_out else None
 
     def _step(self, frame_u8, last=False, cut=False):
@@ -979,7 +939,7 @@ class LiveStream:
                     if x is None:
                         x = self._to_input(slot)
                     if self.auto_sigma:
-                        slot.dev_sigma.copy_(x[0, -1, 0, :1])          # the plane holds the estimate: one element of it, device to device
+                        slot.side["sigma"].dev.copy_(x[0, -1, 0, :1])          # the plane holds the estimate: one element of it, device to device
                     if self.vst.active:
                         self._vst_forward(slot, x, cut)
                     if self.grain.scene:
@@ -994,14 +954,11 @@ class LiveStream:
                 self.down.wait_event(slot.computed)
                 if y is not None:
                     slot.pin_out.copy_(slot.dev_out[0], non_blocking=True)
-                if self.auto_sigma and frame_u8 is not None:
-                    slot.pin_sigma.copy_(slot.dev_sigma, non_blocking=True)
-                if (self.nlf_sigma or self.vst.scene) and frame_u8 is not None:
-                    slot.pin_curve.copy_(slot.dev_curve, non_blocking=True)
-                if self.vst.active and frame_u8 is not None:
-                    slot.pin_vsig.copy_(slot.dev_vsig, non_blocking=True)
+                if frame_u8 is not None:
+                    for side in slot.side.values():
+                        side.pin.copy_(side.dev, non_blocking=True)
                 slot.downloaded.record()
-        self.inflight.append((slot, y is not None, (self.auto_sigma or self.nlf_sigma or self.vst.active) and frame_u8 is not None))
+        self.inflight.append((slot, y is not None, bool(self._side) and frame_u8 is not None))
 
     def _drain(self, keep, outs):
         while len(self.inflight) > keep:

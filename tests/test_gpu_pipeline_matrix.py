@@ -337,7 +337,7 @@ def _m_curve_of_wrong_slot(mp, P):
         other = self.slots[(self.slots.index(slot) - 1) % len(self.slots)]
         r = pop(self)
         if has_sigma and self.nlf_sigma:
-            self.last_noise_curve = [float(v) for v in other.pin_curve]
+            self.last_noise_curve = [float(v) for v in other.side["curve"].pin]
         return r
     mp.setattr(P.LiveStream, "_pop", _pop)
 
